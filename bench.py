@@ -14,12 +14,14 @@ sum of steps over ranks divided by the max-over-ranks wall time (weak scaling).
 Packed seeds: ``--seeds-per-gpu K`` packs K independent learners into each
 GPU's handle for the timed region (cfg.seeds = K: every launch of the update
 graph runs all K, grid z = seed) and ``value`` counts every seed's updates.
-The default keeps one learner per GPU and adds a ``packed_seeds`` leg (8 seeds
-per GPU for hc) measured after the timed region.
 
-Extra JSON fields: ``roofline`` for the dominant kernel (HIP-event timed in
-this process) and ``cpu_baseline`` (the CPU oracle port on the host cores,
-rank 0 at N=1, bounded sample).
+A plain run sets up, warms up, times ``--steps`` updates, writes the learner's
+outputs if ``--dump-outputs DIR`` is given, and prints the result line.
+``--full`` adds every secondary leg after the timed region: ``roofline`` for
+the dominant kernel (HIP-event timed in this process), ``cpu_baseline`` (the
+CPU oracle port on the host cores, rank 0 at N=1, bounded sample), the drop-in
+loop, the world-model legs, a ``packed_seeds`` leg (one learner per GPU in the
+timed region, then 8 seeds per GPU for hc) and, at N > 1, the C4 RCCL leg.
 """
 from __future__ import annotations
 
@@ -499,6 +501,27 @@ def packed_leg(cfgd, config, rep, k, steps, with_roofline):
     return out
 
 
+def dump_outputs(eng, K, out_dir, tag=""):
+    """``--dump-outputs``: what a caller of the timed ``step(steps)`` holds after its last update,
+    one ``<name>.npy`` per array: the last row of the statistics ring (``stats``, float64: q1_loss,
+    q2_loss, p_loss, alpha_loss, alpha, mse_loss, nlp_mean, step), the temperature variable
+    (``alpha``) and every trained network's ``get_net`` list (``<net>.<i>``: W0, b0, W1, b1, ...,
+    float32, whole).  A few MB at every config.  Packed seeds are written as ``seed<k>.<name>``,
+    ranks of an N > 1 run as ``rank<r>.<name>``.  The seeds of build_engine fix every input, so
+    two builds run with the same arguments are comparable array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k in range(K):
+        eng.select_seed(k)
+        pre = tag + (f"seed{k}." if K > 1 else "")
+        arrays = {"stats": np.asarray(eng.stats(1)[0], np.float64), "alpha": np.array([eng.alpha()], np.float64)}
+        for net in ("actor", "q0", "q1", "t0", "t1"):
+            for i, w in enumerate(eng.get_net(net)):
+                arrays[f"{net}.{i}"] = np.asarray(w, np.float32)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, pre + name + ".npy"), a)
+    eng.select_seed(0)
+
+
 def _ranks_cmd(n, argv):
     import socket
     with socket.socket() as s:
@@ -649,6 +672,13 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", default="hc", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every secondary leg: roofline, CPU baseline, drop-in "
+                         "loop, world-model legs, packed seeds and (N > 1) the C4 RCCL leg; the --no-* and "
+                         "--packed-leg options below choose among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the learner's state of the last step (statistics row, "
+                         "alpha, every trained network) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -659,10 +689,10 @@ def main():
                     help="independent learners packed into each GPU's handle for the timed region "
                          "(one launch chain, grid z = seed); value counts the updates of every seed")
     ap.add_argument("--packed-leg", type=int, default=-1,
-                    help="after the timed region, also time K packed seeds per GPU and report them as "
+                    help="--full: after the timed region, also time K packed seeds per GPU and report them as "
                          "packed_seeds (default 8 for hc, 4 for the Humanoid configs; 0 = off)")
     ap.add_argument("--no-dp-leg", action="store_true",
-                    help="N > 1: skip the C4 data-parallel RCCL leg (a child launch of --mode dpcheck)")
+                    help="--full at N > 1: skip the C4 data-parallel RCCL leg (a child launch of --mode dpcheck)")
     ap.add_argument("--plan-only", action="store_true",
                     help="no GPU: every rank joins a gloo group and prints its rank and seeds (launch check)")
     args = ap.parse_args()
@@ -723,32 +753,35 @@ def main():
     stats = eng.stats(1)[0]
     finite = bool(np.all(np.isfinite(stats)))
     value = args.steps * (1 if dp else ws * K) / el     # dp: every rank runs the same global update
-    # secondary legs on rank 0, after the timed region; the roofline leg last (its ablated
-    # graph replay leaves the learner's state meaningless)
+    if args.dump_outputs and (rank == 0 or not dp):     # dp: every rank holds the same learner
+        dump_outputs(eng, K, args.dump_outputs, f"rank{rank}." if ws > 1 and not dp else "")
+    # secondary legs (--full) on rank 0, after the timed region; the roofline leg last (its
+    # ablated graph replay leaves the learner's state meaningless)
+    full = args.full
     loop = None
-    if rank == 0 and K == 1 and not dp and not args.no_roofline:
+    if full and rank == 0 and K == 1 and not dp and not args.no_roofline:
         loop = drop_in_loop(eng, cfgd)
     fit = roll = None
-    if rank == 0 and cfgd["use_expert"] and K == 1:
+    if full and rank == 0 and cfgd["use_expert"] and K == 1:
         fit, roll = world_model_legs(eng, cfgd)
     mfit = None
-    if rank == 0 and not args.no_roofline and not dp and K == 1 and args.config == "hc":
+    if full and rank == 0 and not args.no_roofline and not dp and K == 1 and args.config == "hc":
         mfit = model_fit_leg(rep)
     roof = None
-    if rank == 0 and not args.no_roofline and not dp:
+    if full and rank == 0 and not args.no_roofline and not dp:
         roof, _ = roofline(eng, args.config)
     packed = None
     nleg = args.packed_leg if args.packed_leg >= 0 else (8 if args.config == "hc" else 4)
-    if not dp and K == 1 and nleg > 1:
+    if full and not dp and K == 1 and nleg > 1:
         eng.close()
         eng = None
         packed = packed_leg(cfgd, args.config, rep, nleg, min(args.steps, 1024), rank == 0 and not args.no_roofline)
     cpu = None
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline and not dp:
+    if full and rank == 0 and ws == 1 and not args.no_cpu_baseline and not dp:
         cpu = cpu_baseline(cfgd, args.cpu_seconds)
     group_ws = rep.dist.get_world_size() if rep.dist is not None else 1
     dpres = None
-    if ws > 1 and not dp and not args.no_dp_leg:
+    if full and ws > 1 and not dp and not args.no_dp_leg:
         # config C4 over RCCL: every replica rank releases its GPU, rank 0 starts the ws-rank
         # dpcheck launch (its own group), waits for it (bounded), then prints the line
         import torch

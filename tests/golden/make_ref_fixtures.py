@@ -150,8 +150,10 @@ def make_logger(tmp):
         inp["setup_kwargs"] = {"import_path": HERE, "import_file": "ref_runs.pkl", "import_idx": c["import_idx"],
                                "import_all": c["import_all"], "idx": c["idx"], "runs_start": 0}
         inp["env_kwargs"] = {"env_name": "mine"}
-        out = import_inputs(inp)
-        cases.append(dict(case=c, out=_jsonable(out)))
+        out = _jsonable(import_inputs(inp))
+        assert out["setup_kwargs"]["import_path"] == HERE
+        out["setup_kwargs"]["import_path"] = "<golden>"      # wherever the checkout lies (the test puts its own back)
+        cases.append(dict(case=c, out=out))
     # organize_rms_inputs on the flat keys of older logs (train_utils.py:94-129)
     flat = {f"{k}_{f}": (rs.normal(size=3).astype(np.float32) if f != "t" else 4)
             for k in ("s", "a", "r", "delta", "ret") for f in ("t", "mean", "var")}

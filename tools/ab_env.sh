@@ -6,7 +6,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${TAG:-ab}
 mkdir -p $OUT
-BA="--no-cpu-baseline --packed-leg 0 ${BENCH_ARGS:-}"
+BA="--full --no-cpu-baseline --packed-leg 0 ${BENCH_ARGS:-}"
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in on off; do
     if [ $v = off ]; then export $AB_VAR=0; else unset $AB_VAR; fi

@@ -32,7 +32,7 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1
       rc=$?; echo "[$n smoke] rc=$rc $(tail -n 1 "$log")" ;;
     bench)
-      timeout -k 10 500 python bench.py $arg > "$log" 2>&1
+      timeout -k 10 500 python bench.py --full $arg > "$log" 2>&1
       rc=$?; echo "[$n bench $arg] rc=$rc $(value "$log")" ;;
     driver)     # the driver's own command
       timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$log" 2>&1
@@ -48,13 +48,13 @@ for step in "$@"; do
       env "$arg" timeout -k 10 200 python tools/step_overhead.py > "$log" 2>&1
       rc=$?; echo "[$n overheadenv $arg] rc=$rc"; grep -E "n=  20 launch|fit:" "$log" ;;
     n2shared)   # bench --gpus 2 with both ranks on the one visible GPU (gloo replicas; the C4 leg skips)
-      SACX_SHARE_DEVICE=1 SACX_REPLICA_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 400 --warmup 50 \
+      SACX_SHARE_DEVICE=1 SACX_REPLICA_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 400 --warmup 50 \
           --no-cpu-baseline > "$log" 2>&1
       rc=$?; echo "[$n n2shared] rc=$rc $(value "$log")"; grep -o '"dp_c4": {[^}]*}' "$log" || true ;;
     cfgenv)     # bench of config C under one extra environment setting: cfgenv=C:VAR=VALUE (VAR=VALUE may be -)
       cfg=${arg%%:*}; ev=${arg#*:}
       if [ "$ev" = "-" ]; then ev="SACX_NOP=1"; fi
-      env $ev timeout -k 10 300 python bench.py --config $cfg --steps 1000 --warmup 100 --no-cpu-baseline > "$log" 2>&1
+      env $ev timeout -k 10 300 python bench.py --full --config $cfg --steps 1000 --warmup 100 --no-cpu-baseline > "$log" 2>&1
       rc=$?; echo "[$n cfgenv $arg] rc=$rc $(value "$log")" ;;
     mfitv)      # the fit timing with a variant library: mfitv=<tools/libvar name>
       { SACX_LIBPATH=$PWD/tools/libvar/libsacx_$arg.so timeout -k 10 200 python tools/model_fit_time.py hc_eo 512 && \
@@ -88,7 +88,7 @@ for step in "$@"; do
     humanoid)
       rc=0
       for c in humanoid_sac humanoid_bf16 humanoid_eo; do
-        timeout -k 10 300 python bench.py --config $c --steps 1000 --warmup 100 --no-cpu-baseline > "$OUT/$n-$c.log" 2>&1
+        timeout -k 10 300 python bench.py --full --config $c --steps 1000 --warmup 100 --no-cpu-baseline > "$OUT/$n-$c.log" 2>&1
         rc=$?; echo "[$n $c] rc=$rc $(value "$OUT/$n-$c.log")"; [ $rc -eq 0 ] || break
       done ;;
     prof)       # rocprofv3 kernel-trace stats of the one-seed bench of config $arg
@@ -130,10 +130,10 @@ for step in "$@"; do
       env "$ev" timeout -k 10 200 python tools/ktime_dump.py "$cfg" > "$log" 2>&1
       rc=$?; echo "[$n ktimecfgenv $arg] rc=$rc $(tail -n 1 "$log")" ;;
     benchenv)   # the 2,000-update bench under one extra environment setting: benchenv=VAR=VALUE
-      env "$arg" timeout -k 10 300 python bench.py --steps 2000 --warmup 200 --no-cpu-baseline > "$log" 2>&1
+      env "$arg" timeout -k 10 300 python bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline > "$log" 2>&1
       rc=$?; echo "[$n benchenv $arg] rc=$rc $(value "$log")" ;;
     benchv)     # the 2,000-update HC bench with a variant library: benchv=<tools/libvar name>
-      SACX_LIBPATH=$PWD/tools/libvar/libsacx_$arg.so timeout -k 10 300 python bench.py --steps 2000 --warmup 200 --no-cpu-baseline > "$log" 2>&1
+      SACX_LIBPATH=$PWD/tools/libvar/libsacx_$arg.so timeout -k 10 300 python bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline > "$log" 2>&1
       rc=$?; echo "[$n benchv $arg] rc=$rc $(value "$log")" ;;
     dropin)     # host time per drop-in iteration: dropin[=<tools/libvar name>]
       if [ -n "$arg" ]; then lp=$PWD/tools/libvar/libsacx_$arg.so; else lp=$PWD/sac-expert_amd/lib/libsacx.so; fi
