@@ -46,6 +46,21 @@ enum sacx_activation { SACX_ACT_RELU = 0, SACX_ACT_TANH = 1, SACX_ACT_ELU = 2 };
 enum sacx_dtype { SACX_F32 = 0, SACX_I32 = 1, SACX_I64 = 2, SACX_U32 = 3, SACX_F64 = 4 };
 enum sacx_role { SACX_ROLE_WORK = 0, SACX_ROLE_PARAM = 1, SACX_ROLE_TARGET = 2, SACX_ROLE_STATE = 3 };
 
+/* sacx_config.use_expert.  Any non-zero value means "world models exist": the arena layout, the
+   models' normaliser set, sacx_model_fit, sacx_rollout, sacx_expert_diag, sacx_expert_set and
+   sacx_perm_push are the same for EO and BC (the reference's BC constructs critics, targets and
+   alpha too; they stay allocated, settable and gettable).
+   SACX_EXPERT_BC (BC.py:303-363, BC._update_actor): sacx_sac_step runs the actor-only imitation
+   update -- actor.sample(s_e) through world models 0 / 1, loss = mean(0.5 sum (sp_e - sp_pred)^2),
+   Adam on the actor.  The sampler draws only the expert normals (no randint, no target / policy /
+   alpha noise); critics, targets and alpha keep weights, moments and step counts; the statistics row
+   holds the MSE in SACX_STAT_MSE_LOSS and SACX_STAT_P_LOSS, alpha in SACX_STAT_ALPHA, zeros in the
+   critic / alpha / nlp columns.  sacx_config.epsilon and sacx_expert_set's epsilon are not part of
+   the BC loss.  Not with gemm_bf16, seeds > 1 or the data-parallel modes. */
+#define SACX_EXPERT_OFF 0
+#define SACX_EXPERT_EO 1
+#define SACX_EXPERT_BC 2
+
 /* Flags for sacx_sac_step. */
 #define SACX_STEP_EXTERNAL_RANDOMS 1  /* skip the device sampler: caller filled slot0.idx / slot0.noise */
 #define SACX_STEP_EAGER 2             /* launch kernels directly instead of replaying a hipGraph */
@@ -63,7 +78,7 @@ typedef struct sacx_config {
     int32_t batch;              /* --sac_batch_size */
     int64_t buffer_capacity;    /* --env_buffer_size (ring capacity, rows) */
     int32_t per_state_std;      /* --actor_per_state_std */
-    int32_t use_expert;         /* alg_type sac_imit (SAC-EO expert regulariser) */
+    int32_t use_expert;         /* SACX_EXPERT_OFF / _EO (alg_type sac_imit) / _BC (alg_type bc), below */
     int32_t expert_capacity;    /* --expert_buffer_size */
     int32_t expert_batch;       /* rows of expert data per update (even) */
     int32_t model_hidden[2];    /* --model_layers */

@@ -487,6 +487,58 @@ __device__ __forceinline__ void fin_prefetch(const FinalArgs& f, FinPre& p) {
     strided_sums<3>(xs, ns, p.ps);
 }
 
+// The expert MSE of an update (one wave; every lane gets the value) from the world-model head's
+// per-column-tile partials of diff^2 (mse_rows): one model (SAC_expert.py:293-295) the mean over the
+// n_e rows of 0.5 ||sp_e - sp_pred||^2; two (:329-335) row i of half 1 paired with row i of half 2
+__device__ __forceinline__ float expert_mse_mean(const FinalArgs& f) {
+    const int lane = threadIdx.x & 63;
+    const int nt = f.mse_tiles;
+    float sm = 0.f;
+    if (f.nm == 1) {
+        for (int i = lane; i < f.ne; i += 64) {
+            float a = 0.f;
+            for (int t = 0; t < nt; ++t) a += f.mse_rows[i * nt + t];
+            sm += 0.5f * a;
+        }
+        return wave_sum(sm) / (float)f.ne;
+    }
+    const int h = f.ne / 2;
+    for (int i = lane; i < h; i += 64) {
+        float a = 0.f, b = 0.f;
+        for (int t = 0; t < nt; ++t) {
+            a += f.mse_rows[i * nt + t];
+            b += f.mse_rows[(i + h) * nt + t];
+        }
+        sm += 0.5f * (a + b);
+    }
+    return wave_sum(sm) / (float)h;
+}
+
+// The BC update's finalisation (BC.py:340-363; FinalArgs::use_expert == 2), one wave: the statistics
+// row (the MSE as both the policy loss and the MSE column, alpha as it stands, zeros for the critic /
+// alpha / nlp columns) and the counters.  alpha and its moments are not touched.  Folded launches run
+// it BEFORE actor.adam, which then takes the already advanced step (GemmArgs::t_adv).
+__device__ void bc_finalize(const FinalArgs& f) {
+    if (threadIdx.x >= 64) return;
+    const float mse = f.ne > 0 ? expert_mse_mean(f) : 0.f;
+    if ((threadIdx.x & 63) == 0) {
+        Ctl* ctl = f.ctl;
+        const int64_t seq = ctl->step_seq;
+        float* st = f.stats + (size_t)(seq % f.stats_cap) * 8;
+        st[0] = 0.f;
+        st[1] = 0.f;
+        st[2] = mse;
+        st[3] = 0.f;
+        st[4] = *f.alpha;
+        st[5] = mse;
+        st[6] = 0.f;
+        st[7] = (float)seq;
+        ctl->t_sac = ctl->t_sac + 1;
+        ctl->num_timesteps = ctl->num_timesteps + ctl->ts_increment;
+        ctl->step_seq = seq + 1;
+    }
+}
+
 template <bool PRE = false>
 __device__ void finalize_update(const FinalArgs& f, int nred, const FinPre* pre = nullptr) {
     if (threadIdx.x >= 64) return;
@@ -521,32 +573,8 @@ __device__ void finalize_update(const FinalArgs& f, int nred, const FinPre* pre 
     const float q2 = wave_sum(ps[2]) / (float)f.B;
     float pl = wave_sum(ps[3]) / (float)f.B;
     float mse = 0.f;
-    if (f.use_expert && f.ne > 0 && f.nm == 1) {
-        // one model (SAC_expert.py:293-295): mean over the n_e rows of 0.5 ||sp_e - sp_pred||^2
-        float sm = 0.f;
-        const int nt = f.mse_tiles;
-        for (int i = lane; i < f.ne; i += 64) {
-            float a = 0.f;
-            for (int t = 0; t < nt; ++t) a += f.mse_rows[i * nt + t];
-            sm += 0.5f * a;
-        }
-        mse = wave_sum(sm) / (float)f.ne;
-        const float eps = f.ctl->epsilon;
-        pl = (1.f - eps) * pl + eps * mse;
-    } else if (f.use_expert && f.ne > 0) {
-        // two models (:329-335): row i pairs half 1 row i with half 2 row i
-        const int h = f.ne / 2;
-        float sm = 0.f;
-        const int nt = f.mse_tiles;
-        for (int i = lane; i < h; i += 64) {
-            float a = 0.f, b = 0.f;
-            for (int t = 0; t < nt; ++t) {
-                a += f.mse_rows[i * nt + t];
-                b += f.mse_rows[(i + h) * nt + t];
-            }
-            sm += 0.5f * (a + b);
-        }
-        mse = wave_sum(sm) / (float)h;
+    if (f.use_expert && f.ne > 0) {
+        mse = expert_mse_mean(f);
         const float eps = f.ctl->epsilon;
         pl = (1.f - eps) * pl + eps * mse;
     }
@@ -1311,7 +1339,7 @@ __device__ __forceinline__ void gemm_tile32(const GemmArgs& ga, const GemmProb& 
                 if (g.dclip > 0.f) pred = fminf(fmaxf(pred, -g.dclip), g.dclip);
                 const float sp_hat = e1[s] + (pred * e4[s] + e3[s]);
                 const float diff = fit ? e1[s] - pred : e2[s] - sp_hat;
-                const float gscale = -es.eps * g.grad_scale;
+                const float gscale = -((g.mse & MSE_BC) ? 1.f : es.eps) * g.grad_scale;   // BC: no expert weight
                 const float cf = (fit && !(g.mse & MSE_NOREW) && nn == g.N - 1) ? g.fcoef : 1.f;     // the reward column
                 float sq = out_ok ? diff * diff * cf : 0.f;
                 sq += __shfl_xor(sq, 8, 16);   // the 16 columns of this thread's sub-tile row
@@ -1417,7 +1445,13 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         if constexpr (ROWK > 0 && ROWK < 3) {   // horizontally fused Q-head rows
             qhead_block<ROWK - 1, NQ>(ga.qh, tile - total_tiles, so, ROWK == 1 ? &ga.fin : nullptr);
         } else if constexpr (ROWK == 0 || ROWK == 7) {
-            if (ga.has_mfinal) mfit_final(ga.mfin, &ga.adam, ga.p_stride);   // the world-model fit step's k_mfinal
+            if (ga.has_mfinal == 2) {          // the BC update's finalisation (model.bwd2 of the folded BC plan)
+                FinalArgs f = ga.fin;
+                reloc(f, so);
+                bc_finalize(f);
+            } else if (ga.has_mfinal) {
+                mfit_final(ga.mfin, &ga.adam, ga.p_stride);   // the world-model fit step's k_mfinal
+            }
         }
         return;
     }
@@ -1838,7 +1872,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
             if (g.dclip > 0.f) pred = fminf(fmaxf(pred, -g.dclip), g.dclip);
             const float sp_hat = e1 + (pred * e4 + e3);
             const float diff = fit ? e1 - pred : e2 - sp_hat;
-            const float gscale = -es.eps * g.grad_scale;
+            const float gscale = -((g.mse & MSE_BC) ? 1.f : es.eps) * g.grad_scale;   // BC: no expert weight
             const bool rcl = fit && !(g.mse & MSE_NOREW) && nn == g.N - 1;
             const float cf = rcl ? g.fcoef : 1.f;     // the reward column
             float sq = out_ok ? diff * diff * cf : 0.f;
@@ -4050,7 +4084,18 @@ __global__ __launch_bounds__(64) void k_alpha_final(FinalArgs f_in) {
     finalize_update(f, f.nred);
 }
 
+// one wave: the BC update's statistics row and counters (the generic BC plan's last launch)
+__global__ __launch_bounds__(64) void k_bc_final(FinalArgs f_in) {
+    FinalArgs f = f_in;
+    reloc(f, seed_off(f_in.sstride));
+    bc_finalize(f);
+}
+
 void launch_alpha_final(const FinalArgs& f, hipStream_t s) {
+    if (f.use_expert == 2) {
+        hipLaunchKernelGGL(k_bc_final, dim3(1, 1, seeds_z(f.nseeds)), dim3(64), 0, s, f);
+        return;
+    }
     hipLaunchKernelGGL(k_alpha_final, dim3(1, 1, seeds_z(f.nseeds)), dim3(64), 0, s, f);
 }
 

@@ -140,6 +140,7 @@ struct sacx_handle {
     // pairs above are the first and the last hidden layer of each
     NetDims nd[4];
     bool deep = false;        // a net of other than 2 hidden layers: the generic plans (build_plan_generic)
+    bool bc = false;          // use_expert == SACX_EXPERT_BC: the actor-only imitation update (build_plan_bc)
     // world-model variants (ABI 7): GaussianModel (a logstd per model, the NLL fit loss, noise in
     // sample / step) and --separate_reward_nn (a reward net r<k> beside each model net m<k>)
     bool gm = false, srn = false, lscale = false;
@@ -347,8 +348,10 @@ int spec_cancel(sacx_handle* h, bool keep_state = false) {
 }
 
 // the handles the speculative draw applies to: one learner, its own RNG stream
+// (never for BC: its update draws no randint, and the speculative draw's fixed-bound randint would
+// consume words of the stream the reference's BC never draws)
 bool spec_mode(const sacx_handle* h) {
-    return h->spec_enabled && h->dp_ranks == 0 && !h->dp_local && h->nslot >= 3;
+    return h->spec_enabled && h->dp_ranks == 0 && !h->dp_local && h->nslot >= 3 && !h->bc;
 }
 
 #define HIPCHK(h, x)                                                                    \
@@ -1057,8 +1060,12 @@ void dp_split_adam(sacx_handle* h, std::vector<Launch>& plan, const std::string&
 // The update's inputs in slot `slot`: the sampler (randint + every normal of the update,
 // buffers.py:136, continuous_actors.py:351) and the gather of the replay / expert rows into the
 // normalised staging slabs (buffers.py:137-141, normalizer.py:36-41).  Every plan starts with them.
+// BC (SACX_EXPERT_BC, BC.py:309-336): no replay batch, so the sampler draws no integers and only the
+// expert normals (ne * A: len(sec0) * A then len(sec1) * A, one contiguous stretch of the stream), and
+// the gather takes the expert rows alone (B = 0: they are rows [0, ne) of Xa / Xm)
 void plan_inputs(sacx_handle* h, std::vector<Launch>& plan, int slot) {
-    const int S = h->S, A = h->A, B = h->B, ne = h->ne;
+    const int S = h->S, A = h->A, B = h->bc ? 0 : h->B, ne = h->ne;
+    const int n_norm = h->bc ? ne * A : h->n_norm;
     const int ldS = h->ldS, ldQ = h->ldQ;
     const std::string sl = "slot" + std::to_string(slot);
     auto W = [&](const std::string& n) { return h->f(n); };
@@ -1074,7 +1081,7 @@ void plan_inputs(sacx_handle* h, std::vector<Launch>& plan, int slot) {
         L.rng.st = h->ptr<RngState>("rng");
         L.rng.ctl = h->ctl();
         L.rng.n_int = B;
-        L.rng.n_norm = h->n_norm;
+        L.rng.n_norm = n_norm;
         L.rng.out_idx = idx;
         L.rng.out_norm = noise;
         L.rng.slot = slot;
@@ -1095,7 +1102,7 @@ void plan_inputs(sacx_handle* h, std::vector<Launch>& plan, int slot) {
         }
         L.grid = 1;
         L.block = 1024;
-        L.bytes = 4.0 * (B + h->n_norm) + 2.0 * sizeof(RngState);
+        L.bytes = 4.0 * (B + n_norm) + 2.0 * sizeof(RngState);
         plan.push_back(L);
     }
     // ---- gather
@@ -2067,6 +2074,274 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
 }
 
+// ---------------------------------------------------------------- the BC update plans
+// BC._update_actor (BC.py:309-363): actor.sample(s_e) through world models 0 / 1 (or model 0 alone),
+// loss = mean(0.5 sum (sp_e - sp_pred)^2), Adam on the actor.  It is the expert term of the SAC-EO
+// update with weight 1 and no policy rows (sac_oracle.py:608-628), so it runs the same kernels with a
+// batch of zero replay rows: the expert rows are rows [0, ne) of every actor-side buffer, the row
+// kernels see B = 0, and the world-model head takes weight 1 (MSE_BC) instead of ctl->epsilon.  No
+// critic, target or alpha launch; bc_finalize writes the statistics row and advances the counters.
+//   generic (any depth, layer norm, SACX_GENERIC=1): one GEMM launch per layer and direction, the heads
+//     on the row kernels -- actor.fwd<i> (actor.ln) actor.head model.fwd<i> model.head model.bwd<i>
+//     actor.head.bwd actor.bwd<i> (actor.ln.bwd) actor.adam bc.final;
+//   folded (two-layer nets): the actor pair and the model pair as k_fwd2 launches (the actor's writing
+//     the head's partial dots, the models' on the fit's pre-gathered-rows variant: layer 0 up to 512
+//     wide), the head backward as actor.bwd1's tile prologue from model.bwd1's partial action gradients,
+//     and the finalisation as one more workgroup of model.bwd2 (behind model.head, whose MSE partials it
+//     sums; actor.adam then takes the advanced step, t_adv) -- 8 launches at the HalfCheetah shapes:
+//     actor.fwd01 actor.head model.fwd01 model.head model.bwd2+bc.final model.bwd1
+//     actor.head.bwd+actor.bwd1 actor.adam.
+void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
+    std::vector<Launch>& plan = h->plan[slot];
+    plan.clear();
+    h->probs_cursor = 0;
+    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, ne = h->ne, Aout = h->Aout;
+    const int Hm0 = h->Hm0, Hm1 = h->Hm1, half = ne / 2;
+    const int nm = std::min(h->nm, 2), mrows = nm == 1 ? ne : half;   // the expert term's models
+    const int ldS = h->ldS, ldQ = h->ldQ;
+    const bool fold = !h->deep;
+    const NetDims &na = h->nd[0], &nmd = h->nd[2];
+    const int Da = na.D(), Dm = nmd.D();
+    const std::string sl = "slot" + std::to_string(slot);
+    auto W = [&](const std::string& n) { return h->f(n); };
+    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
+    auto ch = [&](const std::string& p, int i, int D) -> float* {     // as build_plan_generic's
+        if (i == 0) return W(p + "1");
+        if (i == D - 1) return W(p + "2");
+        return W(p + "m" + std::to_string(i));
+    };
+    float* noise_e = h->f(sl + ".noise");
+    float *Xa = W(sl + ".Xa"), *Xm = W(sl + ".Xm"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
+    float* Ha_last = W("ws.Ha2");
+
+    plan_inputs(h, plan, slot);
+    const size_t body0 = plan.size();
+    // ---- actor forward on the expert rows
+    const int tqh = (H1 + 15) / 16;
+    const bool head_part = fold && Aout <= 8 && H1 <= 256 && H1 % 64 == 0 && h->tile32_plan == 0;
+    for (int i = 0; i < Da; ++i) {
+        const float* in = i == 0 ? Xa : ch("ws.Ha", i - 1, Da);
+        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
+        GemmProb p = prob_fwd(in, ldi, ne, K, W(L_("actor", i)), na.h[i], ch("ws.Ha", i, Da),
+                              (i == 0 && h->ln) ? ACT_NONE : na.act[i]);
+        if (head_part && i == Da - 1) {      // the head's Ha2 . W3 as per-column-tile partials (rowk 5)
+            p.pw = W(L_("actor", Da)); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;
+            p.ppart = W("ws.hpart");
+        }
+        add_gemm(h, plan, "actor.fwd" + std::to_string(i), {p}, record_probs);
+        if (head_part && i == Da - 1) plan.back().gemm.rowk = 5;
+        if (i == 0 && h->ln) {
+            Launch L{};
+            L.kind = Launch::LNORM;
+            L.name = "actor.ln";
+            LNArgs& a = L.ln;
+            a.mode = 0; a.H = H0; a.Z = W("ws.Ha1"); a.nrange = 1; a.r[0] = 0; a.r[1] = ne;
+            a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = ne;
+            L.grid = (ne + 3) / 4;
+            L.flops = 8.0 * ne * H0;
+            L.bytes = 4.0 * ne * H0 * 3;
+            plan.push_back(L);
+        }
+    }
+    if (fold && !h->ln && h->fwd2) fuse_fwd2(h, plan, "actor.fwd01");
+    {   // ---- actor head: sample(s_e) into the models' input rows (their normaliser for the action columns)
+        Launch L{};
+        L.kind = Launch::AHEAD;
+        L.name = "actor.head";
+        HeadArgs& a = L.head;
+        a.H2 = Ha_last; a.ldh = H1; a.W3 = W(L_("actor", Da)); a.logstd = W("actor.logstd");
+        a.part = head_part ? W("ws.hpart") : nullptr; a.tq = tqh;
+        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
+        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
+        a.ma_mean = W("mnorm.a_mean"); a.ma_den = W("mnorm.a_den");
+        a.nseg = 1;
+        a.seg[0] = {0, ne, 1, 0, noise_e, Xm, nullptr};
+        a.total_rows = ne;
+        a.cache_row0 = 0;
+        a.cache_row1 = ne;
+        a.c_t = W("ws.c_t"); a.c_std = W("ws.c_std"); a.c_u = W("ws.c_u"); a.c_mask = W("ws.c_mask");
+        a.alpha_mode = 0;
+        L.grid = (ne + 3) / 4;
+        L.flops = 2.0 * ne * H1 * Aout;
+        L.bytes = 4.0 * ne * (H1 + 6.0 * A);
+        plan.push_back(L);
+    }
+    // ---- world models 0 / 1 forward on [s_e | pi(s_e)]
+    for (int i = 0; i < Dm; ++i) {
+        std::vector<GemmProb> ps;
+        for (int k = 0; k < nm; ++k) {
+            const std::string n = "m" + std::to_string(k);
+            const float* in = i == 0 ? Xm + (size_t)k * half * ldQ : ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1];
+            ps.push_back(prob_fwd(in, i == 0 ? ldQ : nmd.h[i - 1], mrows, i == 0 ? S + A : nmd.h[i - 1], W(L_(n, i)),
+                                  nmd.h[i], ch("ws.Hm", i, Dm) + (size_t)k * half * nmd.h[i], nmd.act[i]));
+        }
+        add_gemm(h, plan, "model.fwd" + std::to_string(i), ps, record_probs);
+    }
+    if (fold && h->fwd2 && S + A <= 32) {    // the pair as one k_fwd2 launch (rowk 9: layer 0 up to 512 wide)
+        Launch& F0 = plan[plan.size() - 2];
+        if (F0.gemm.rowk == 0 && !F0.gemm.t32) {
+            F0.gemm.rowk = 9;
+            if (!fuse_fwd2(h, plan, "model.fwd01")) plan[plan.size() - 2].gemm.rowk = 0;
+        }
+    }
+    const int mtn = (S + 15) / 16;
+    {   // ---- the models' head + the MSE (BC.py:340-352), weight 1
+        std::vector<GemmProb> pm;
+        for (int k = 0; k < nm; ++k) {
+            const std::string n = "m" + std::to_string(k);
+            GemmProb p{};
+            p.A = W("ws.Hm2") + (size_t)k * half * Hm1; p.lda = Hm1; p.a_kc = 1; p.ones_row = -1;
+            p.B = W(L_(n, Dm)); p.ldb = h->Om; p.b_kc = 0;       // W_ext [(Hm1+1) x Om], Om = S (+1)
+            p.M = mrows; p.N = S; p.K = Hm1;                     // delta-s columns only
+            p.bias = W(L_(n, Dm)) + (size_t)Hm1 * h->Om;
+            p.C = W("ws.dout") + (size_t)k * half * S; p.ldc = S;
+            p.epi = EPI_FWD; p.act = ACT_NONE;
+            p.mse = MSE_EXPERT | MSE_BC; p.grad_scale = 1.f / (float)mrows;   // the mean over the section's rows
+            p.dclip = h->cfg.delta_clip_pred > 0.f ? h->cfg.delta_clip_pred : 0.f;
+            p.se_raw = se_raw + (size_t)k * half * S; p.spe_raw = spe_raw + (size_t)k * half * S;
+            p.dmean = W("mnorm.d_mean"); p.dden = W("mnorm.d_den");
+            p.part = W("ws.mse") + (size_t)k * half * mtn;
+            pm.push_back(p);
+        }
+        add_gemm(h, plan, "model.head", pm, record_probs);
+    }
+    FinalArgs fin{};
+    fin.alpha = W("alpha"); fin.alpha_m = fin.alpha + h->p_stride; fin.alpha_v = fin.alpha + 2 * h->p_stride;
+    fin.ctl = h->ctl();
+    fin.ne = ne; fin.use_expert = SACX_EXPERT_BC; fin.nm = nm;
+    fin.mse_rows = W("ws.mse"); fin.mse_tiles = mtn;
+    fin.stats = W("stats"); fin.stats_cap = h->stats_cap;
+    bool fin_folded = false;
+    // ---- the models' backward down to their layer-0 output (the expert rows' action gradient)
+    const int tqm = (Hm0 + 15) / 16;
+    const bool fold_hbw = fold && Aout <= 8 && H1 <= 256 && H1 % 16 == 0 && Hm0 <= 512 && Hm0 % 64 == 0 &&
+                          h->tile32_plan == 0;
+    for (int i = Dm; i >= 1; --i) {
+        std::vector<GemmProb> pb;
+        for (int k = 0; k < nm; ++k) {
+            const std::string n = "m" + std::to_string(k);
+            const float* D = i == Dm ? W("ws.dout") + (size_t)k * half * S : ch("ws.Dm", i, Dm) + (size_t)k * half * nmd.h[i];
+            GemmProb p = prob_dx(D, mrows, i == Dm ? S : nmd.h[i], W(L_(n, i)), nmd.h[i - 1],
+                                 ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1],
+                                 ch("ws.Dm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1], nmd.act[i - 1]);
+            if (i == Dm) p.ldb = h->Om;          // the head's delta-s columns: B[n][k] = W_ext[n][k], stride Om
+            if (i == 1 && fold_hbw) {            // partial action gradients instead of Dm1 (read by no one else)
+                p.pw = W(L_(n, 0)) + (size_t)S * Hm0;   // action rows of W_ext
+                p.pw_ld = Hm0;
+                p.pw_cs = 1;
+                p.pw_n = A;
+                p.ppart = W("ws.mpart") + (size_t)k * half * A * tqm;
+                p.C = nullptr;
+            }
+            pb.push_back(p);
+        }
+        add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
+        Launch& L = plan.back();
+        if (i == 1 && fold_hbw) L.gemm.rowk = 2;       // DX with the partial epilogue (no q-head rows)
+        if (fold && i == Dm && L.gemm.rowk == 0) {     // + the finalisation: one more workgroup
+            L.name += "+bc.final";
+            L.gemm.has_mfinal = 2;
+            L.gemm.fin = fin;
+            fin_folded = true;
+        }
+    }
+    // ---- actor backward: tanh-Gaussian backward -> the delta at the last hidden layer, dX, dW + Adam
+    if (fold_hbw) {
+        GemmProb p = prob_dx(Ha_last, ne, H1, W("actor.l1"), H0, W("ws.Ha1"), W("ws.Da1"), h->ln ? ACT_TANH : na.act[0]);
+        p.wgen = W("actor.l2");              // W3a [(H1+1) x Aout]
+        p.gen_act = na.act[1];               // act'(Ha2)
+        p.hbw = 1;
+        add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
+        Launch& L = plan.back();
+        L.gemm.rowk = 4;
+        HeadBwdArgs& b = L.gemm.hbw;
+        b.B = 0; b.A = A; b.Aout = Aout; b.per_state_std = h->cfg.per_state_std; b.tq = 0;
+        b.lim = h->cfg.act_limit; b.part = nullptr; b.gpol = nullptr; b.a_den = W("norm.a_den");
+        b.ma_den = W("mnorm.a_den"); b.alpha = W("alpha");
+        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
+        b.Da3 = W("ws.Da3"); b.E = W("ws.E"); b.Da2 = W("ws.Da2");
+        b.ne = ne; b.tqm = tqm; b.mpart = W("ws.mpart"); b.ctl = h->ctl();
+        L.flops += 2.0 * ne * H1 * Aout;
+        L.bytes += 4.0 * (ne * tqm * A + 2.0 * ne * H1);
+    } else {
+        Launch L{};
+        L.kind = Launch::ABWD;
+        L.name = "actor.head.bwd";
+        ActorBwdArgs& b = L.ab;
+        b.B = 0; b.ne = ne; b.S = S; b.A = A; b.Aout = Aout; b.H0 = 0; b.H1 = H1; b.Hm0 = Hm0;
+        b.per_state_std = h->cfg.per_state_std; b.lim = h->cfg.act_limit;
+        b.Dp1 = nullptr; b.Wq1[0] = nullptr; b.Wq1[1] = nullptr;
+        b.Dm1 = W("ws.Dm1"); b.Wm1[0] = W("m0.l0"); b.Wm1[1] = W(nm > 1 ? "m1.l0" : "m0.l0");
+        b.a_den = W("norm.a_den"); b.ma_den = W("mnorm.a_den"); b.alpha = W("alpha"); b.ctl = h->ctl();
+        b.use_expert = 1;
+        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
+        b.W3a = W(L_("actor", Da)); b.Ha2 = Ha_last;
+        b.act = (Da == 1 && h->ln) ? ACT_TANH : na.act[Da - 1];   // layer norm: tanh' at the norm's output
+        b.Da3 = W("ws.Da3"); b.Da2 = W("ws.Da2"); b.E = W("ws.E");
+        b.gpol = nullptr;
+        L.grid = (ne + 3) / 4;
+        L.flops = 2.0 * ne * Hm0 * A + 2.0 * ne * H1 * Aout;
+        L.bytes = 4.0 * (ne * Hm0 + 2.0 * ne * H1);
+        plan.push_back(L);
+        for (int i = Da - 1; i >= 1; --i)
+            add_gemm(h, plan, "actor.bwd" + std::to_string(i),
+                     {prob_dx(ch("ws.Da", i, Da), ne, na.h[i], W(L_("actor", i)), na.h[i - 1], ch("ws.Ha", i - 1, Da),
+                              ch("ws.Da", i - 1, Da), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
+                     record_probs);
+    }
+    if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
+        Launch N{};
+        N.kind = Launch::LNORM;
+        N.name = "actor.ln.bwd";
+        LNArgs& a = N.ln;
+        a.mode = 1; a.H = H0; a.Z = W("ws.Da1"); a.r[1] = ne; a.gamma = W("actor.ln");
+        a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = 0;
+        a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
+        N.grid = (ne + 3) / 4;
+        N.flops = 8.0 * ne * H0;
+        N.bytes = 4.0 * ne * H0 * 5;
+        plan.push_back(N);
+    }
+    {
+        std::vector<GemmProb> pw;
+        for (int i = 0; i < Da; ++i) {
+            const float* X = i == 0 ? Xa : ch("ws.Ha", i - 1, Da);
+            const int K = i == 0 ? S : na.h[i - 1];
+            pw.push_back(prob_dw(X, i == 0 ? ldS : K, K, ne, ch("ws.Da", i, Da), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
+        }
+        pw.push_back(prob_dw(Ha_last, H1, H1, ne, W("ws.Da3"), Aout, W(L_("actor", Da)), nullptr, GRP_PI));
+        if (!h->cfg.per_state_std) {
+            GemmProb p = prob_dw(W("ws.E"), 1, 0, ne, W("ws.E"), A, W("actor.logstd"), nullptr, GRP_PI);
+            p.ones_row = 0;   // single all-ones row: column sums of E
+            pw.push_back(p);
+        }
+        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
+            for (int k = 0; k < 2; ++k) {
+                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
+                GemmProb p = prob_dw(gsrc, 1, 0, ne, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
+                p.ones_row = 0;
+                pw.push_back(p);
+            }
+        }
+        const size_t first = plan.size();
+        add_gemm_split(h, plan, "actor.adam", pw, record_probs);
+        for (size_t i = first; i < plan.size(); ++i) plan[i].gemm.t_adv = fin_folded ? 1 : 0;
+    }
+    if (!fin_folded) {
+        Launch L{};
+        L.kind = Launch::FINAL;
+        L.name = "bc.final";
+        L.fin = fin;
+        L.grid = 1;
+        L.block = 64;
+        L.bytes = 4.0 * ne * mtn;
+        plan.push_back(L);
+    }
+    // the update reads its slot from its first launch on, and no later update reads it
+    plan[body0].frees_slot = true;
+    for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
+}
+
 // one world-model fitting step: gather -> 3 fwd GEMMs -> loss grads -> 2 dX GEMMs -> dW + Adam -> finalize
 // the fitting plan of the selected seed (its arena block's pointers).  Folded (h->mfuse, the
 // default): the loss and its gradient are model.fwd2's epilogue (mse = 2) and the finalisation is
@@ -2501,6 +2776,8 @@ bool merged_body(sacx_handle* h, int slot, int prev_slot, std::vector<Launch>& o
             else if (L.kind == Launch::LNORM) pln = &L;
         }
     size_t gi = 0;
+    // (a plan without an alpha branch -- BC -- has nothing to fold: the body is the update itself)
+    if (pg.empty() && !ph && !pf && !pln) prev_slot = -1;
     bool head_done = prev_slot < 0, final_done = prev_slot < 0, ln_done = pln == nullptr;
     bool afin_next = false;    // the split alpha finalisation still has its q.head half to place
     for (const Launch& L : h->plan[slot]) {
@@ -3129,6 +3406,13 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     if (cfg->batch <= 0 || cfg->buffer_capacity <= 0) return bad("batch/buffer_capacity must be positive");
     if (cfg->buffer_capacity >= (int64_t(1) << 31)) return bad("buffer_capacity must be < 2^31");
     if (cfg->num_models < 0 || cfg->num_models > SACX_MAX_MODELS) return bad("num_models must be in [1, 8] (0 -> 2)");
+    if (cfg->use_expert < SACX_EXPERT_OFF || cfg->use_expert > SACX_EXPERT_BC)
+        return bad("use_expert must be SACX_EXPERT_OFF, SACX_EXPERT_EO or SACX_EXPERT_BC");
+    if (cfg->use_expert == SACX_EXPERT_BC) {
+        if (cfg->gemm_bf16) return bad("BC (use_expert = SACX_EXPERT_BC) runs fp32 only (gemm_bf16 = 0)");
+        if (cfg->seeds > 1) return bad("BC (use_expert = SACX_EXPERT_BC) runs one learner per handle (seeds <= 1)");
+        if (cfg->actor_gaussian) return bad("BC (use_expert = SACX_EXPERT_BC) trains the squashed actor");
+    }
     if (cfg->use_expert) {
         const int nmc = cfg->num_models > 0 ? cfg->num_models : 2;
         if (cfg->expert_batch <= 0) return bad("expert_batch must be positive");
@@ -3222,6 +3506,7 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     // plans (SACX_GENERIC=1 forces them at two layers too: their parity test)
     h->deep = nd[0].D() != 2 || nd[1].D() != 2 || (cfg->use_expert && nd[2].D() != 2) || (h->srn && nd[3].D() != 2);
     if (const char* e = std::getenv("SACX_GENERIC")) h->deep = h->deep || std::atoi(e) != 0;
+    h->bc = cfg->use_expert == SACX_EXPERT_BC;
     h->mb = cfg->use_expert ? (cfg->model_batch > 0 ? cfg->model_batch : 200) : 0;
     h->ln = cfg->actor_layer_norm != 0;
     h->ldS = (int)r4(h->S);
@@ -3341,6 +3626,7 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     auto t32_of = [](int64_t rows) { return rows >= 4096 ? 1 : rows >= 1024 ? 2 : 0; };
     h->tile32 = t32_of((int64_t)h->seeds * h->B);
     h->tile32_plan = t32_of((int64_t)h->plan_seeds * h->B);
+    if (h->bc) h->tile32 = h->tile32_plan = 0;   // the BC update has the expert rows only, whatever the batch
     if (const char* e = std::getenv("SACX_T32")) h->tile32 = h->tile32_plan = std::atoi(e);
     // dW + Adam over >= 512 batch rows (Humanoid B = 1,024) on k_dwl: LDS-DMA staged 128-B row
     // pieces instead of the fragment-shaped column loads, bit-identical results
@@ -3383,7 +3669,8 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     h->wbf_live = h->wbf_attach;
     for (int sl = 0; sl < h->nslot; ++sl) {
         h->abf_written.clear();
-        if (h->deep) build_plan_generic(h, sl, sl == 0);
+        if (h->bc) build_plan_bc(h, sl, sl == 0);
+        else if (h->deep) build_plan_generic(h, sl, sl == 0);
         else build_plan(h, sl, sl == 0);
     }
     h->abf_written.clear();
@@ -4205,7 +4492,8 @@ static int launch_info(const std::vector<Launch>& plan, sacx_launch_info* out, i
     for (int i = 0; i < (int)plan.size() && i < cap; ++i) {
         std::memset(&out[i], 0, sizeof(sacx_launch_info));
         std::strncpy(out[i].name, plan[i].name.c_str(), sizeof(out[i].name) - 1);
-        std::strncpy(out[i].kernel, kernel_family(plan[i].kind), sizeof(out[i].kernel) - 1);
+        const bool bcf = plan[i].kind == Launch::FINAL && plan[i].fin.use_expert == SACX_EXPERT_BC;
+        std::strncpy(out[i].kernel, bcf ? "k_bc_final" : kernel_family(plan[i].kind), sizeof(out[i].kernel) - 1);
         out[i].grid = plan[i].grid;
         out[i].block = plan[i].block;
         out[i].flops = plan[i].flops;

@@ -65,7 +65,9 @@ enum GemmMode { GM_FWD = 0, GM_DX = 1, GM_DW = 2, GM_FWD2 = 3 };
 // so the 256 tiles and the head rows run in one round; its head rows take NW / 4 blocks of 4 rows each
 #define SACX_FWD2_HEAD_NW 8
 
-enum { MSE_EXPERT = 1, MSE_FIT = 2, MSE_GAUSS = 4, MSE_SCALE = 8, MSE_NOREW = 16 };
+// MSE_BC (with MSE_EXPERT): the BC update's head (BC.py:340-352) -- the expert term with weight 1
+// whatever ctl->epsilon holds
+enum { MSE_EXPERT = 1, MSE_FIT = 2, MSE_GAUSS = 4, MSE_SCALE = 8, MSE_NOREW = 16, MSE_BC = 32 };
 struct GemmProb {
     const float* A;        // a_kc: A[m*lda + k]   else A[k*lda + m] (row ones_row = 1.0)
     const float* B;        // b_kc: B[n*ldb + k]   else B[k*ldb + n]

@@ -17,6 +17,7 @@ MAX_MODELS = 8                  # SACX_MAX_MODELS: --num_models
 STAGE_FLOATS = 65536            # SACX_STAGE_FLOATS (include/sacx.h)
 ACT = {"relu": 0, "tanh": 1, "elu": 2}
 DTYPES = {0: "f32", 1: "i32", 2: "i64", 3: "u32", 4: "f64"}
+EXPERT_OFF, EXPERT_EO, EXPERT_BC = 0, 1, 2      # sacx_config.use_expert (SACX_EXPERT_*)
 STEP_EXTERNAL_RANDOMS = 1
 STEP_EAGER = 2
 ROLE_WORK, ROLE_PARAM, ROLE_TARGET, ROLE_STATE = 0, 1, 2, 3

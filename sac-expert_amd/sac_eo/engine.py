@@ -81,6 +81,14 @@ class EngineConfig:
     separate_reward_nn: bool = False
     reward_hidden: Sequence[int] = (512, 512)
     reward_activations: Optional[Sequence[str]] = None
+    # alg_type bc (BC.py:303-363): the actor-only imitation update through the world models.  Implies
+    # the expert path (world models, expert rows, permutations); critics, targets and alpha stay in
+    # the arena untouched.  fp32, one seed, no data-parallel ranks.
+    bc: bool = False
+
+    def __post_init__(self):
+        if self.bc:
+            self.use_expert = True
 
     @staticmethod
     def _acts(lst, dflt: str, depth: int, what: str) -> List[str]:
@@ -123,7 +131,7 @@ class EngineConfig:
         c.batch = int(self.batch)
         c.buffer_capacity = int(self.buffer_capacity)
         c.per_state_std = int(bool(self.per_state_std))
-        c.use_expert = int(bool(self.use_expert))
+        c.use_expert = N.EXPERT_BC if self.bc else int(bool(self.use_expert))
         c.expert_capacity = int(self.expert_capacity)
         c.expert_batch = int(self.expert_batch)
         c.model_hidden[0], c.model_hidden[1] = [int(x) for x in two(self.model_hidden)]

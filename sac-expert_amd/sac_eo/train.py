@@ -133,8 +133,9 @@ def main(argv=None):
     start = datetime.now()
     args = create_train_parser().parse_args(argv)
     inputs_dict = gather_inputs(args)
-    if args.alg_type in ("sac", "sac_imit"):
-        inputs_dict["actor_kwargs"]["actor_squash"] = True     # SAC uses the squashed actor
+    if args.alg_type in ("sac", "sac_imit", "bc"):
+        # SAC uses the squashed actor; the device BC trains the squashed actor only
+        inputs_dict["actor_kwargs"]["actor_squash"] = True
     seeds = derive_seeds(args.seed, args.runs, args.runs_start)
     runs = list(range(args.runs))
     ws = int(os.environ.get("WORLD_SIZE", "1"))
