@@ -38,6 +38,7 @@ extern "C" {
 
 #define SACX_ABI_VERSION 8
 #define SACX_MAX_DEPTH 4    /* hidden layers per net (create_nn's layers list, nn_utils.py:100-138) */
+#define SACX_MAX_WIDTH 1024 /* widest hidden layer of any net; above 512 the handle runs the generic plan */
 #define SACX_MAX_MODELS 8   /* --num_models */
 
 typedef struct sacx_handle sacx_handle;
@@ -151,7 +152,8 @@ typedef struct sacx_config {
                                    --actor_layers / --critic_layers / --model_layers / --reward_layers lists,
                                    train_parser.py:56-57, :107-108, of any length).  Any net not of 2 layers runs
                                    the generic launch plan (unfused, every layer its own GEMM problem) */
-    int32_t net_hidden[4][SACX_MAX_DEPTH];   /* widths, [1, 512] */
+    int32_t net_hidden[4][SACX_MAX_DEPTH];   /* widths, [1, SACX_MAX_WIDTH]; a used net with a
+                                                layer above 512 puts the handle on the generic plan */
     int32_t net_acts[4][SACX_MAX_DEPTH];     /* per-layer sacx_activation */
 } sacx_config;
 

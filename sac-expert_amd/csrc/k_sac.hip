@@ -341,8 +341,11 @@ __device__ __forceinline__ void reloc(ActorBwdArgs& b, int64_t so) {
 // stores s_memrealtime at kernel start [0], problem selected [1], main loop done [2], tile
 // reduced [3] and kernel end [4] (the last launch's workgroups, by blockIdx.x)
 #ifdef SACX_GEMM_PHASES
-__device__ unsigned long long g_gemm_ph[8192][5];
-#define GEMM_PH(i) do { if (threadIdx.x == 0) g_gemm_ph[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+// (a launch of more workgroups -- a 1,024 x 1,024 dW on 16x16 tiles is 4,160 per problem -- stamps its
+// first GEMM_PH_WGS only: never past the end)
+#define GEMM_PH_WGS 8192
+__device__ unsigned long long g_gemm_ph[GEMM_PH_WGS][5];
+#define GEMM_PH(i) do { if (threadIdx.x == 0 && blockIdx.x < GEMM_PH_WGS) g_gemm_ph[blockIdx.x][i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define GEMM_PH(i) do { } while (0)
 #endif
@@ -390,6 +393,47 @@ __device__ __forceinline__ void rowdot8(const float (&hv)[NQ], __amdgpu_buffer_r
         p[u] = 0.f;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) p[u] = fmaf(hv[q], w[q][u], p[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) out[u] = wave_sum(p[u]);
+}
+
+// ---- wide rows (512 < H <= 1,024 = 64 * WIDEQ): walked in slabs of 8 q (512 columns), so the
+// weights in flight stay at the 8 x 8 of the narrow kernels.  Per output the products accumulate
+// in ascending q within and across the slabs -- the order of the narrow kernels continued -- and
+// each slab's loads are all issued before its FMAs.
+#define WIDEQ 16
+// slab s of a row: hv[i] = h[base + lane + 64 (8 s + i)] (0 beyond H)
+__device__ __forceinline__ void load_slab(__amdgpu_buffer_rsrc_t r, int base, int H, int s, float (&hv)[MAXQ]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int i = 0; i < MAXQ; ++i) {
+        const int k = lane + 64 * (MAXQ * s + i);
+        hv[i] = bload(r, boff(k < H, base + k));
+    }
+}
+
+// rowdot8 of a wide row held in registers: W's slabs one after the other into the same 8 sums
+template <>
+__device__ __forceinline__ void rowdot8<WIDEQ>(const float (&hv)[WIDEQ], __amdgpu_buffer_rsrc_t rW, int H, int ldw,
+                                               int o0, int O, float (&out)[8]) {
+    const int lane = threadIdx.x & 63;
+    float p[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) p[u] = 0.f;
+#pragma unroll
+    for (int s = 0; s < WIDEQ / MAXQ; ++s) {
+        float w[MAXQ][8];
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int k = lane + 64 * (MAXQ * s + q);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w[q][u] = bload(rW, boff(k < H && o0 + u < O, k * ldw + o0 + u));
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) p[u] = fmaf(hv[MAXQ * s + q], w[q][u], p[u]);
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) out[u] = wave_sum(p[u]);
@@ -2020,7 +2064,7 @@ __global__ __launch_bounds__(256, SACX_T32_OCC) void k_gemm(uint32_t h0, uint32_
                                                            GemmArgs ga) {
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
 #ifdef SACX_GEMM_PHASES
-    if (threadIdx.x == 0) g_gemm_ph[blockIdx.x][0] = t0;
+    if (threadIdx.x == 0 && blockIdx.x < GEMM_PH_WGS) g_gemm_ph[blockIdx.x][0] = t0;
 #endif
     gemm_core<MODE, VEC, ROWK, NQ, BF, PK, T32>(KHdr{{h0, h1, h2, h3}}, ga);
     GEMM_PH(4);
@@ -2141,7 +2185,7 @@ __global__ __launch_bounds__(256, 2) void k_dwl(uint32_t h0, uint32_t h1, uint32
     constexpr int STG = dwl_stg<NH>(), NS = 2 * NH;     // stage floats; sub-tiles per thread
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
 #ifdef SACX_GEMM_PHASES
-    if (threadIdx.x == 0) g_gemm_ph[blockIdx.x][0] = t0;
+    if (threadIdx.x == 0 && blockIdx.x < GEMM_PH_WGS) g_gemm_ph[blockIdx.x][0] = t0;
 #endif
     __shared__ float lds[4 * SACX_DWL_NST * STG];    // the one LDS object (staging, then reduction)
     const int64_t so = PK ? seed_off(ga.sstride) : 0;
@@ -4342,9 +4386,12 @@ void launch_actor_head(const HeadArgs& a, const FinalArgs& f, hipStream_t s) {
         } else {
             hipLaunchKernelGGL((k_actor_head<4, false>), grid, dim3(256), 0, s, a, f);
         }
-    } else {
+    } else if (a.H1 <= 64 * MAXQ) {
         if (pk) hipLaunchKernelGGL((k_actor_head<8, true>), grid, dim3(256), 0, s, a, f);
         else hipLaunchKernelGGL((k_actor_head<8, false>), grid, dim3(256), 0, s, a, f);
+    } else {    // wide rows: the row in 16 registers, W3 in two slabs (rowdot8<WIDEQ>)
+        if (pk) hipLaunchKernelGGL((k_actor_head<WIDEQ, true>), grid, dim3(256), 0, s, a, f);
+        else hipLaunchKernelGGL((k_actor_head<WIDEQ, false>), grid, dim3(256), 0, s, a, f);
     }
 }
 
@@ -4811,9 +4858,112 @@ __device__ __forceinline__ void qhead_block(const QHeadArgs& q_in, int block, in
 template <int MODE, int NQ>
 __global__ __launch_bounds__(256) void k_qhead(QHeadArgs q) { qhead_block<MODE, NQ>(q, blockIdx.x, seed_off(q.sstride)); }
 
+// The replay rows of qhead_block for wide rows (512 < H1 <= 1,024; the generic plans: no expert
+// rows, no split alpha finalisation): the four (two) dots run slab by slab into one partial sum
+// per net, and the delta re-reads the differentiated nets' rows and weights (L2-resident)
+// instead of keeping 16 registers per array live.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_qhead_wide(QHeadArgs q_in) {
+    QHeadArgs q = q_in;
+    reloc(q, seed_off(q_in.sstride));
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    const int B = q.B, H1 = q.H1;
+    if (row >= B) return;
+    constexpr int nnet = (MODE == 0) ? 4 : 2;
+    const float alpha = *q.alpha;
+    const float nlp_r = q.nlp[row];
+    float r_r = 0.f, d_r = 0.f, rd = 1.f;
+    if (MODE == 0) {
+        r_r = q.r[row];
+        d_r = q.d[row];
+        rd = *q.ret_den;
+    }
+    const __amdgpu_buffer_rsrc_t rH = rs(q.H2);
+    float p[4], bias[4];
+#pragma unroll
+    for (int k = 0; k < nnet; ++k) {
+        p[k] = 0.f;
+        bias[k] = bload(rs(q.W3[k]), (uint32_t)H1 * 4u);
+    }
+#pragma unroll
+    for (int s = 0; s < WIDEQ / MAXQ; ++s) {
+        float hv[4][MAXQ], wv[4][MAXQ];
+#pragma unroll
+        for (int k = 0; k < nnet; ++k) {
+            load_slab(rH, (k * B + row) * H1, H1, s, hv[k]);
+            load_slab(rs(q.W3[k]), 0, H1, s, wv[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < nnet; ++k)
+#pragma unroll
+            for (int i = 0; i < MAXQ; ++i) p[k] = fmaf(hv[k][i], wv[k][i], p[k]);
+    }
+    float out[4];
+#pragma unroll
+    for (int k = 0; k < nnet; ++k) out[k] = wave_sum(p[k]) + bias[k];
+    float g0, g1;
+    if constexpr (MODE == 0) {
+        const float v0 = out[0] * rd, v1 = out[1] * rd;
+        const float nv = fminf(v0, v1) + alpha * nlp_r;
+        const float y = r_r + q.gamma * ((1.f - d_r) * nv);
+        const float e0 = out[2] - y, e1 = out[3] - y;
+        const float invB = 1.f / (float)B;
+        g0 = e0 * invB;
+        g1 = e1 * invB;
+        if (lane == 0) {
+            q.loss_rows[row] = 0.5f * (e0 * e0);
+            q.loss_rows[B + row] = 0.5f * (e1 * e1);
+            q.g[row] = g0;
+            q.g[B + row] = g1;
+        }
+    } else {
+        const float q0 = out[0], q1 = out[1];
+        const float minq = fminf(q0, q1);
+        if (lane == 0) q.loss_rows[row] = (-alpha) * nlp_r - minq;
+        const float gmin = -q.w_sac * (1.f / (float)B);
+        const float s0 = q0 < q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
+        const float s1 = q1 < q0 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
+        g0 = gmin * s0;
+        g1 = gmin * s1;
+        if (lane == 0 && q.g != nullptr) {
+            q.g[row] = g0;
+            q.g[B + row] = g1;
+        }
+        if (q.D2 == nullptr) return;
+    }
+    // differentiated nets: 2,3 (mode 0) or 0,1 (mode 1); d[k] = g w3[k] act'(h[k]), the row re-read
+    constexpr int dn = MODE == 0 ? 2 : 0;
+    float* d0 = q.D2 + (size_t)row * H1;
+    float* d1 = q.D2 + ((size_t)B + row) * H1;
+#pragma unroll
+    for (int s = 0; s < WIDEQ / MAXQ; ++s) {
+        float hv[2][MAXQ], wv[2][MAXQ];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            load_slab(rH, ((dn + k) * B + row) * H1, H1, s, hv[k]);
+            load_slab(rs(q.W3[dn + k]), 0, H1, s, wv[k]);
+        }
+#pragma unroll
+        for (int i = 0; i < MAXQ; ++i) {
+            const int k = lane + 64 * (MAXQ * s + i);
+            if (k < H1) {
+                d0[k] = (g0 * wv[0][i]) * dact_f(hv[0][i], q.act);
+                d1[k] = (g1 * wv[1][i]) * dact_f(hv[1][i], q.act);
+            }
+        }
+    }
+}
+
 void launch_qhead(const QHeadArgs& a, hipStream_t s) {
     const int rows = a.B + (a.mode == 0 ? a.ne : 0);
     const dim3 grid((rows + 3) / 4, 1, seeds_z(a.nseeds));
+    if (a.H1 > 64 * MAXQ) {     // wide rows (the host builds no such launch with expert rows)
+        const dim3 gw((a.B + 3) / 4, 1, seeds_z(a.nseeds));
+        if (a.mode == 0) hipLaunchKernelGGL(k_qhead_wide<0>, gw, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(k_qhead_wide<1>, gw, dim3(256), 0, s, a);
+        return;
+    }
     if (a.H1 <= 256) {
         if (a.mode == 0) hipLaunchKernelGGL((k_qhead<0, 4>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_qhead<1, 4>), grid, dim3(256), 0, s, a);
@@ -4999,10 +5149,157 @@ __global__ __launch_bounds__(256) void k_actor_bwd(ActorBwdArgs b) {
     ktime_stamp(b.ktime, t0);
 }
 
+// actor_bwd_body with either axis wide (H1 or max(Hc0, Hm0) in (512, 1,024]): NS slabs of the
+// actor's last hidden row, NSD slabs of the layer-1 delta row, each 1 or 2, chosen independently.
+// The action gradient takes the delta row and both W1 row blocks slab by slab into the chunk's 8
+// sums; the head backward keeps its pacc per column of H1 and takes W3 slab by slab; act'(h2) reads
+// the row again at the end.  Per sum the same fmaf order as the narrow body, continued over slabs.
+template <int NS, int NSD, bool PK>
+__device__ __forceinline__ void actor_bwd_wide_body(const ActorBwdArgs& b_in) {
+    ActorBwdArgs b = b_in;
+    if constexpr (PK) reloc(b, seed_off(b_in.sstride));
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    const int B = b.B, S = b.S, A = b.A;
+    if (row >= B + b.ne) return;
+    const bool pol = row < B;
+    const bool jok = lane < A;
+    const float eps = b.use_expert ? b.ctl->epsilon : 0.f;
+    const float alpha = *b.alpha;
+    const int ci = row * A + lane;
+    const float t_pf = bload(rs(b.c_t), boff(jok, ci));
+    const float sd_pf = bload(rs(b.c_std), boff(jok, ci));
+    const float u_pf = bload(rs(b.c_u), boff(jok, ci));
+    const float mk_pf = bload(rs(b.c_mask), boff(jok, ci));
+    const float ad_pf = bload(rs(pol ? b.a_den : b.ma_den), boff(jok, lane));
+    const float w_sac = 1.f - eps;
+    const float c = -w_sac * alpha * (1.f / (float)B);
+    const int e = row - B;
+    const int km = e < b.ne / 2 ? 0 : 1;
+    const int Hd = pol ? b.H0 : b.Hm0;
+    const int Hb = pol ? Hd : 0;
+    const __amdgpu_buffer_rsrc_t rD0 = rs(pol ? b.Dp1 : b.Dm1), rD1 = rs(b.Dp1);
+    const int base0 = pol ? row * b.H0 : e * b.Hm0, base1 = (B + row) * b.H0;
+    const __amdgpu_buffer_rsrc_t rg = rs(b.gpol);
+    const float gs0 = bload(rg, boff(pol && b.gpol != nullptr, row)) + ((pol && b.gpol != nullptr) ? 0.f : 1.f);
+    const float gs1 = bload(rg, boff(pol && b.gpol != nullptr, B + row)) + ((pol && b.gpol != nullptr) ? 0.f : 1.f);
+    const __amdgpu_buffer_rsrc_t rWa = rs(pol ? b.Wq1[0] : (km ? b.Wm1[1] : b.Wm1[0]));
+    const __amdgpu_buffer_rsrc_t rWb = rs(b.Wq1[1]);
+    float ga = 0.f;
+    for (int j0 = 0; j0 < A; j0 += 8) {
+        float p[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) p[u] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NSD; ++s) {
+            float dv0[MAXQ], dv1[MAXQ];
+            load_slab(rD0, base0, Hd, s, dv0);
+            load_slab(rD1, base1, Hb, s, dv1);
+            float w0[8][MAXQ], w1[8][MAXQ];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const bool uok = j0 + u < A;
+                const int jr = S + j0 + u;
+#pragma unroll
+                for (int i = 0; i < MAXQ; ++i) {
+                    const int k = lane + 64 * (MAXQ * s + i);
+                    w0[u][i] = bload(rWa, boff(uok && k < Hd, jr * Hd + k));
+                    w1[u][i] = bload(rWb, boff(uok && k < Hb, jr * Hd + k));
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+#pragma unroll
+                for (int i = 0; i < MAXQ; ++i) {
+                    p[u] = fmaf(gs0 * dv0[i], w0[u][i], p[u]);
+                    p[u] = fmaf(gs1 * dv1[i], w1[u][i], p[u]);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const float sj = wave_sum(p[u]);
+            ga = (lane == j0 + u) ? sj : ga;
+        }
+    }
+    ga = ga / ad_pf;
+    float gx = 0.f, dl = 0.f;
+    if (jok) {
+        const float t = t_pf, sd = sd_pf, u = u_pf, mask = mk_pf;
+        gx = ga * b.lim * (1.f - t * t);
+        if (pol) gx = gx - (2.f * c) * t;
+        dl = (gx * sd) * u;
+        if (pol) dl = dl + c;
+        dl = dl * mask;
+        b.Da3[(size_t)row * b.Aout + lane] = gx;
+        if (b.per_state_std) b.Da3[(size_t)row * b.Aout + A + lane] = dl;
+        else b.E[ci] = dl;
+    }
+    // Da2[row][i] = (sum_o Da3[row][o] W3a[i][o]) * act'(Ha2[row][i]); columns o live in lanes
+    const __amdgpu_buffer_rsrc_t rW3 = rs(b.W3a);
+    float pacc[MAXQ * NS];
+#pragma unroll
+    for (int qq = 0; qq < MAXQ * NS; ++qq) pacc[qq] = 0.f;
+    for (int o0 = 0; o0 < b.Aout; o0 += 8) {
+        float d3[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int o = o0 + u;
+            const float src = (o < A) ? __shfl(gx, min(o, 63), 64) : __shfl(dl, min(max(o - A, 0), 63), 64);
+            d3[u] = (o < b.Aout) ? src : 0.f;
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            float w[MAXQ][8];
+#pragma unroll
+            for (int qq = 0; qq < MAXQ; ++qq) {
+                const int i = (MAXQ * s + qq) * 64 + lane;
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    w[qq][u] = bload(rW3, boff(i < b.H1 && o0 + u < b.Aout, i * b.Aout + o0 + u));
+            }
+#pragma unroll
+            for (int qq = 0; qq < MAXQ; ++qq)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) pacc[MAXQ * s + qq] = fmaf(d3[u], w[qq][u], pacc[MAXQ * s + qq]);
+        }
+    }
+    const __amdgpu_buffer_rsrc_t rH2 = rs(b.Ha2);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float h2v[MAXQ];
+        load_slab(rH2, row * b.H1, b.H1, s, h2v);
+#pragma unroll
+        for (int qq = 0; qq < MAXQ; ++qq) {
+            const int i = (MAXQ * s + qq) * 64 + lane;
+            if (i < b.H1) b.Da2[(size_t)row * b.H1 + i] = pacc[MAXQ * s + qq] * dact_f(h2v[qq], b.act);
+        }
+    }
+}
+
+template <int NS, int NSD, bool PK>
+__global__ __launch_bounds__(256) void k_actor_bwd_wide(ActorBwdArgs b) {
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    actor_bwd_wide_body<NS, NSD, PK>(b);
+    ktime_stamp(b.ktime, t0);
+}
+
 void launch_actor_bwd(const ActorBwdArgs& a, hipStream_t s) {
     const int rows = a.B + a.ne;
     const dim3 grid((rows + 3) / 4, 1, seeds_z(a.nseeds));
     const int hd = std::max(a.H0, a.use_expert ? a.Hm0 : 0);
+    if (a.H1 > 64 * MAXQ || hd > 64 * MAXQ) {   // either axis wide: slabs on each, independently
+#define SACX_ABW(Q, D)                                                                                    \
+    do {                                                                                                  \
+        if (a.nseeds > 1) hipLaunchKernelGGL((k_actor_bwd_wide<Q, D, true>), grid, dim3(256), 0, s, a);   \
+        else hipLaunchKernelGGL((k_actor_bwd_wide<Q, D, false>), grid, dim3(256), 0, s, a);               \
+    } while (0)
+        if (a.H1 > 64 * MAXQ && hd > 64 * MAXQ) SACX_ABW(2, 2);
+        else if (a.H1 > 64 * MAXQ) SACX_ABW(2, 1);
+        else SACX_ABW(1, 2);
+#undef SACX_ABW
+        return;
+    }
     const bool q8 = a.H1 > 256, d8 = hd > 256;
 #define SACX_AB(Q, D, ...)                                                                                  \
     do {                                                                                                    \
@@ -5636,10 +5933,128 @@ __global__ __launch_bounds__(256) void k_ln(LNArgs a) {
     }
 }
 
+// k_ln for wide rows (512 < H <= 1,024): each pass walks the row in two slabs of 8 q and reads it
+// again (L2-resident) instead of holding it; the sums run in ascending q across the slabs, k_ln's
+// order continued.  (A lane writes only elements it alone reads, and after reading them.)
+__global__ __launch_bounds__(256) void k_ln_wide(LNArgs a) {
+    constexpr int NS = WIDEQ / MAXQ;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t so = seed_off(a.sstride);
+    const int H = a.H;
+    const float inv_h = 1.f / (float)H;
+    int row = blockIdx.x * 4 + wave;
+    const float* gamma = sr(a.gamma, so);
+    if (a.mode == 0) {
+        const int n0 = a.r[1] - a.r[0];
+        if (row >= n0 + (a.nrange > 1 ? a.r[3] - a.r[2] : 0)) return;
+        row = row < n0 ? a.r[0] + row : a.r[2] + (row - n0);
+        float* z = sr(a.Z, so) + (size_t)row * H;
+        float s = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            float v[MAXQ];
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                const int j = lane + 64 * (MAXQ * sl + q);
+                v[q] = j < H ? z[j] : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) s += v[q];
+        }
+        const float mu = wave_sum(s) * inv_h;
+        float ss = 0.f;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            float v[MAXQ];
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                const int j = lane + 64 * (MAXQ * sl + q);
+                v[q] = j < H ? z[j] : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                const float d = (lane + 64 * (MAXQ * sl + q) < H) ? v[q] - mu : 0.f;
+                ss += d * d;
+            }
+        }
+        const float var = wave_sum(ss) * inv_h;
+        const float rstd = 1.f / sqrtf(var + 1e-3f);     // Keras LayerNormalization epsilon
+        const bool cache = row < a.cache_rows && a.xhat != nullptr;
+        float* xh = cache ? sr(a.xhat, so) + (size_t)row * H : nullptr;
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            float v[MAXQ];
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                const int j = lane + 64 * (MAXQ * sl + q);
+                v[q] = j < H ? z[j] : 0.f;
+            }
+#pragma unroll
+            for (int q = 0; q < MAXQ; ++q) {
+                const int j = lane + 64 * (MAXQ * sl + q);
+                if (j < H) {
+                    const float x = (v[q] - mu) * rstd;
+                    if (cache) xh[j] = x;
+                    z[j] = tanhf(gamma[j] * x + gamma[H + j]);
+                }
+            }
+        }
+        if (cache && lane == 0) sr(a.rstd, so)[row] = rstd;
+        return;
+    }
+    // mode 1: dY -> dZ = rstd (g - mean(g) - xhat mean(g xhat)), g = dY gamma
+    if (row >= a.r[1]) return;
+    float* d = sr(a.Z, so) + (size_t)row * H;
+    const float* xh = sr(a.xhat, so) + (size_t)(row + a.xrow0) * H;
+    const float rstd = sr(a.rstd, so)[row + a.xrow0];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        float dy[MAXQ], x[MAXQ], gm[MAXQ];
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int j = lane + 64 * (MAXQ * sl + q);
+            dy[q] = j < H ? d[j] : 0.f;
+            x[q] = j < H ? xh[j] : 0.f;
+            gm[q] = j < H ? gamma[j] : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const float g = (lane + 64 * (MAXQ * sl + q) < H) ? dy[q] * gm[q] : 0.f;
+            s1 += g;
+            s2 += g * x[q];
+        }
+    }
+    const float m1 = wave_sum(s1) * inv_h, m2 = wave_sum(s2) * inv_h;
+    float* gy = sr(a.gy, so) + (size_t)row * H;
+    float* gb = sr(a.gb, so) + (size_t)row * H;
+#pragma unroll
+    for (int sl = 0; sl < NS; ++sl) {
+        float dy[MAXQ], x[MAXQ], gm[MAXQ];
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int j = lane + 64 * (MAXQ * sl + q);
+            dy[q] = j < H ? d[j] : 0.f;
+            x[q] = j < H ? xh[j] : 0.f;
+            gm[q] = j < H ? gamma[j] : 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) {
+            const int j = lane + 64 * (MAXQ * sl + q);
+            if (j < H) {
+                d[j] = rstd * ((dy[q] * gm[q] - m1) - x[q] * m2);
+                gy[j] = dy[q] * x[q];
+                gb[j] = dy[q];
+            }
+        }
+    }
+}
+
 void launch_ln(const LNArgs& a, hipStream_t s) {
     const int rows = a.mode == 0 ? (a.r[1] - a.r[0]) + (a.nrange > 1 ? a.r[3] - a.r[2] : 0) : a.r[1];
     const dim3 grid((rows + 3) / 4, 1, seeds_z(a.nseeds));
-    if (a.H <= 256) hipLaunchKernelGGL(k_ln<4>, grid, dim3(256), 0, s, a);
+    if (a.H > 64 * MAXQ) hipLaunchKernelGGL(k_ln_wide, grid, dim3(256), 0, s, a);
+    else if (a.H <= 256) hipLaunchKernelGGL(k_ln<4>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_ln<8>, grid, dim3(256), 0, s, a);
 }
 

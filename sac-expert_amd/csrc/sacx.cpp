@@ -140,6 +140,8 @@ struct sacx_handle {
     // pairs above are the first and the last hidden layer of each
     NetDims nd[4];
     bool deep = false;        // a net of other than 2 hidden layers: the generic plans (build_plan_generic)
+    bool wide = false;        // a used net has a hidden layer above 512 (sets deep): no fold, no k_fwd2, no ROWK
+                              // variant takes such a row -- the per-layer GEMMs and the wide row kernels do
     bool bc = false;          // use_expert == SACX_EXPERT_BC: the actor-only imitation update (build_plan_bc)
     // world-model variants (ABI 7): GaussianModel (a logstd per model, the NLL fit loss, noise in
     // sample / step) and --separate_reward_nn (a reward net r<k> beside each model net m<k>)
@@ -911,7 +913,7 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
 // K0 <= 32, H0 a multiple of 64 up to 256, layer 1 reading exactly layer 0's output.  Returns
 // whether it fused.
 bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& name) {
-    if (plan.size() < 2) return false;
+    if (plan.size() < 2 || h->wide) return false;     // (k_fwd2 holds layer 0's rows in LDS: <= 512 wide)
     Launch& L0 = plan[plan.size() - 2];
     Launch& L1 = plan[plan.size() - 1];
     const GemmArgs &a0 = L0.gemm, &a1 = L1.gemm;
@@ -2365,7 +2367,7 @@ void build_model_plan(sacx_handle* h) {
     const int ntm = (mb + 15) / 16;   // GaussianModel: logstd-gradient partials per column (row tiles)
     // model.bwd2 generated on model.bwd1's operand loads (rowk 7) for narrow heads (S + 1 <= 32)
     const bool bfold = fuse && h->mfuse >= 3 && O <= 32 && h->mtile != 2 && h->unaligned_b && !h->gm && !h->srn &&
-                       Dm == 2;
+                       Dm == 2 && !h->wide;
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
     // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
@@ -2405,7 +2407,8 @@ void build_model_plan(sacx_handle* h) {
         L.bytes = 4.0 * nm * mb * (2.0 * S + A + 1 + ldQ + O);
         h->mpres[h->sel] = L;
     }
-    const bool gfold = !pre && fuse && h->mfuse >= 2 && h->mtile != 2 && h->stride % 4 == 0 && ldQ % 4 == 0 && !h->srn;
+    const bool gfold = !pre && fuse && h->mfuse >= 2 && h->mtile != 2 && h->stride % 4 == 0 && ldQ % 4 == 0 && !h->srn &&
+                       !h->wide;              // (rowk 6 / 9 and k_fwd2: layer 0 up to 512 wide)
     if (!gfold && !pre) {
         Launch L{};
         L.kind = Launch::MGATHER;
@@ -2543,7 +2546,7 @@ void build_model_plan(sacx_handle* h) {
         // the gathered layer 0 and layer 1 as ONE k_fwd2 launch (SACX_MFWD2, default; K0 = S + A <= 32)
         if (i == 1 && gfold && h->mfwd2) fuse_fwd2(h, plan, "model.gather+fwd01");
         // or, pre-gathered, layer 0 (rowk 9: H0 <= 512, plain A) and layer 1 the same way
-        if (i == 1 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32) {
+        if (i == 1 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32 && !h->wide) {
             Launch& F0 = plan[plan.size() - 2];
             if (F0.kind == Launch::GEMM && F0.gemm.rowk == 0 && !F0.gemm.t32) {
                 F0.gemm.rowk = 9;
@@ -3435,6 +3438,7 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
                 if (cfg->act_layers[n][l] < 0 || cfg->act_layers[n][l] > 2) return bad("act_layers must be relu/tanh/elu");
     // every net's hidden layers: the ABI-8 lists, or the two of the older fields
     NetDims nd[4];
+    bool wide = false;      // a used net has a hidden layer above 512
     {
         const int leg_w[4][2] = {{cfg->hidden[0], cfg->hidden[1]},
                                  {cfg->critic_hidden[0] > 0 ? cfg->critic_hidden[0] : cfg->hidden[0],
@@ -3461,8 +3465,11 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
         for (int n = 0; n < 4; ++n) {
             if (!used[n]) continue;
             for (int l = 0; l < nd[n].D(); ++l) {
-                if (nd[n].h[l] <= 0 || nd[n].h[l] > 512)
-                    return bad("hidden sizes must be in [1, 512] (row kernels hold a row in 8 regs/lane)");
+                if (nd[n].h[l] <= 0 || nd[n].h[l] > SACX_MAX_WIDTH)
+                    return bad("hidden sizes must be in [1, 1024] (SACX_MAX_WIDTH: the row kernels walk a row in at "
+                               "most two 512-column slabs)");
+                static_assert(SACX_MAX_WIDTH == 1024, "the message above and k_sac.hip's WIDEQ name the bound");
+                wide = wide || nd[n].h[l] > 512;
                 if (nd[n].act[l] < 0 || nd[n].act[l] > 2) return bad("activations must be relu/tanh/elu");
             }
         }
@@ -3505,6 +3512,10 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     // the fused plans are built for two hidden layers per net; any other depth takes the generic
     // plans (SACX_GENERIC=1 forces them at two layers too: their parity test)
     h->deep = nd[0].D() != 2 || nd[1].D() != 2 || (cfg->use_expert && nd[2].D() != 2) || (h->srn && nd[3].D() != 2);
+    // a layer wider than 512 does too: the fused plans' row kernels and folds hold a row in 8
+    // registers per lane, the generic plans' heads have the slab-walking wide variants
+    h->wide = wide;
+    h->deep = h->deep || wide;
     if (const char* e = std::getenv("SACX_GENERIC")) h->deep = h->deep || std::atoi(e) != 0;
     h->bc = cfg->use_expert == SACX_EXPERT_BC;
     h->mb = cfg->use_expert ? (cfg->model_batch > 0 ? cfg->model_batch : 200) : 0;
@@ -3675,6 +3686,15 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     }
     h->abf_written.clear();
     h->wbf_attach = false;
+    // q.head's expert rows (qhead_block's SAC-EO tail) hold a world-model row in 8 registers per lane,
+    // and the wide q.head has no such rows: no plan may carry them beside a wide row
+    for (int sl = 0; sl < h->nslot; ++sl)
+        for (const Launch& L : h->plan[sl]) {
+            const QHeadArgs* q = L.kind == Launch::QHEAD ? &L.qh
+                                 : (L.kind == Launch::GEMM && (L.gemm.rowk == 1 || L.gemm.rowk == 2)) ? &L.gemm.qh : nullptr;
+            if (q && q->ne > 0 && (q->Hm1 > 512 || q->H1 > 512))
+                return fail(h, "internal: q.head with expert rows beside a hidden layer wider than 512");
+        }
     for (int sl = 1; sl < h->nslot; ++sl) {
         if (h->plan[0].size() != h->plan[sl].size()) return fail(h, "internal: slot plans differ");
         for (size_t i = 0; i < h->plan[0].size(); ++i)

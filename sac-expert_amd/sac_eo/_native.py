@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SACX_LIBPATH") or os.path.join(os.path.dirname(_HERE)
 
 SACX_ABI_VERSION = 8
 MAX_DEPTH = 4                   # SACX_MAX_DEPTH: hidden layers per net
+MAX_WIDTH = 1024                # SACX_MAX_WIDTH: widest hidden layer
 MAX_MODELS = 8                  # SACX_MAX_MODELS: --num_models
 STAGE_FLOATS = 65536            # SACX_STAGE_FLOATS (include/sacx.h)
 ACT = {"relu": 0, "tanh": 1, "elu": 2}

@@ -118,6 +118,8 @@ class EngineConfig:
         for n, (hid, acts) in enumerate(nets):
             if not 1 <= len(hid) <= N.MAX_DEPTH:
                 raise NotImplementedError(f"the device nets run 1 to {N.MAX_DEPTH} hidden layers (got {list(hid)})")
+            if any(not 1 <= int(w) <= N.MAX_WIDTH for w in hid):
+                raise NotImplementedError(f"the device nets run hidden layers 1 to {N.MAX_WIDTH} wide (got {list(hid)})")
             # ABI 8: every layer of every net (the legacy two-layer fields below stay filled as well)
             c.net_depth[n] = len(hid)
             for l, (w, a) in enumerate(zip(hid, acts)):
