@@ -62,6 +62,22 @@ enum sacx_role { SACX_ROLE_WORK = 0, SACX_ROLE_PARAM = 1, SACX_ROLE_TARGET = 2, 
 #define SACX_EXPERT_EO 1
 #define SACX_EXPERT_BC 2
 
+/* sacx_config.actor_gaussian.
+   SACX_ACTOR_GAUSSIAN_TRAIN: a plain (unsquashed) GaussianActor that is trained on-policy by the PPO
+   actor update (sac_eo/algs/model_free/ppo.py through GaussianActor.neglogp / entropy / kl /
+   get_kl_info, continuous_actors.py:132-192): the sacx_ppo_* entry points below.  Its arena holds the
+   "ppo.*" segments beside the layout of a SACX_ACTOR_GAUSSIAN handle: the rollout table (s, a, adv and
+   the per-row nlp_old, mean_ref, ls_ref; cfg.buffer_capacity rows at most), the minibatch row buffers
+   (cfg.batch rows at most), alpha with its Adam moments ("ppo.alpha"), the step statistics ring
+   ("ppo.stats": loss, mean entropy, grad_norm_pre, grad_norm_post, alpha, the surrogate mean, the
+   minibatch advantage std + 1e-8, the step number).  It acts as a SACX_ACTOR_GAUSSIAN handle does.
+   Refused at sacx_create: actor_output_norm (no backward is built for it), gemm_bf16, seeds > 1,
+   use_expert != 0; sacx_dp_init / sacx_dp_init_local fail on it.  sacx_sac_step and
+   sacx_actor_evaluate fail on it as on a SACX_ACTOR_GAUSSIAN handle. */
+#define SACX_ACTOR_SQUASHED 0
+#define SACX_ACTOR_GAUSSIAN 1
+#define SACX_ACTOR_GAUSSIAN_TRAIN 2
+
 /* Flags for sacx_sac_step. */
 #define SACX_STEP_EXTERNAL_RANDOMS 1  /* skip the device sampler: caller filled slot0.idx / slot0.noise */
 #define SACX_STEP_EAGER 2             /* launch kernels directly instead of replaying a hipGraph */
@@ -334,6 +350,60 @@ int sacx_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, 
 enum { SACX_DIAG_DISC = 1, SACX_DIAG_EXPERT_ACTIONS = 2 };
 int sacx_expert_diag(sacx_handle* h, const float* s_e, const float* a_e, const float* sp_e, int32_t n,
                      int32_t flags, float delta_clip, float* out);
+/* --- the PPO actor update of a trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN handles) ------
+ * Every call below fails with a message on any other handle.  Device rows in, device rows out,
+ * asynchronous on the bound stream unless stated; rows go through the actor in chunks of 1024. */
+/* GaussianActor.neglogp (continuous_actors.py:132-138) on s[n,S], a[n,A]: nlp_out[n] =
+ * 0.5 sum_j (((a - mean) / e^ls)^2 + 2 ls + log 2 pi), (mean, ls) = _forward(s) (:74-100: the state
+ * normalised, ls = logstd + log(std_mult), or log(softplus(raw)) + log(std_mult) - log(log 2) with
+ * per_state_std, floored at log 1e-3). */
+int sacx_ppo_neglogp(sacx_handle* h, const float* s, const float* a, int64_t n, float* nlp_out);
+/* GaussianActor._forward / get_kl_info / entropy (:74-100, :186-192, :140-143) on s[n,S]:
+ * mean_out[n,A], logstd_out[n,A], ent_out[n] = 0.5 sum_j (2 ls + log 2 pi + 1); each nullable. */
+int sacx_ppo_dist(sacx_handle* h, const float* s, int64_t n, float* mean_out, float* logstd_out, float* ent_out);
+/* GaussianActor.kl(direction='forward') (:159-184) on s[n,S] against mean_ref[n,A], logstd_ref[n,A]:
+ * kl_out[n] = 0.5 sum_j (((mean - mean_ref)^2 + e^{2 ls_ref}) / e^{2 ls} + 2 ls - 2 ls_ref - 1). */
+int sacx_ppo_kl(sacx_handle* h, const float* s, const float* mean_ref, const float* logstd_ref, int64_t n,
+                float* kl_out);
+/* The head of PPO.update (ppo.py:43-46): stores the rollout s[n,S], a[n,A], adv[n] (device pointers,
+ * 1 <= n <= cfg.buffer_capacity) as the table the steps gather from, computes with the weights as
+ * they stand neglogp_old, the reference distribution (kl_info_ref) and the mean entropy over all
+ * rows, and resets the per-update accumulators (the two grad-norm sums, the step count). */
+int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* adv, int64_t n);
+/* Run-time inputs of the minibatch steps (PPO._setup's update_kwargs, ppo.py:13-39).  actor_lr is
+ * the CURRENT rate of the actor's Adam: the adaptlr rule (:109-117) changes it between update()
+ * calls while the iteration count and the moments persist, so it is read from device memory by the
+ * step's launches and is no constant of a captured graph. */
+typedef struct sacx_ppo_params {
+    float eps_ppo;          /* clip range: r in [1 - eps, 1 + eps] */
+    float max_grad_norm;    /* clip_by_global_norm bound; <= 0: None (both norms the same) */
+    float ent_targ;
+    float alpha_lr;
+    float actor_lr;
+    int32_t ent_reg;        /* != 0: Keras Adam on alpha (gradient mean(ent) - ent_targ), then max(alpha, 0) */
+    int32_t adv_center;     /* adv - mean(adv) over the minibatch (:71-75) */
+    int32_t adv_scale;      /* / (std(adv) + 1e-8), the std of the uncentred minibatch (:72, :76-77) */
+} sacx_ppo_params;
+/* n_steps x PPO._apply_actor_grad (ppo.py:122-147, :225-239, the expert_reg is None branch) on
+ * the minibatches idx[n_steps, mb] (HOST array of table rows, each in [0, n); 1 <= mb <= cfg.batch):
+ * gather + advantage statistics, the actor forward, the clipped surrogate - alpha (mean(ent) -
+ * ent_targ) with TF's gradient rules, alpha's step (with the alpha from before it in the actor
+ * gradient), clip_by_global_norm, Keras Adam on the actor's trainables (logstd included unless
+ * per_state_std) at params->actor_lr.  No host synchronisation between the steps; replayed as
+ * captured graphs of 64 / 8 / 1 steps, or launched directly with SACX_STEP_EAGER (bit-identical).
+ * Requires a sacx_ppo_begin.  Each step appends a row to the "ppo.stats" ring. */
+int sacx_ppo_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const sacx_ppo_params* params,
+                   int32_t flags);
+/* The tail of PPO.update (ppo.py:86-106) over the table's rows with the weights as they stand now:
+ * out[0] = ent (from sacx_ppo_begin), out[1] = tv = 0.5 mean |r - 1|, out[2] = mean kl against the
+ * reference distribution, out[3] = outside_clip = mean(|r - 1| > eps_ppo), out[4] / out[5] =
+ * grad_norm_pre / grad_norm_post averaged over the steps since sacx_ppo_begin (0 without a step),
+ * out[6] = alpha, out[7] = the step count.  out: HOST double[8] (the f32 device values widened;
+ * outside_clip is the row count over n in f64, as np.mean of booleans).  Synchronous. */
+int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out);
+/* The launches of one minibatch step of mb rows, as sacx_plan_info. */
+int sacx_ppo_plan_info(sacx_handle* h, int32_t mb, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
+
 int sacx_sync(sacx_handle* h);
 /* Brings the arena to the state the calls so far define, without waiting: runs an alpha branch
  * the drop-in loop's one-update steps deferred (its alpha Adam, stats row and counters; see

@@ -5513,7 +5513,12 @@ __global__ __launch_bounds__(256) void k_adam_apply(AdamApplyArgs a) {
     }
 }
 
+void launch_ppo_adam(const AdamApplyArgs& a, hipStream_t s);     // (k_ppo_adam, with the PPO kernels below)
 void launch_adam_apply(const AdamApplyArgs& a, hipStream_t s) {
+    if (a.lr_dev != nullptr) {
+        launch_ppo_adam(a, s);
+        return;
+    }
     hipLaunchKernelGGL(k_adam_apply, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
 }
 
@@ -6062,7 +6067,301 @@ void launch_gnorm(const GNormArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_gnorm_part, dim3(GNORM_PARTS), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_gnorm_final, dim3(1), dim3(64), 0, s, a);
 }
+void launch_gnorm_part(const GNormArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_gnorm_part, dim3(GNORM_PARTS), dim3(256), 0, s, a);
+}
 void launch_mfinal(const MFinalArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_mfinal, dim3(1), dim3(64), 0, s, a);
+}
+
+// ==================================================================== PPO actor update
+// The on-policy step of a trainable GaussianActor handle (ppo.py:41-147, :225-239; the
+// distribution of continuous_actors.py:74-192).  The matrix work is the generic plan's GEMM
+// launches (actor.fwd<i>, actor.bwd<i>, the dW launches in EPI_STORE form, k_gnorm_part,
+// k_adam_apply); the kernels below are the rows around them.
+
+// the four wave sums of a 256-thread workgroup added in a fixed order: every thread gets the
+// bit-identical block sum
+__device__ __forceinline__ float block_sum_256(float v, float* red) {
+    const float w = wave_sum(v);
+    __syncthreads();                // (red may still be read from the previous sum)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// GaussianActor._forward's (mean, logstd) of column `lane` of output row `row` (continuous_actors.py:
+// 83-95): ls = logstd + logstd_init, or log(softplus(raw)) + logstd_init, floored at log(1e-3).
+// pass: the unfloored value is >= the floor (TF maximum: ties go to the first argument, so the
+// gradient passes there); inv_sp / sden: LogGrad's 1 / softplus(raw) and SoftplusGrad's
+// exp(-raw) + 1 (per_state_std; 1 otherwise)
+struct PpoCol {
+    float mean, ls, inv_sp, sden;
+    bool pass;
+};
+__device__ __forceinline__ PpoCol ppo_col(const PpoDist& d, int row, int lane, bool jok) {
+    PpoCol c;
+    const float* o = d.O + (size_t)row * d.Aout;
+    c.mean = jok ? o[lane] : 0.f;
+    c.inv_sp = 1.f;
+    c.sden = 1.f;
+    float lun;
+    if (d.per_state_std) {
+        const float raw = jok ? o[d.A + lane] : 0.f;
+        const float sp = softplus_f(raw);
+        lun = logf(sp) + d.logstd_init;
+        c.inv_sp = 1.f / sp;
+        c.sden = expf(-raw) + 1.f;
+    } else {
+        lun = (jok ? d.logstd[lane] : 0.f) + d.logstd_init;
+    }
+    const float fl = logf(1e-3f);
+    c.pass = lun >= fl;
+    c.ls = c.pass ? lun : fl;
+    return c;
+}
+
+// neglogp and entropy of a row from its columns (continuous_actors.py:132-143): wave sums over j < A
+__device__ __forceinline__ float ppo_nlp(const PpoCol& c, float a, bool jok, float& z, float& sd) {
+    sd = expf(c.ls);
+    z = (a - c.mean) / sd;
+    return 0.5f * wave_sum(jok ? (z * z + 2.f * c.ls) + LOG2PI_F : 0.f);
+}
+__device__ __forceinline__ float ppo_ent(const PpoCol& c, bool jok) {
+    return 0.5f * wave_sum(jok ? (2.f * c.ls + LOG2PI_F) + 1.f : 0.f);
+}
+
+__global__ __launch_bounds__(256) void k_ppo_gather(PpoGatherArgs g) {
+    __shared__ float red[4];
+    const int mb = g.mb, S = g.S, A = g.A, ldS = g.ldS;
+    const int64_t n = g.ctl->n_rows;
+    if (n < 1) return;              // (no table: the host refuses the step before it gets here)
+    const int32_t* idx = g.idx_ring + (size_t)(g.ctl->seq % PPO_IDX_CAP) * g.idx_ld;
+    // an index outside the table is clamped into it (the host checks every index it uploads)
+    auto row_of = [&](int i) -> int64_t {
+        const int64_t r = idx[i];
+        return r < 0 ? 0 : (r >= n ? n - 1 : r);
+    };
+    // np.mean / np.std of the uncentred minibatch (ppo.py:71-72), the same sums in every workgroup
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < mb; i += 256) acc = acc + g.adv[row_of(i)];
+    const float mean = block_sum_256(acc, red) / (float)mb;
+    float acc2 = 0.f;
+    for (int i = threadIdx.x; i < mb; i += 256) {
+        const float d = g.adv[row_of(i)] - mean;
+        acc2 = acc2 + d * d;
+    }
+    const float sd = sqrtf(block_sum_256(acc2, red) / (float)mb) + 1e-8f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        g.acc[PPO_ACC_AMEAN] = mean;
+        g.acc[PPO_ACC_ASTD] = sd;
+    }
+    const int center = g.par->adv_center, scale = g.par->adv_scale;
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    constexpr int RW = PPO_GATHER_ROWS / 4;     // rows per wave
+    for (int k = 0; k < RW; ++k) {
+        const int i = blockIdx.x * PPO_GATHER_ROWS + wave * RW + k;
+        if (i >= mb) break;
+        const int64_t r = row_of(i);
+        for (int c = lane; c < ldS; c += 64)
+            g.X[(size_t)i * ldS + c] = c < S ? (g.s[r * S + c] - g.s_mean[c]) / g.s_den[c] : 0.f;
+        for (int j = lane; j < A; j += 64) g.Arow[(size_t)i * A + j] = g.a[r * A + j];
+        if (lane == 0) {
+            float x = g.adv[r];
+            if (center) x = x - mean;
+            if (scale) x = x / sd;
+            g.advn[i] = x;
+            g.nlpo[i] = g.nlp_old[r];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ppo_head(PpoHeadArgs g) {
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= g.mb) return;
+    const int A = g.d.A;
+    const bool jok = lane < A;
+    const PpoCol c = ppo_col(g.d, row, lane, jok);
+    const float a = jok ? g.Arow[(size_t)row * A + lane] : 0.f;
+    float z, sd;
+    const float nlp = ppo_nlp(c, a, jok, z, sd);
+    const float ent = ppo_ent(c, jok);
+    const float adv = g.advn[row], old = g.nlpo[row];
+    const float lo = g.par->clip_lo, hi = g.par->clip_hi;
+    // ppo.py:135-140; TF's maximum sends the gradient to its first argument on ties (every row inside
+    // the clip range), and a row whose clipped branch wins has r outside the range: gradient 0
+    const float r = expf(old - nlp);
+    const float rc = fminf(fmaxf(r, lo), hi);
+    const float surr = (r * adv) * -1.f, clp = (rc * adv) * -1.f;
+    const bool take = surr >= clp;
+    const float inv_mb = 1.f / (float)g.mb;
+    const float gn = take ? (adv * r) * inv_mb : 0.f;      // d loss / d nlp_cur (dr / dnlp = -r)
+    const float alpha = g.alpha[0];
+    const float dmean = gn * (-(z / sd));                  // d nlp / d mean = -(a - mean) / sd^2
+    float dls = gn * (1.f - z * z) - alpha * inv_mb;       // d nlp / d ls = 1 - z^2, d ent / d ls = 1
+    dls = c.pass ? dls : 0.f;
+    if (jok) {
+        g.D3[(size_t)row * g.d.Aout + lane] = dmean;
+        if (g.d.per_state_std) g.D3[(size_t)row * g.d.Aout + A + lane] = (dls * c.inv_sp) / c.sden;
+        else g.E[(size_t)row * A + lane] = dls;
+    }
+    if (lane == 0) {
+        g.row_loss[row] = fmaxf(surr, clp);
+        g.row_ent[row] = ent;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ppo_final(PpoFinalArgs g) {
+    __shared__ float red[4];
+    float al = 0.f, ae = 0.f, ag = 0.f;
+    for (int i = threadIdx.x; i < g.mb; i += 256) {
+        al = al + g.row_loss[i];
+        ae = ae + g.row_ent[i];
+    }
+    for (int i = threadIdx.x; i < GNORM_PARTS; i += 256) ag = ag + g.gpart[i];
+    const float sl = block_sum_256(al, red), se = block_sum_256(ae, red), tot = block_sum_256(ag, red);
+    if (threadIdx.x != 0) return;
+    const PpoPar par = *g.par;
+    const float pg = sl / (float)g.mb, em = se / (float)g.mb;
+    float alpha = g.alpha[0];
+    const float loss = pg - alpha * (em - par.ent_targ);
+    // clip_by_global_norm (ppo.py:230-235), k_gnorm_final's arithmetic; None: both norms the same
+    const float norm = sqrtf(tot);
+    float scale = 1.f, post = norm;
+    if (par.max_grad_norm > 0.f) {
+        scale = par.max_grad_norm * fminf(1.f / norm, 1.f / par.max_grad_norm) + (norm - norm);
+        post = norm * scale;
+    }
+    PpoCtl* ctl = g.ctl;
+    if (par.ent_reg) {              // Keras Adam on alpha with gradient +(mean(ent) - ent_targ), then max(alpha, 0)
+        const int64_t t = ctl->t_alpha + 1;
+        const float tt = (float)t;
+        const float lr_t = par.alpha_lr * sqrtf(1.f - powf(0.999f, tt)) / (1.f - powf(0.9f, tt));
+        adam_update(&g.alpha[0], &g.alpha[1], &g.alpha[2], em - par.ent_targ, lr_t);
+        alpha = fmaxf(g.alpha[0], 0.f);
+        g.alpha[0] = alpha;
+        ctl->t_alpha = t;
+    }
+    const int64_t seq = ctl->seq;
+    float* st = g.stats + (size_t)(seq % g.stats_cap) * 8;
+    st[PPO_STAT_LOSS] = loss;
+    st[PPO_STAT_ENT] = em;
+    st[PPO_STAT_GN_PRE] = norm;
+    st[PPO_STAT_GN_POST] = post;
+    st[PPO_STAT_ALPHA] = alpha;
+    st[PPO_STAT_PG] = pg;
+    st[PPO_STAT_ADV_STD] = g.acc[PPO_ACC_ASTD];
+    st[PPO_STAT_STEP] = (float)(seq + 1);
+    g.acc[PPO_ACC_PRE] = g.acc[PPO_ACC_PRE] + norm;
+    g.acc[PPO_ACC_POST] = g.acc[PPO_ACC_POST] + post;
+    g.acc[PPO_ACC_SCALE] = scale;
+    ctl->seq = seq + 1;
+    ctl->t_pi = ctl->t_pi + 1;      // (the Adam launch behind this one takes the advanced count: t_adv)
+    ctl->n_steps = ctl->n_steps + 1;
+}
+
+__global__ __launch_bounds__(256) void k_ppo_rows(PpoRowsArgs g) {
+    const int wave = wave_id(), lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= g.m) return;
+    const int A = g.d.A;
+    const bool jok = lane < A;
+    const PpoCol c = ppo_col(g.d, row, lane, jok);
+    if (jok && g.mean_out != nullptr) g.mean_out[(size_t)row * A + lane] = c.mean;
+    if (jok && g.ls_out != nullptr) g.ls_out[(size_t)row * A + lane] = c.ls;
+    if (g.ent_out != nullptr) {
+        const float ent = ppo_ent(c, jok);
+        if (lane == 0) g.ent_out[row] = ent;
+    }
+    if (g.a != nullptr) {
+        float z, sd;
+        const float nlp = ppo_nlp(c, jok ? g.a[(size_t)row * A + lane] : 0.f, jok, z, sd);
+        if (lane == 0 && g.nlp_out != nullptr) g.nlp_out[row] = nlp;
+        if (lane == 0 && g.rdiff_out != nullptr) g.rdiff_out[row] = fabsf(expf(g.nlp_old[row] - nlp) - 1.f);
+    }
+    if (g.mean_ref != nullptr) {    // forward KL (continuous_actors.py:176-184)
+        const float mr = jok ? g.mean_ref[(size_t)row * A + lane] : 0.f;
+        const float lr = jok ? g.ls_ref[(size_t)row * A + lane] : 0.f;
+        // ((dm^2 + e^{2 lr}) / e^{2 l} + 2 l - 2 lr - 1 as written cancels terms of order 1 down to
+        // order (l - lr)^2 -- in f32 an absolute error of ~1e-7 per dimension, the same in every row of
+        // a state-independent std, against a kl of 1e-3 .. 1e-2 after an update.  The same value without
+        // the cancellation: e^{2 lr} / e^{2 l} - 1 = expm1(-2 (l - lr)).)
+        const float dm = c.mean - mr;
+        const float dl = c.ls - lr;
+        const float vec = (dm * dm) / expf(2.f * c.ls) + (expm1f(-2.f * dl) + 2.f * dl);
+        const float kl = 0.5f * wave_sum(jok ? vec : 0.f);
+        if (lane == 0) g.kl_out[row] = kl;
+    }
+}
+
+__global__ __launch_bounds__(DIAG_THREADS) void k_ppo_reduce(PpoReduceArgs g) {
+    __shared__ float red[DIAG_THREADS / 64];
+    for (int c = 0; c < 3; ++c) {
+        if (g.c[c] == nullptr) continue;
+        const bool cnt = c == 2 && g.count2 != 0;
+        float acc = 0.f;
+        for (int64_t i = threadIdx.x; i < g.n; i += DIAG_THREADS) {
+            const float x = g.c[c][i];
+            acc = acc + (cnt ? (x > g.thr ? 1.f : 0.f) : x);
+        }
+        const float s = block_sum_1024(acc, red);
+        // (the count is stored as it is, exact below 2^24 rows: the host divides in double, np.mean of bools)
+        if (threadIdx.x == 0) g.out[c][0] = cnt ? s : (c == 0 ? g.half0 : 1.f) * (s / (float)g.n);
+    }
+}
+
+// host values into the arena in stream order (kernel arguments: no staging copy, no synchronisation):
+// the step's parameters, or (n >= 0) a new table's row count with the per-update accumulators reset
+__global__ __launch_bounds__(64) void k_ppo_set(PpoPar* dst, PpoPar v, PpoCtl* ctl, float* acc, int64_t n) {
+    if (threadIdx.x != 0) return;
+    if (dst != nullptr) *dst = v;
+    if (n >= 0) {
+        ctl->n_rows = n;
+        ctl->n_steps = 0;
+        acc[PPO_ACC_PRE] = 0.f;
+        acc[PPO_ACC_POST] = 0.f;
+    }
+}
+void launch_ppo_set(PpoPar* dst, const PpoPar& v, PpoCtl* ctl, float* acc, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_set, dim3(1), dim3(64), 0, s, dst, v, ctl, acc, n);
+}
+
+// k_adam_apply's arithmetic with the learning rate and the optimiser's iteration count read from the
+// device (AdamApplyArgs::lr_dev / t_dev) and the clip scale always present: the PPO actor's Adam.  Its own
+// kernel, so that k_adam_apply and every launch of the other plans stay the code they were.
+__global__ __launch_bounds__(256) void k_ppo_adam(AdamApplyArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    const float tt = (float)(a.t_dev[0] + 1 - a.t_adv);
+    const float lr_t = a.lr_dev[0] * sqrtf(1.f - powf(0.999f, tt)) / (1.f - powf(0.9f, tt));
+    float* P = a.P + i;
+    const float gr = (P[3 * a.p_stride] * a.grad_scale) * a.scale_dev[0];
+    const float e0 = P[0], e1 = P[a.p_stride], e2 = P[2 * a.p_stride];
+    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-7f;
+    const float mm1 = e1 + (gr - e1) * (1.f - b1);
+    const float vv1 = e2 + (gr * gr - e2) * (1.f - b2);
+    P[0] = e0 - (mm1 * lr_t) / (sqrtf(vv1) + eps);
+    P[a.p_stride] = mm1;
+    P[2 * a.p_stride] = vv1;
+}
+void launch_ppo_adam(const AdamApplyArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+}
+
+void launch_ppo_gather(const PpoGatherArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_gather, dim3((a.mb + PPO_GATHER_ROWS - 1) / PPO_GATHER_ROWS), dim3(256), 0, s, a);
+}
+void launch_ppo_head(const PpoHeadArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_head, dim3((a.mb + 3) / 4), dim3(256), 0, s, a);
+}
+void launch_ppo_final(const PpoFinalArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_final, dim3(1), dim3(256), 0, s, a);
+}
+void launch_ppo_rows(const PpoRowsArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_rows, dim3((a.m + 3) / 4), dim3(256), 0, s, a);
+}
+void launch_ppo_reduce(const PpoReduceArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_ppo_reduce, dim3(1), dim3(DIAG_THREADS), 0, s, a);
 }
 }  // namespace sacx

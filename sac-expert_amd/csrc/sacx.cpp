@@ -65,7 +65,7 @@ struct SegInfo {
 
 struct Launch {
     enum Kind { RNG, GATHER, GEMM, AHEAD, QHEAD, ABWD, FINAL, MGATHER, MLOSS, MFINAL, ALLREDUCE, APPLY, AAPPLY,
-                GNORM, LNORM } kind;
+                GNORM, LNORM, PPOGATHER, PPOHEAD, GNPART, PPOFINAL } kind;
     std::string name;
     RngArgs rng;
     GatherArgs gather;
@@ -80,6 +80,9 @@ struct Launch {
     AdamApplyArgs ap;          // APPLY
     GNormArgs gn;              // GNORM
     LNArgs ln;                 // LNORM
+    PpoGatherArgs pg;          // PPOGATHER
+    PpoHeadArgs ph;            // PPOHEAD
+    PpoFinalArgs pf;           // PPOFINAL (GNPART: gn)
     float* ar_buf = nullptr;   // ALLREDUCE: in-place sum over the data-parallel ranks
     int64_t ar_count = 0;
     int grid = 0, block = 256;
@@ -109,6 +112,10 @@ const char* kernel_family(Launch::Kind k) {
         case Launch::AAPPLY: return "k_alpha_apply";
         case Launch::GNORM: return "k_gnorm";
         case Launch::LNORM: return "k_ln";
+        case Launch::PPOGATHER: return "k_ppo_gather";
+        case Launch::PPOHEAD: return "k_ppo_head";
+        case Launch::GNPART: return "k_gnorm";
+        case Launch::PPOFINAL: return "k_ppo_final";
     }
     return "?";
 }
@@ -150,6 +157,12 @@ struct sacx_handle {
     int Hr0 = 0, Hr1 = 0;     // the reward nets' hidden sizes (srn)
     int racts[2] = {0, 0};    // their hidden-layer activations
     bool ln = false;          // --actor_layer_norm: Dense -> LayerNorm -> tanh on the actor's layer 0
+    // actor_gaussian == SACX_ACTOR_GAUSSIAN_TRAIN: the PPO actor step (sacx_ppo_*, build_ppo_plan)
+    bool ppo = false;
+    int64_t ppo_rows = 0;     // rows of the rollout table (sacx_ppo_begin; 0: none yet)
+    int64_t ppo_seq_host = 0; // minibatch steps issued (mirrors PpoCtl::seq: the index ring position)
+    std::map<int, std::vector<Launch>> ppo_plans;                  // minibatch rows -> one step's launches
+    std::map<std::pair<int, int>, hipGraphExec_t> ppo_graphs;      // (minibatch rows, steps) -> graph
     // layout
     std::vector<SegInfo> segs;
     std::map<std::string, size_t> seg_index;
@@ -698,6 +711,35 @@ void build_layout(sacx_handle* h) {
     for (const Mid& m : mids)
         for (int i = 1; i + 1 < h->nd[m.net].D(); ++i)
             h->add(m.p + std::to_string(i), m.rows, h->nd[m.net].h[i], F, 0);
+    // the PPO actor step of a trainable GaussianActor handle: after everything else, so the segments
+    // of every other handle kind keep their offsets
+    if (h->ppo) {
+        const int64_t cap = h->cap;
+        static_assert(sizeof(PpoCtl) == 64 && sizeof(PpoPar) == 64, "ppo.ctl is 8 int64, ppo.par 16 words");
+        h->add("ppo.ctl", 1, 8, SACX_I64, SACX_ROLE_STATE);
+        h->add("ppo.par", 1, 16, F, SACX_ROLE_WORK);
+        h->add("ppo.alpha", 1, 3, F, SACX_ROLE_STATE);       // alpha (starts at 0, ppo.py:36), Adam m, v
+        h->add("ppo.acc", 1, 8, F, SACX_ROLE_STATE);
+        h->add("ppo.log", 1, 8, F, SACX_ROLE_STATE);
+        h->add("ppo.stats", h->stats_cap, 8, F, SACX_ROLE_STATE);
+        h->add("ppo.idx", PPO_IDX_CAP, B, SACX_I32, SACX_ROLE_WORK);
+        // the rollout table and what sacx_ppo_begin computes per row
+        h->add("ppo.s", cap, S, F, SACX_ROLE_STATE);
+        h->add("ppo.a", cap, A, F, SACX_ROLE_STATE);
+        h->add("ppo.adv", 1, cap, F, SACX_ROLE_STATE);
+        h->add("ppo.nlp_old", 1, cap, F, SACX_ROLE_STATE);
+        h->add("ppo.mean_ref", cap, A, F, SACX_ROLE_STATE);
+        h->add("ppo.ls_ref", cap, A, F, SACX_ROLE_STATE);
+        h->add("ppo.tmp", 2, cap, F, 0);                     // per-row entropy / |r - 1|, kl of the whole-rollout passes
+        // the minibatch rows of a step (the hidden layers and deltas are the update's ws.Ha* / ws.Da*)
+        h->add("ppo.X", B, h->ldS, F, 0);
+        h->add("ppo.A", B, A, F, 0);
+        h->add("ppo.advn", 1, B, F, 0);
+        h->add("ppo.nlpo", 1, B, F, 0);
+        h->add("ppo.rl", 2, B, F, 0);                        // per-row loss, entropy
+        h->add("ppo.O", std::max(B, ACT_CAP), h->Aout, F, 0);   // the actor's output rows (a step's, or a chunk's)
+        h->add("ppo.gnorm", 1, GNORM_PARTS, F, 0);
+    }
     h->arena_bytes = (h->arena_bytes + 255) & ~uint64_t(255);
 }
 
@@ -2693,6 +2735,10 @@ void enqueue(const Launch& L, sacx_handle* h, hipStream_t s) {
         case Launch::AAPPLY: launch_alpha_apply(L.fin, s); break;
         case Launch::GNORM: launch_gnorm(L.gn, s); break;
         case Launch::LNORM: launch_ln(L.ln, s); break;
+        case Launch::PPOGATHER: launch_ppo_gather(L.pg, s); break;
+        case Launch::PPOHEAD: launch_ppo_head(L.ph, s); break;
+        case Launch::GNPART: launch_gnorm_part(L.gn, s); break;
+        case Launch::PPOFINAL: launch_ppo_final(L.pf, s); break;
     }
 }
 
@@ -3416,6 +3462,20 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
         if (cfg->seeds > 1) return bad("BC (use_expert = SACX_EXPERT_BC) runs one learner per handle (seeds <= 1)");
         if (cfg->actor_gaussian) return bad("BC (use_expert = SACX_EXPERT_BC) trains the squashed actor");
     }
+    if (cfg->actor_gaussian < 0 || cfg->actor_gaussian > SACX_ACTOR_GAUSSIAN_TRAIN)
+        return bad("actor_gaussian must be SACX_ACTOR_SQUASHED, SACX_ACTOR_GAUSSIAN or SACX_ACTOR_GAUSSIAN_TRAIN");
+    if (cfg->actor_gaussian == SACX_ACTOR_GAUSSIAN_TRAIN) {
+        if (cfg->actor_output_norm)
+            return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN): actor_output_norm has no backward (set it to 0)");
+        if (cfg->gemm_bf16) return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN) runs fp32 only (gemm_bf16 = 0)");
+        if (cfg->seeds > 1)
+            return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN) runs one learner per handle (seeds <= 1)");
+        if (cfg->use_expert)
+            return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN): use_expert must be SACX_EXPERT_OFF "
+                       "(the expert_reg branch of the PPO step is not built)");
+        if (cfg->buffer_capacity > (int64_t(1) << 24))
+            return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN): buffer_capacity (rollout rows) must be <= 2^24");
+    }
     if (cfg->use_expert) {
         const int nmc = cfg->num_models > 0 ? cfg->num_models : 2;
         if (cfg->expert_batch <= 0) return bad("expert_batch must be positive");
@@ -3520,6 +3580,7 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     h->bc = cfg->use_expert == SACX_EXPERT_BC;
     h->mb = cfg->use_expert ? (cfg->model_batch > 0 ? cfg->model_batch : 200) : 0;
     h->ln = cfg->actor_layer_norm != 0;
+    h->ppo = cfg->actor_gaussian == SACX_ACTOR_GAUSSIAN_TRAIN;
     h->ldS = (int)r4(h->S);
     h->ldQ = (int)r4(h->S + h->A);
     h->stride = (int)r4(2 * h->S + h->A + 2);
@@ -3555,6 +3616,7 @@ void sacx_destroy(sacx_handle* h) {
     for (auto& m : h->mgraphs)
         for (auto& kv : m) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->roll_graphs) (void)hipGraphExecDestroy(kv.second);
+    for (auto& kv : h->ppo_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto e : h->events) (void)hipEventDestroy(e);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->done_host) (void)hipHostFree(h->done_host);
@@ -3678,7 +3740,9 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     // keep them current (not the data-parallel modes, whose Adam runs in k_adam_apply)
     h->wbf_attach = (!h->wbf_mats.empty() || !h->abf_segs.empty()) && h->tile32 > 0 && h->dp_ranks == 0;
     h->wbf_live = h->wbf_attach;
-    for (int sl = 0; sl < h->nslot; ++sl) {
+    // (a trainable GaussianActor handle has no SAC / BC update: its step plans are built per minibatch
+    // size by build_ppo_plan, and cfg.batch only bounds them)
+    for (int sl = 0; sl < h->nslot && !h->ppo; ++sl) {
         h->abf_written.clear();
         if (h->bc) build_plan_bc(h, sl, sl == 0);
         else if (h->deep) build_plan_generic(h, sl, sl == 0);
@@ -3734,6 +3798,12 @@ int sacx_resync(sacx_handle* h) {
     h->seq_host = c.step_seq;
     h->cur_size_host = c.cur_size;
     h->mfit_hosts[h->sel] = c.mfit_seq;
+    if (h->ppo) {                            // the step sequence (index ring position) and the table's rows
+        PpoCtl pc{};
+        HIPCHK(h, hipMemcpy(&pc, h->ptr<PpoCtl>("ppo.ctl"), sizeof(PpoCtl), hipMemcpyDeviceToHost));
+        h->ppo_seq_host = pc.seq;
+        h->ppo_rows = pc.n_rows;
+    }
     return 0;
 }
 
@@ -3752,6 +3822,7 @@ int sacx_dp_init(sacx_handle* h, const void* id, int32_t nranks, int32_t rank) {
     if (h->seeds > 1) return fail(h, "data-parallel mode needs seeds = 1");
     if (!id || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, "bad data-parallel arguments");
     if (h->cfg.use_expert) return fail(h, "data-parallel mode covers plain SAC (use_expert = 0)");
+    if (h->ppo) return fail(h, "data-parallel mode covers plain SAC (not a trainable GaussianActor handle)");
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     const ncclResult_t r = ncclCommInitRank(&h->comm, nranks, uid, rank);
@@ -3768,6 +3839,7 @@ int sacx_dp_init_local(sacx_handle* h, int32_t nranks, int32_t rank) {
     if (h->seeds > 1) return fail(h, "data-parallel mode needs seeds = 1");
     if (nranks < 1 || nranks > DP_LOCAL_MAX || rank < 0 || rank >= nranks) return fail(h, "bad data-parallel arguments");
     if (h->cfg.use_expert) return fail(h, "data-parallel mode covers plain SAC (use_expert = 0)");
+    if (h->ppo) return fail(h, "data-parallel mode covers plain SAC (not a trainable GaussianActor handle)");
     h->dp_ranks = nranks;
     h->dp_rank = rank;
     h->dp_local = true;
@@ -4270,6 +4342,7 @@ int sacx_rng_get_state(sacx_handle* h, uint32_t key[624], int32_t* pos, int32_t*
 int sacx_sac_step(sacx_handle* h, int64_t n_steps, int64_t num_timesteps, int32_t ts_increment, int32_t flags) {
     if (!h || !h->bound) return fail(h, "not bound");
     if (h->dp_local) return fail(h, "in-process data-parallel ranks step together (sacx_dp_local_step)");
+    if (h->ppo) return fail(h, "trainable GaussianActor handle: no SAC / BC step (sacx_ppo_steps trains it)");
     if (h->cfg.actor_gaussian) return fail(h, "GaussianActor handle: inference only (sacx_actor_act)");
     if (n_steps <= 0) return 0;
     // the drop-in loop's one-update steps: the randoms drawn speculatively after the previous
@@ -5158,6 +5231,399 @@ int sacx_time_graph(sacx_handle* h, int64_t n_replays, const char* skip_kernel, 
     *ms_out = ms;
     h->seq_host += (n_replays + 1) * h->graph_steps;
     return 0;
+}
+
+// ---------------------------------------------------------------- PPO actor update
+// One minibatch step of mb rows (ppo.py:122-147, :225-239) as a launch list:
+//   ppo.gather     table rows by index -> normalised states, actions, adv (centred / scaled), nlp_old
+//   actor.fwd<i>   the hidden layers (actor.ln behind layer 0), then the output layer as a plain GEMM
+//   ppo.head       the distribution, nlp_cur, r, the clipped surrogate's branch, d loss / d output
+//   actor.bwd<i>   dX from the output layer down (actor.ln.bwd behind layer 0's)
+//   actor.grad     every dW (+ the logstd / layer-norm column sums) stored, not applied (EPI_STORE)
+//   actor.gnorm    the gradient range's sum of squares by chunks
+//   ppo.final      means, the clip scale, alpha's step, the statistics row, the counters
+//   actor.adam     Keras Adam over the actor's parameter range at the device-read rate
+static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
+    auto it = h->ppo_plans.find(mb);
+    if (it != h->ppo_plans.end()) return it->second;
+    std::vector<Launch> plan;
+    const int cur = h->probs_cursor;
+    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, Aout = h->Aout, ldS = h->ldS;
+    const NetDims& na = h->nd[0];
+    const int Da = na.D();
+    auto W = [&](const std::string& n) { return h->f(n); };
+    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
+    auto ch = [&](const std::string& p, int i, int D) -> float* {     // as build_plan_generic's
+        if (i == 0) return W(p + "1");
+        if (i == D - 1) return W(p + "2");
+        return W(p + "m" + std::to_string(i));
+    };
+    PpoCtl* pctl = h->ptr<PpoCtl>("ppo.ctl");
+    PpoPar* par = h->ptr<PpoPar>("ppo.par");
+    float *X = W("ppo.X"), *O = W("ppo.O"), *D3 = W("ws.Da3"), *E = W("ws.E"), *acc = W("ppo.acc");
+    float* Ha_last = W("ws.Ha2");
+    {
+        Launch L{};
+        L.kind = Launch::PPOGATHER;
+        L.name = "ppo.gather";
+        PpoGatherArgs& g = L.pg;
+        g.s = W("ppo.s"); g.a = W("ppo.a"); g.adv = W("ppo.adv"); g.nlp_old = W("ppo.nlp_old");
+        g.idx_ring = h->ptr<int32_t>("ppo.idx"); g.idx_ld = h->B;
+        g.ctl = pctl; g.par = par;
+        g.s_mean = W("norm.s_mean"); g.s_den = W("norm.s_den");
+        g.S = S; g.A = A; g.mb = mb; g.ldS = ldS;
+        g.X = X; g.Arow = W("ppo.A"); g.advn = W("ppo.advn"); g.nlpo = W("ppo.nlpo"); g.acc = acc;
+        L.grid = (mb + PPO_GATHER_ROWS - 1) / PPO_GATHER_ROWS;
+        L.bytes = 4.0 * mb * (S + ldS + 2.0 * A + 4);
+        plan.push_back(L);
+    }
+    for (int i = 0; i < Da; ++i) {
+        const float* in = i == 0 ? X : ch("ws.Ha", i - 1, Da);
+        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
+        add_gemm(h, plan, "actor.fwd" + std::to_string(i),
+                 {prob_fwd(in, ldi, mb, K, W(L_("actor", i)), na.h[i], ch("ws.Ha", i, Da),
+                           (i == 0 && h->ln) ? ACT_NONE : na.act[i])}, false);
+        if (i == 0 && h->ln) {
+            Launch L{};
+            L.kind = Launch::LNORM;
+            L.name = "actor.ln";
+            LNArgs& a = L.ln;
+            a.mode = 0; a.H = H0; a.Z = W("ws.Ha1"); a.nrange = 1; a.r[0] = 0; a.r[1] = mb;
+            a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = mb;
+            L.grid = (mb + 3) / 4;
+            L.flops = 8.0 * mb * H0;
+            L.bytes = 4.0 * mb * H0 * 3;
+            plan.push_back(L);
+        }
+    }
+    add_gemm(h, plan, "actor.fwd" + std::to_string(Da),
+             {prob_fwd(Ha_last, H1, mb, H1, W(L_("actor", Da)), Aout, O, ACT_NONE)}, false);
+    PpoDist dist{};
+    dist.O = O; dist.A = A; dist.Aout = Aout; dist.per_state_std = h->cfg.per_state_std;
+    dist.logstd = W("actor.logstd");
+    {   // logstd_init (continuous_actors.py:39-44), f32, as sacx_actor_act's
+        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+        dist.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    }
+    {
+        Launch L{};
+        L.kind = Launch::PPOHEAD;
+        L.name = "ppo.head";
+        PpoHeadArgs& a = L.ph;
+        a.d = dist; a.mb = mb;
+        a.Arow = W("ppo.A"); a.advn = W("ppo.advn"); a.nlpo = W("ppo.nlpo");
+        a.alpha = W("ppo.alpha"); a.par = par;
+        a.D3 = D3; a.E = E; a.row_loss = W("ppo.rl"); a.row_ent = W("ppo.rl") + h->B;
+        L.grid = (mb + 3) / 4;
+        L.flops = 40.0 * mb * A;
+        L.bytes = 4.0 * mb * (2.0 * Aout + 2.0 * A + 4);
+        plan.push_back(L);
+    }
+    for (int i = Da; i >= 1; --i)
+        add_gemm(h, plan, "actor.bwd" + std::to_string(i),
+                 {prob_dx(i == Da ? D3 : ch("ws.Da", i, Da), mb, i == Da ? Aout : na.h[i], W(L_("actor", i)), na.h[i - 1],
+                          ch("ws.Ha", i - 1, Da), ch("ws.Da", i - 1, Da), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
+                 false);
+    if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
+        Launch N{};
+        N.kind = Launch::LNORM;
+        N.name = "actor.ln.bwd";
+        LNArgs& a = N.ln;
+        a.mode = 1; a.H = H0; a.Z = W("ws.Da1"); a.r[1] = mb; a.gamma = W("actor.ln");
+        a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = 0;
+        a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
+        N.grid = (mb + 3) / 4;
+        N.flops = 8.0 * mb * H0;
+        N.bytes = 4.0 * mb * H0 * 5;
+        plan.push_back(N);
+    }
+    {
+        std::vector<GemmProb> pw;
+        for (int i = 0; i < Da; ++i) {
+            const float* Xi = i == 0 ? X : ch("ws.Ha", i - 1, Da);
+            const int K = i == 0 ? S : na.h[i - 1];
+            pw.push_back(prob_dw(Xi, i == 0 ? ldS : K, K, mb, ch("ws.Da", i, Da), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
+        }
+        pw.push_back(prob_dw(Ha_last, H1, H1, mb, D3, Aout, W(L_("actor", Da)), nullptr, GRP_PI));
+        if (!h->cfg.per_state_std) {
+            GemmProb p = prob_dw(E, 1, 0, mb, E, A, W("actor.logstd"), nullptr, GRP_PI);
+            p.ones_row = 0;   // single all-ones row: column sums of E
+            pw.push_back(p);
+        }
+        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
+            for (int k = 0; k < 2; ++k) {
+                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
+                GemmProb p = prob_dw(gsrc, 1, 0, mb, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
+                p.ones_row = 0;
+                pw.push_back(p);
+            }
+        }
+        const int n_dw = add_gemm_split(h, plan, "actor.grad", pw, false);
+        for (int j = 0; j < n_dw; ++j) {       // store the gradients (+3 p_stride): the clip comes first
+            Launch& G = plan[plan.size() - 1 - j];
+            for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
+        }
+    }
+    // the actor's trainables are one contiguous parameter range: actor.l0 .. actor.logstd (with
+    // per_state_std the logstd variable is no trainable: its gradient stays 0 and Adam leaves it)
+    float* P = W("actor.l0");
+    const SegInfo& sl = h->seg("actor.logstd");
+    const int64_t n = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4);
+    {
+        Launch N{};
+        N.kind = Launch::GNPART;
+        N.name = "actor.gnorm";
+        N.gn.g = P + 3 * h->p_stride; N.gn.n = n; N.gn.part = W("ppo.gnorm");
+        N.grid = GNORM_PARTS;
+        N.bytes = 4.0 * n;
+        plan.push_back(N);
+    }
+    {
+        Launch L{};
+        L.kind = Launch::PPOFINAL;
+        L.name = "ppo.final";
+        PpoFinalArgs& a = L.pf;
+        a.mb = mb; a.row_loss = W("ppo.rl"); a.row_ent = W("ppo.rl") + h->B; a.gpart = W("ppo.gnorm");
+        a.par = par; a.ctl = pctl; a.alpha = W("ppo.alpha"); a.acc = acc;
+        a.stats = W("ppo.stats"); a.stats_cap = h->stats_cap;
+        L.grid = 1;
+        L.bytes = 4.0 * (2.0 * mb + GNORM_PARTS);
+        plan.push_back(L);
+    }
+    {
+        Launch U{};
+        U.kind = Launch::APPLY;
+        U.name = "actor.adam";
+        AdamApplyArgs& a = U.ap;
+        a.P = P; a.n = n; a.p_stride = h->p_stride; a.group = GRP_PI; a.t_off = 0;
+        a.grad_scale = 1.f; a.scale_dev = acc + PPO_ACC_SCALE;
+        a.ctl = h->ctl(); a.adam = adam_consts(h); a.t_adv = 1;       // ppo.final advanced t_pi
+        a.lr_dev = &par->actor_lr; a.t_dev = &pctl->t_pi;
+        U.grid = (int)((n + 255) / 256);
+        U.bytes = 4.0 * n * 7;
+        plan.push_back(U);
+    }
+    h->probs_cursor = cur;
+    return h->ppo_plans.emplace(mb, std::move(plan)).first->second;
+}
+
+static int ppo_check(sacx_handle* h) {
+    if (!h || !h->bound) return fail(h, "not bound");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no PPO actor update");
+    return 0;
+}
+
+// the actor on m <= ACT_CAP caller rows s: normalise, hidden layers, the output layer -> ppo.O [m, Aout]
+static PpoDist ppo_forward(sacx_handle* h, const float* s, int m) {
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    launch_obs_norm(s, m, h->S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), h->ldS, h->stream);
+    const float* Hl = actor_hidden(h, W("act.X"), h->ldS, m, W("act.H1"), W("act.H2"), h->stream);
+    std::vector<Launch> pl;
+    add_gemm(h, pl, "actor.out", {prob_fwd(Hl, h->H1, m, h->H1, W(actor_head_name(h)), h->Aout, W("ppo.O"), ACT_NONE)}, false);
+    h->probs_cursor -= 1;
+    launch_gemm(pl[0].gemm, h->stream);
+    PpoDist d{};
+    d.O = W("ppo.O"); d.A = h->A; d.Aout = h->Aout; d.per_state_std = h->cfg.per_state_std;
+    d.logstd = W("actor.logstd");
+    const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+    d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    return d;
+}
+
+// the whole-rollout passes: n rows of s through the actor in chunks, k_ppo_rows on each; the
+// prototype's row pointers are those of row 0 and move with the chunk
+static int ppo_rows_pass(sacx_handle* h, const float* s, int64_t n, const PpoRowsArgs& proto) {
+    const int S = h->S, A = h->A;
+    for (int64_t done = 0; done < n; done += ACT_CAP) {
+        const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
+        PpoRowsArgs r = proto;
+        r.d = ppo_forward(h, s + done * S, m);
+        r.m = m;
+        auto mv = [&](auto*& p, int64_t w) { if (p) p += done * w; };
+        mv(r.a, A); mv(r.nlp_old, 1); mv(r.mean_ref, A); mv(r.ls_ref, A);
+        mv(r.nlp_out, 1); mv(r.mean_out, A); mv(r.ls_out, A); mv(r.ent_out, 1); mv(r.kl_out, 1); mv(r.rdiff_out, 1);
+        launch_ppo_rows(r, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int sacx_ppo_neglogp(sacx_handle* h, const float* s, const float* a, int64_t n, float* nlp_out) {
+    if (ppo_check(h)) return -1;
+    if (n < 0 || (n > 0 && (!s || !a || !nlp_out))) return fail(h, "bad arguments");
+    PpoRowsArgs r{};
+    r.a = a; r.nlp_out = nlp_out;
+    return ppo_rows_pass(h, s, n, r);
+}
+
+int sacx_ppo_dist(sacx_handle* h, const float* s, int64_t n, float* mean_out, float* logstd_out, float* ent_out) {
+    if (ppo_check(h)) return -1;
+    if (n < 0 || (n > 0 && !s)) return fail(h, "bad arguments");
+    PpoRowsArgs r{};
+    r.mean_out = mean_out; r.ls_out = logstd_out; r.ent_out = ent_out;
+    return ppo_rows_pass(h, s, n, r);
+}
+
+int sacx_ppo_kl(sacx_handle* h, const float* s, const float* mean_ref, const float* logstd_ref, int64_t n,
+                float* kl_out) {
+    if (ppo_check(h)) return -1;
+    if (n < 0 || (n > 0 && (!s || !mean_ref || !logstd_ref || !kl_out))) return fail(h, "bad arguments");
+    PpoRowsArgs r{};
+    r.mean_ref = mean_ref; r.ls_ref = logstd_ref; r.kl_out = kl_out;
+    return ppo_rows_pass(h, s, n, r);
+}
+
+int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* adv, int64_t n) {
+    if (ppo_check(h)) return -1;
+    if (!s || !a || !adv) return fail(h, "null rollout pointer");
+    if (n < 1 || n > h->cap)
+        return fail(h, "rollout rows " + std::to_string(n) + " outside [1, buffer_capacity = " + std::to_string(h->cap) + "]");
+    const int S = h->S, A = h->A;
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    HIPCHK(h, hipMemcpyAsync(W("ppo.s"), s, sizeof(float) * (size_t)n * S, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(W("ppo.a"), a, sizeof(float) * (size_t)n * A, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(W("ppo.adv"), adv, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+    launch_ppo_set(nullptr, PpoPar{}, h->ptr<PpoCtl>("ppo.ctl"), W("ppo.acc"), n, h->stream);
+    {   // the gradient words of the actor's parameter range: the norm and Adam read all of it, the dW
+        // launches write the weights' words only (not the padding between segments, nor logstd's with
+        // per_state_std), so the rest must hold 0 whatever the caller's arena held before
+        const SegInfo& sl = h->seg("actor.logstd");
+        const size_t nb = (size_t)(sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0"));
+        HIPCHK(h, hipMemsetAsync(W("actor.l0") + 3 * h->p_stride, 0, nb, h->stream));
+    }
+    PpoRowsArgs r{};                  // neglogp_old, kl_info_ref, the entropy rows (ppo.py:44-46)
+    r.a = W("ppo.a"); r.nlp_out = W("ppo.nlp_old"); r.mean_out = W("ppo.mean_ref"); r.ls_out = W("ppo.ls_ref");
+    r.ent_out = W("ppo.tmp");
+    if (ppo_rows_pass(h, W("ppo.s"), n, r)) return -1;
+    PpoReduceArgs q{};
+    q.c[0] = W("ppo.tmp"); q.out[0] = W("ppo.log"); q.n = n; q.half0 = 1.f;
+    launch_ppo_reduce(q, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->ppo_rows = n;
+    return 0;
+}
+
+int sacx_ppo_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const sacx_ppo_params* params,
+                   int32_t flags) {
+    if (ppo_check(h)) return -1;
+    if (n_steps <= 0) return 0;
+    if (!idx || !params) return fail(h, "null index array or parameters");
+    if (h->ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
+    if (mb < 1 || mb > h->B)
+        return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
+    for (int64_t i = 0; i < n_steps * (int64_t)mb; ++i)
+        if (idx[i] < 0 || idx[i] >= h->ppo_rows) return fail(h, "minibatch index outside the rollout table");
+    if (!(params->eps_ppo >= 0.f) || !(params->actor_lr >= 0.f) || !(params->alpha_lr >= 0.f))
+        return fail(h, "eps_ppo, actor_lr and alpha_lr must be non-negative");
+    const std::vector<Launch>& plan = build_ppo_plan(h, mb);
+    PpoPar par{};
+    par.clip_lo = (float)(1.0 - (double)params->eps_ppo);
+    par.clip_hi = (float)(1.0 + (double)params->eps_ppo);
+    par.max_grad_norm = params->max_grad_norm;
+    par.ent_targ = params->ent_targ; par.alpha_lr = params->alpha_lr; par.actor_lr = params->actor_lr;
+    par.ent_reg = params->ent_reg != 0; par.adv_center = params->adv_center != 0; par.adv_scale = params->adv_scale != 0;
+    launch_ppo_set(h->ptr<PpoPar>("ppo.par"), par, h->ptr<PpoCtl>("ppo.ctl"), h->f("ppo.acc"), -1, h->stream);
+    int32_t* ring = h->ptr<int32_t>("ppo.idx");
+    const int B = h->B;
+    // each step reads its minibatch from the index ring at PpoCtl::seq, so a graph of several steps
+    // replays them back to back (the capture discipline of sacx_model_fit)
+    auto graph_of = [&](int n, hipGraphExec_t* out) -> int {
+        auto it = h->ppo_graphs.find({mb, n});
+        if (it != h->ppo_graphs.end()) {
+            *out = it->second;
+            return 0;
+        }
+        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+        for (int j = 0; j < n; ++j)
+            for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
+        const hipError_t le = hipGetLastError();
+        hipGraph_t graph = nullptr;
+        const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
+        if (le != hipSuccess || ee != hipSuccess) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return fail(h, std::string("PPO step graph capture: ") + hipGetErrorString(le != hipSuccess ? le : ee));
+        }
+        hipGraphExec_t ex = nullptr;
+        const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) return fail(h, std::string("PPO step graph instantiate: ") + hipGetErrorString(ie));
+        h->ppo_graphs[{mb, n}] = ex;
+        *out = ex;
+        return 0;
+    };
+    // ppo_seq_host mirrors PpoCtl::seq: it advances with every step handed to the stream, so a failure
+    // midway leaves the two in step
+    for (int64_t done = 0; done < n_steps;) {
+        const int64_t chunk = std::min<int64_t>(n_steps - done, PPO_IDX_CAP);
+        HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
+        const int64_t s0 = h->ppo_seq_host % PPO_IDX_CAP;
+        const int64_t first = std::min<int64_t>(chunk, PPO_IDX_CAP - s0);
+        HIPCHK(h, hipMemcpy2D(ring + s0 * B, sizeof(int32_t) * B, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
+                              (size_t)first, hipMemcpyHostToDevice));
+        if (chunk > first)
+            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * B, idx + (done + first) * mb, sizeof(int32_t) * mb,
+                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
+        if (flags & SACX_STEP_EAGER) {
+            for (int64_t j = 0; j < chunk; ++j)
+                for (const Launch& L : plan) enqueue(L, h, h->stream);
+            h->ppo_seq_host += chunk;
+            HIPCHK(h, hipGetLastError());
+        } else {
+            for (int64_t j = 0; j < chunk;) {
+                const int n = chunk - j >= 64 ? 64 : chunk - j >= 8 ? 8 : 1;
+                hipGraphExec_t ex = nullptr;
+                if (graph_of(n, &ex)) return -1;
+                HIPCHK(h, hipGraphLaunch(ex, h->stream));
+                h->ppo_seq_host += n;
+                j += n;
+            }
+        }
+        done += chunk;
+    }
+    return 0;
+}
+
+int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out) {
+    if (ppo_check(h)) return -1;
+    if (!out) return fail(h, "null output");
+    if (h->ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    const int64_t n = h->ppo_rows;
+    PpoRowsArgs r{};                  // neglogp_cur over all rows -> |r - 1|; kl against the reference (ppo.py:91-95)
+    r.a = W("ppo.a"); r.nlp_old = W("ppo.nlp_old"); r.rdiff_out = W("ppo.tmp");
+    r.mean_ref = W("ppo.mean_ref"); r.ls_ref = W("ppo.ls_ref"); r.kl_out = W("ppo.tmp") + h->cap;
+    if (ppo_rows_pass(h, W("ppo.s"), n, r)) return -1;
+    float* lg = W("ppo.log");
+    PpoReduceArgs q{};
+    q.c[0] = W("ppo.tmp"); q.out[0] = lg + 1; q.half0 = 0.5f;          // tv
+    q.c[1] = W("ppo.tmp") + h->cap; q.out[1] = lg + 2;                 // kl
+    q.c[2] = W("ppo.tmp"); q.out[2] = lg + 3; q.count2 = 1; q.thr = eps_ppo;   // outside_clip
+    q.n = n;
+    launch_ppo_reduce(q, h->stream);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float lh[8], ah[8], al[3];
+    PpoCtl pc{};
+    HIPCHK(h, hipMemcpy(lh, lg, sizeof(lh), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(ah, W("ppo.acc"), sizeof(ah), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(al, W("ppo.alpha"), sizeof(al), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&pc, h->ptr<PpoCtl>("ppo.ctl"), sizeof(pc), hipMemcpyDeviceToHost));
+    out[0] = lh[0]; out[1] = lh[1]; out[2] = lh[2];
+    out[3] = (double)lh[3] / (double)n;      // np.mean of booleans (ppo.py:103): the count over n in f64
+    // ppo.py:86-89: the f32 sums over the steps divided by their count
+    out[4] = pc.n_steps > 0 ? (double)(float)((double)ah[PPO_ACC_PRE] / (double)pc.n_steps) : 0.0;
+    out[5] = pc.n_steps > 0 ? (double)(float)((double)ah[PPO_ACC_POST] / (double)pc.n_steps) : 0.0;
+    out[6] = al[0];
+    out[7] = (double)pc.n_steps;
+    return 0;
+}
+
+int sacx_ppo_plan_info(sacx_handle* h, int32_t mb, sacx_launch_info* out, int32_t cap, int32_t* n_out) {
+    if (ppo_check(h)) return -1;
+    if (!n_out) return fail(h, "null output");
+    if (mb < 1 || mb > h->B) return fail(h, "minibatch rows outside [1, batch]");
+    return launch_info(build_ppo_plan(h, mb), out, cap, n_out);
 }
 
 }  // extern "C"

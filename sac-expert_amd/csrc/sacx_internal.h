@@ -657,6 +657,13 @@ struct AdamApplyArgs {
     const Ctl* ctl;
     AdamConsts adam;
     int32_t t_adv;              // as GemmArgs::t_adv
+    // the PPO actor step (nullable, both or neither; scale_dev then set): the learning rate and the
+    // optimiser's iteration count read from the device -- ppo.py:109-117 changes the rate between
+    // update() calls, so it is no constant of a captured graph -- in place of adam.lr[group] and ctl's
+    // counter.  launch_adam_apply then launches k_ppo_adam (the same arithmetic), and k_adam_apply
+    // stays the code it was for every other plan
+    const float* lr_dev;
+    const int64_t* t_dev;
 };
 
 // In-process data-parallel reduce (sacx_dp_local_step): buf[r][i] = sum over r' of buf[r'][i], in
@@ -762,7 +769,116 @@ struct ActRowArgs {
     uint32_t* done;
 };
 
+// ---------------------------------------------------------------- PPO actor update
+// The on-policy actor step of a trainable GaussianActor handle (actor_gaussian =
+// SACX_ACTOR_GAUSSIAN_TRAIN; ppo.py:41-147, :225-239, continuous_actors.py:74-192).
+// Segment "ppo.par": the step's run-time parameters, written by the host at each sacx_ppo_steps call
+// (never constants of a captured graph: actor_lr changes between update() calls, ppo.py:109-117)
+struct PpoPar {
+    float clip_lo, clip_hi;     // f32(1 - eps_ppo), f32(1 + eps_ppo)
+    float max_grad_norm;        // <= 0: None
+    float ent_targ, alpha_lr, actor_lr;
+    int32_t ent_reg, adv_center, adv_scale;
+    int32_t pad[7];
+};
+// Segment "ppo.ctl" (int64 x 8)
+struct PpoCtl {
+    int64_t seq;                // minibatch steps run (index / statistics ring position)
+    int64_t t_pi;               // iterations of the actor's Adam
+    int64_t t_alpha;            // iterations of alpha's Adam
+    int64_t n_steps;            // steps since sacx_ppo_begin
+    int64_t n_rows;             // rows of the rollout table (sacx_ppo_begin)
+    int64_t pad[3];
+};
+// Segment "ppo.acc" (float x 8): [0] sum of grad_norm_pre, [1] of grad_norm_post since begin
+// (ppo.py:83-84: f32 sums in step order), [2] this step's clip scale, [3] / [4] the minibatch's
+// advantage mean and std + 1e-8
+enum { PPO_ACC_PRE = 0, PPO_ACC_POST = 1, PPO_ACC_SCALE = 2, PPO_ACC_AMEAN = 3, PPO_ACC_ASTD = 4 };
+// Statistics row per step (float x 8, ring "ppo.stats")
+enum { PPO_STAT_LOSS = 0, PPO_STAT_ENT, PPO_STAT_GN_PRE, PPO_STAT_GN_POST, PPO_STAT_ALPHA, PPO_STAT_PG,
+       PPO_STAT_ADV_STD, PPO_STAT_STEP };
+// Segment "ppo.log" (float x 8): [0] mean entropy over the rollout (begin); [1] tv, [2] kl,
+// [3] the rows with |r - 1| > eps (end)
+#define PPO_IDX_CAP 1024            // minibatch steps the index ring holds
+#define PPO_GATHER_ROWS 64          // rows per workgroup of k_ppo_gather
+
+// k_ppo_gather: the step's minibatch rows by index from the rollout table -> the plan's row buffers,
+// and the minibatch advantage statistics (ppo.py:66-77), one launch: every workgroup sums the mb
+// advantages itself (the same order, the same value), then writes its own rows
+struct PpoGatherArgs {
+    const float *s, *a, *adv, *nlp_old;     // the table: [n, S], [n, A], [n], [n], n = ctl->n_rows (indices clamped)
+    const int32_t* idx_ring; int32_t idx_ld;    // [PPO_IDX_CAP, idx_ld]
+    const PpoCtl* ctl;
+    const PpoPar* par;
+    const float *s_mean, *s_den;
+    int32_t S, A, mb, ldS;
+    float* X;                   // [mb, ldS] normalised states (pad columns 0)
+    float* Arow;                // [mb, A]
+    float* advn;                // [mb] centred / scaled advantages
+    float* nlpo;                // [mb]
+    float* acc;                 // ppo.acc
+};
+
+// the distribution of continuous_actors.py:74-100 from the actor's output rows O [rows, Aout]
+struct PpoDist {
+    const float* O; int32_t A, Aout, per_state_std;
+    const float* logstd;        // [A] (state-independent std)
+    float logstd_init;          // log(std_mult) (- log(log 2) with per_state_std)
+};
+
+// k_ppo_head: one wave per minibatch row -- ls, nlp_cur, r, the branch of the clipped surrogate,
+// the row's loss and entropy, d loss / d mean and d loss / d (raw | logstd)
+struct PpoHeadArgs {
+    PpoDist d;
+    int32_t mb;
+    const float *Arow, *advn, *nlpo;
+    const float* alpha;         // ppo.alpha[0] (the value before this step's alpha update)
+    const PpoPar* par;
+    float* D3;                  // [mb, Aout] d loss / d O
+    float* E;                   // [mb, A] d loss / d logstd per row (state-independent std; its column sums)
+    float* row_loss; float* row_ent;    // [mb]
+};
+
+// k_ppo_final: one workgroup -- loss and entropy means, the global norm and the clip scale
+// (k_gnorm_final's arithmetic), alpha's Keras Adam + max(alpha, 0), the statistics row, counters
+struct PpoFinalArgs {
+    int32_t mb;
+    const float *row_loss, *row_ent;
+    const float* gpart;         // [GNORM_PARTS] from k_gnorm_part
+    const PpoPar* par;
+    PpoCtl* ctl;
+    float* alpha;               // [3] alpha, m, v
+    float* acc;
+    float* stats; int32_t stats_cap;
+};
+
+// k_ppo_rows: the whole-rollout passes over a chunk of rows (neglogp / (mean, ls) / entropy / kl /
+// |r - 1|), each output nullable
+struct PpoRowsArgs {
+    PpoDist d;
+    int32_t m;
+    const float* a;             // [m, A] (nlp)
+    const float* nlp_old;       // [m] (rdiff)
+    const float *mean_ref, *ls_ref;   // [m, A] (kl)
+    float *nlp_out, *mean_out, *ls_out, *ent_out, *kl_out, *rdiff_out;
+};
+// k_ppo_reduce: one workgroup -- means over n rows of up to three columns; c[2], with count2, is
+// counted (> thr) instead of averaged (out[2] = the count)
+struct PpoReduceArgs {
+    const float* c[3]; float* out[3];
+    int64_t n; float thr; int32_t count2;
+    float half0;                // out[0] scaled by this (tv = 0.5 mean |r - 1|)
+};
+
 // launchers (defined in k_sac.hip)
+void launch_ppo_gather(const PpoGatherArgs& a, hipStream_t s);
+void launch_ppo_head(const PpoHeadArgs& a, hipStream_t s);
+void launch_ppo_final(const PpoFinalArgs& a, hipStream_t s);
+void launch_ppo_rows(const PpoRowsArgs& a, hipStream_t s);
+void launch_ppo_reduce(const PpoReduceArgs& a, hipStream_t s);
+// dst != null: *dst = v (the step parameters); n >= 0: a new table of n rows, accumulators reset
+void launch_ppo_set(PpoPar* dst, const PpoPar& v, PpoCtl* ctl, float* acc, int64_t n, hipStream_t s);
+void launch_gnorm_part(const GNormArgs& a, hipStream_t s);
 void launch_act_rows(const ActRowArgs& a, int m, hipStream_t s);
 // rows + the sampler draw beside them (+ a deferred 1-row append as one more workgroup when app is set)
 void launch_act_rng(const ActRowArgs& a, int m, const RngArgs& r, hipStream_t s, const AppendArgs* app = nullptr, bool polar = true);

@@ -19,6 +19,8 @@ STAGE_FLOATS = 65536            # SACX_STAGE_FLOATS (include/sacx.h)
 ACT = {"relu": 0, "tanh": 1, "elu": 2}
 DTYPES = {0: "f32", 1: "i32", 2: "i64", 3: "u32", 4: "f64"}
 EXPERT_OFF, EXPERT_EO, EXPERT_BC = 0, 1, 2      # sacx_config.use_expert (SACX_EXPERT_*)
+ACTOR_SQUASHED, ACTOR_GAUSSIAN, ACTOR_GAUSSIAN_TRAIN = 0, 1, 2     # sacx_config.actor_gaussian (SACX_ACTOR_*)
+PPO_STAT_NAMES = ["loss", "ent", "grad_norm_pre", "grad_norm_post", "alpha", "pg_loss", "adv_std", "step"]
 STEP_EXTERNAL_RANDOMS = 1
 STEP_EAGER = 2
 ROLE_WORK, ROLE_PARAM, ROLE_TARGET, ROLE_STATE = 0, 1, 2, 3
@@ -36,6 +38,8 @@ EXPORTS = [
     "sacx_dp_unique_id", "sacx_dp_init", "sacx_dp_init_local", "sacx_dp_local_step", "sacx_expert_diag", "sacx_resync", "sacx_seed_stride",
     "sacx_seed_select", "sacx_prepare", "sacx_actor_evaluate", "sacx_critic_forward", "sacx_model_forward",
     "sacx_model_loss", "sacx_spec_hits", "sacx_settle", "sacx_model_sample",
+    "sacx_ppo_neglogp", "sacx_ppo_dist", "sacx_ppo_kl", "sacx_ppo_begin", "sacx_ppo_steps", "sacx_ppo_end",
+    "sacx_ppo_plan_info",
 ]
 
 
@@ -95,6 +99,20 @@ class Config(ctypes.Structure):
         ("net_depth", ctypes.c_int32 * 4),
         ("net_hidden", (ctypes.c_int32 * 4) * 4),
         ("net_acts", (ctypes.c_int32 * 4) * 4),
+    ]
+
+
+class PpoParams(ctypes.Structure):
+    """sacx_ppo_params: the run-time inputs of the PPO minibatch steps (ppo.py:13-39)."""
+    _fields_ = [
+        ("eps_ppo", ctypes.c_float),
+        ("max_grad_norm", ctypes.c_float),      # <= 0: None
+        ("ent_targ", ctypes.c_float),
+        ("alpha_lr", ctypes.c_float),
+        ("actor_lr", ctypes.c_float),
+        ("ent_reg", ctypes.c_int32),
+        ("adv_center", ctypes.c_int32),
+        ("adv_scale", ctypes.c_int32),
     ]
 
 
@@ -178,6 +196,13 @@ def lib():
         "sacx_dp_init_local": (ctypes.c_int, [vp, i32, i32]),
         "sacx_dp_local_step": (ctypes.c_int, [vp, i32, i64, i64, i32]),
         "sacx_rollout": (ctypes.c_int, [vp, i32, vp, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+        "sacx_ppo_neglogp": (ctypes.c_int, [vp, vp, vp, i64, vp]),
+        "sacx_ppo_dist": (ctypes.c_int, [vp, vp, i64, vp, vp, vp]),
+        "sacx_ppo_kl": (ctypes.c_int, [vp, vp, vp, vp, i64, vp]),
+        "sacx_ppo_begin": (ctypes.c_int, [vp, vp, vp, vp, i64]),
+        "sacx_ppo_steps": (ctypes.c_int, [vp, vp, i64, i32, P(PpoParams), i32]),
+        "sacx_ppo_end": (ctypes.c_int, [vp, f32, P(f64)]),
+        "sacx_ppo_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -99,6 +99,45 @@ class GaussianActor:
         out = self._engine.act(np.asarray(s, np.float32), deterministic=deterministic)
         return _as_out(out.cpu().numpy())
 
+    # ------------------------------------------------------------------ the on-policy distribution calls
+    # (continuous_actors.py:132-192; on the GPU through a trainable engine,
+    # EngineConfig(actor_gaussian="train") -- sac_eo.algs.model_free.PPO builds one)
+    def _ppo_engine(self):
+        if self._engine is None:
+            raise RuntimeError("actor is not bound to a device engine (build the algorithm first)")
+        if not getattr(self._engine.cfg, "trainable_gaussian", False):
+            raise RuntimeError("neglogp / entropy / kl / get_kl_info need a trainable GaussianActor engine "
+                               "(EngineConfig(actor_gaussian='train'))")
+        return self._engine
+
+    def neglogp(self, s, a):
+        """0.5 sum_j (((a - mean) / e^ls)^2 + 2 ls + log 2 pi) per row (:132-138); one row gives a scalar."""
+        eng = self._ppo_engine()
+        out = eng.neglogp(np.asarray(s, np.float32).reshape(-1, self.s_dim),
+                          np.asarray(a, np.float32).reshape(-1, self.a_dim)).cpu().numpy()
+        return _as_out(out[0] if out.shape[0] == 1 else out)       # tf.squeeze
+
+    def entropy(self, s):
+        """0.5 sum_j (2 ls + log 2 pi + 1) per row (:140-143)."""
+        return _as_out(self._ppo_engine().dist(np.asarray(s, np.float32).reshape(-1, self.s_dim))[2].cpu().numpy())
+
+    def get_kl_info(self, s):
+        """np.stack((mean, logstd), axis=-1) of _forward (:186-192): [n, A, 2]."""
+        mean, ls, _ = self._ppo_engine().dist(np.asarray(s, np.float32).reshape(-1, self.s_dim))
+        return np.stack((mean.cpu().numpy(), ls.cpu().numpy()), axis=-1)
+
+    def kl(self, s, kl_info_ref, direction="forward"):
+        """KL(reference || current) per row (:159-184, the forward direction).  The reference's
+        'reverse' branch reads the state-independent ``self.logstd`` without its init and floor and
+        is never called by PPO: not built."""
+        if direction != "forward":
+            raise NotImplementedError("GaussianActor.kl: only direction='forward' runs on the device")
+        eng = self._ppo_engine()
+        mean_ref, ls_ref = np.moveaxis(np.asarray(kl_info_ref, np.float32), -1, 0)
+        out = eng.kl(np.asarray(s, np.float32).reshape(-1, self.s_dim), np.ascontiguousarray(mean_ref),
+                     np.ascontiguousarray(ls_ref))
+        return _as_out(out.cpu().numpy())
+
     def clip(self, a):
         # np.clip (continuous_actors.py's tf.clip_by_value on host arrays); minimum / maximum
         # give the same values without np.clip's per-call dispatch cost in the env loop
@@ -110,6 +149,14 @@ class GaussianActor:
 
 class SquashedGaussianActor(GaussianActor):
     squash = True
+
+    # the squashed actor's neglogp differs (continuous_actors.py:313-325: the tanh correction) and
+    # no device path computes it or its companions: they do not fall through to GaussianActor's
+    def _no_onpolicy(self, *a, **kw):
+        raise NotImplementedError("SquashedGaussianActor: neglogp / entropy / kl / get_kl_info are not built "
+                                  "(the on-policy PPO update trains the plain GaussianActor)")
+
+    neglogp = entropy = kl = get_kl_info = _no_onpolicy
 
     def evaluate(self, s):
         """(pi_action, neglogp_adjusted) of continuous_actors.py:327-379 on the GPU

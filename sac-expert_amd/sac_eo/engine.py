@@ -59,7 +59,11 @@ class EngineConfig:
     gemm_bf16: bool = False     # config C5: bf16 MFMA operands, fp32 accumulate / master weights
     seeds: int = 1              # independent learners packed in one handle (one launch chain for all)
     single_seed_plan: bool = False  # packed seeds run the one-seed plan: each seed bit-identical to its own run
-    actor_gaussian: bool = False    # GaussianActor (no squash): inference only (an imported expert)
+    # GaussianActor (no squash).  True: inference only (an imported expert).  "train": the actor
+    # the PPO update trains on-policy (sac_eo.algs.model_free.PPO; Engine.ppo_* / neglogp / dist / kl):
+    # fp32, one seed, no expert path, no data-parallel ranks, no actor_output_norm; buffer_capacity
+    # bounds the rollout rows of an update and batch its minibatch rows
+    actor_gaussian: object = False
     actor_std_mult: float = 1.0
     actor_output_norm: bool = False
     actor_layer_norm: bool = False  # Dense -> LayerNorm -> tanh on the actor's layer 0
@@ -89,6 +93,10 @@ class EngineConfig:
     def __post_init__(self):
         if self.bc:
             self.use_expert = True
+
+    @property
+    def trainable_gaussian(self) -> bool:
+        return isinstance(self.actor_gaussian, str) and self.actor_gaussian == "train"
 
     @staticmethod
     def _acts(lst, dflt: str, depth: int, what: str) -> List[str]:
@@ -153,7 +161,17 @@ class EngineConfig:
         c.gemm_bf16 = int(bool(self.gemm_bf16))
         c.seeds = int(self.seeds)
         c.single_seed_plan = int(bool(self.single_seed_plan))
-        c.actor_gaussian = int(bool(self.actor_gaussian))
+        if isinstance(self.actor_gaussian, str) and self.actor_gaussian != "train":
+            raise ValueError("actor_gaussian must be False, True (inference only) or 'train'")
+        if self.trainable_gaussian:
+            for bad, why in ((self.actor_output_norm, "actor_output_norm has no backward"),
+                             (self.gemm_bf16, "gemm_bf16 (fp32 only)"), (int(self.seeds) > 1, "seeds > 1"),
+                             (self.use_expert, "use_expert / bc (the expert_reg branch of the PPO step is not built)")):
+                if bad:
+                    raise ValueError(f"actor_gaussian='train' (the PPO-trained GaussianActor) does not run with {why}")
+            c.actor_gaussian = N.ACTOR_GAUSSIAN_TRAIN
+        else:
+            c.actor_gaussian = int(bool(self.actor_gaussian))
         c.actor_std_mult = float(self.actor_std_mult)
         c.actor_output_norm = int(bool(self.actor_output_norm))
         c.actor_layer_norm = int(bool(self.actor_layer_norm))
@@ -524,6 +542,106 @@ class Engine:
         N.check(self.lib.sacx_actor_evaluate(self.h, p(x), n, p(pi), p(nlp)), self.h, "actor_evaluate")
         self._keep_eval = x
         return pi, nlp
+
+    # ------------------------------------------------------------------ PPO actor update
+    # (EngineConfig(actor_gaussian="train"); every call fails with a message on any other engine)
+    def neglogp(self, s, a) -> "torch.Tensor":
+        """GaussianActor.neglogp (continuous_actors.py:132-138): s [n, S], a [n, A] -> [n] (CUDA)."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        n = int(x.shape[0])
+        if int(u.shape[0]) != n:
+            raise ValueError("s and a need the same number of rows")
+        out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_ppo_neglogp(self.h, p(x), p(u), n, p(out)), self.h, "ppo_neglogp")
+        self._keep_ppo = (x, u)
+        return out
+
+    def dist(self, s):
+        """GaussianActor._forward and entropy (continuous_actors.py:74-100, :140-143):
+        s [n, S] -> (mean [n, A], logstd [n, A], entropy [n]) CUDA tensors."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x = self._dev(s, (-1, S))
+        n = int(x.shape[0])
+        kw = dict(dtype=torch.float32, device=self.device)
+        mean, ls, ent = torch.empty((n, A), **kw), torch.empty((n, A), **kw), torch.empty((n,), **kw)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_ppo_dist(self.h, p(x), n, p(mean), p(ls), p(ent)), self.h, "ppo_dist")
+        self._keep_ppo = (x,)
+        return mean, ls, ent
+
+    def kl(self, s, mean_ref, logstd_ref) -> "torch.Tensor":
+        """GaussianActor.kl(direction='forward') (continuous_actors.py:159-184) -> [n] (CUDA)."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x = self._dev(s, (-1, S))
+        n = int(x.shape[0])
+        mr, lr = self._dev(mean_ref, (n, A)), self._dev(logstd_ref, (n, A))
+        out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_ppo_kl(self.h, p(x), p(mr), p(lr), n, p(out)), self.h, "ppo_kl")
+        self._keep_ppo = (x, mr, lr)
+        return out
+
+    def ppo_begin(self, s, a, adv) -> int:
+        """The head of PPO.update (ppo.py:43-46): the rollout (s [n, S], a [n, A], adv [n]) becomes
+        the table the steps gather from; neglogp_old, kl_info_ref and the mean entropy are computed
+        with the weights as they stand.  Returns n."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        n = int(x.shape[0])
+        w = self._dev(adv, (-1,))
+        if int(u.shape[0]) != n or int(w.shape[0]) != n:
+            raise ValueError("s, a and adv need the same number of rows")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_ppo_begin(self.h, p(x), p(u), p(w), n), self.h, "ppo_begin")
+        self._keep_ppo = (x, u, w)
+        return n
+
+    def ppo_steps(self, idx: np.ndarray, *, eps_ppo: float, actor_lr: float, max_grad_norm=None, ent_targ: float = 0.0,
+                  ent_reg: bool = False, alpha_lr: float = 0.0, adv_center: bool = True, adv_scale: bool = True,
+                  eager: bool = False):
+        """``idx[n_steps, mb]`` (table rows): n_steps x PPO._apply_actor_grad (ppo.py:122-147,
+        :225-239) with no host synchronisation between them.  ``actor_lr`` is the current rate of the
+        actor's Adam (a run-time input: the adaptlr rule changes it between updates)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.ndim != 2:
+            raise ValueError("idx must be [n_steps, mb]")
+        par = N.PpoParams(eps_ppo=float(eps_ppo), max_grad_norm=float(max_grad_norm or 0.0), ent_targ=float(ent_targ),
+                          alpha_lr=float(alpha_lr), actor_lr=float(actor_lr), ent_reg=int(bool(ent_reg)),
+                          adv_center=int(bool(adv_center)), adv_scale=int(bool(adv_scale)))
+        N.check(self.lib.sacx_ppo_steps(self.h, idx.ctypes.data, int(idx.shape[0]), int(idx.shape[1]), ctypes.byref(par),
+                                        N.STEP_EAGER if eager else 0), self.h, "ppo_steps")
+
+    def ppo_end(self, eps_ppo: float) -> dict:
+        """The tail of PPO.update (ppo.py:86-106) over the table's rows: ent, tv, kl, outside_clip,
+        the two grad norms averaged over the steps since ppo_begin, alpha, the step count."""
+        out = (ctypes.c_double * 8)()
+        N.check(self.lib.sacx_ppo_end(self.h, float(eps_ppo), out), self.h, "ppo_end")
+        keys = ("ent", "tv", "kl", "outside_clip", "actor_grad_norm_pre", "actor_grad_norm", "alpha")
+        d = {k: np.float32(out[i]) for i, k in enumerate(keys)}
+        d["outside_clip"] = np.float64(out[3])           # np.mean of booleans: f64
+        d["n_steps"] = int(out[7])
+        return d
+
+    def ppo_stats(self, n_last: int) -> np.ndarray:
+        """Last n_last rows of the PPO step statistics ring (_native.PPO_STAT_NAMES), oldest first."""
+        seq = int(self.v["ppo.ctl"][0, 0].item())
+        cap = self.cfg.stats_capacity
+        st = self.v["ppo.stats"].cpu().numpy()
+        return st[[(seq - n_last + i) % cap for i in range(n_last)]]
+
+    def ppo_alpha(self) -> float:
+        return float(self.v["ppo.alpha"][0, 0].item())
+
+    def ppo_plan_info(self, mb: int) -> List[dict]:
+        """The launches of one PPO minibatch step of mb rows."""
+        n = ctypes.c_int32()
+        N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), None, 0, ctypes.byref(n)), self.h, "ppo_plan_info")
+        arr = (N.LaunchInfo * n.value)()
+        N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), arr, n.value, ctypes.byref(n)), self.h, "ppo_plan_info")
+        return [dict(name=a.name.decode(), kernel=a.kernel.decode(), grid=a.grid, block=a.block,
+                     flops=a.flops, bytes=a.bytes) for a in arr]
 
     def critic_forward(self, net: str, s, a, value: bool = False):
         """QCritic._forward (value=False: [n, 1]) / value (value=True: [n], x ret sigma)
