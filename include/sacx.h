@@ -404,6 +404,65 @@ int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out);
 /* The launches of one minibatch step of mb rows, as sacx_plan_info. */
 int sacx_ppo_plan_info(sacx_handle* h, int32_t mb, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
 
+/* --- VCritics beside the trainable GaussianActor: value, GAE and the critic update ----------------
+ * The critic side of MBRLOnPolicyAlg._update_actor_critic (buffer.get_update_info -> _update_critics;
+ * _update_actor is the sacx_ppo_* calls above).  SACX_ACTOR_GAUSSIAN_TRAIN handles only; every call
+ * fails with a message elsewhere, and (but for sacx_vcritic_init) on a handle without critics.
+ * Device rows in, device rows out, asynchronous on the bound stream unless stated; whole-table
+ * passes go through a critic in chunks of 1024 rows. */
+/* Gives the handle n_critics VCritics (1 .. SACX_MAX_MODELS: num_models under --critic_ensemble, else
+ * 1, init_critic.py:10): nets [S] -> the critic layers -> 1 with the handle's critic description
+ * (critic_hidden / net_depth[1] / net_hidden[1] / net_acts[1]).  After sacx_create and before
+ * sacx_arena_bytes / sacx_layout / sacx_bind are used, as sacx_dp_init.  Appends, behind the "ppo.*"
+ * segments (every other segment keeps its offset): "v<k>.l<i>" (W_ext, one contiguous parameter
+ * range over all critics), "vc.adam_m" / "vc.adam_v" / "vc.grad" (that range's Adam moments and
+ * gradients, each one range length behind the last), "vc.ctl" (int64 x 16: steps run, Adam
+ * iterations, each critic's table rows), "vc.par", the tables "vc.s" [n_critics x buffer_capacity, S]
+ * and "vc.rtg" [n_critics, buffer_capacity], the rings "vc.stats" (a row per step: the summed loss,
+ * SACX_MAX_MODELS per-critic losses, the step number) and "vc.idx", and the work rows of a step
+ * (n_critics x batch rows), of the whole-table passes and of the GAE scan.  Errors: a second call, a
+ * bound handle, another handle kind, n_critics out of range. */
+int sacx_vcritic_init(sacx_handle* h, int32_t n_critics);
+/* VCritic._forward / value (critics.py:30-40) of critic `critic` on s[n,S], the state normalised
+ * with norm.s_*: out[n] = the net's output (value = 0), or that times norm.ret_den (value = 1). */
+int sacx_vcritic_value(sacx_handle* h, int32_t critic, const float* s, int64_t n, int32_t value, float* out);
+/* gae (buffer_utils.py:11-42) on given values over a batch of trajectories, in f64 as NumPy computes
+ * it: delta = r + gamma (1 - d) v_sp - v_s; adv_t = delta_t + gamma lam adv_{t+1}, restarted
+ * wherever traj[t+1] != traj[t] (gae_batch's sections, :63-65); rtg = adv + v_s; rtg_sp =
+ * (rtg - r) / gamma; each rounded to f32 once, at the store.  v_s, v_sp, r, d: float[n]; traj:
+ * int32[n]; 1 <= n <= cfg.buffer_capacity; gamma > 0.  A parallel segmented scan (two launches). */
+int sacx_gae_values(sacx_handle* h, const float* v_s, const float* v_sp, const float* r, const float* d,
+                    const int32_t* traj, int64_t n, double gamma, double lam, float* adv_out, float* rtg_out,
+                    float* rtg_sp_out);
+/* gae_batch (buffer_utils.py:44-83) with critic `critic`: value(s) and value(sp) (s, sp: [n,S]), then
+ * the arithmetic above, with no host round trip. */
+int sacx_gae(sacx_handle* h, int32_t critic, const float* s, const float* r, const float* sp, const float* d,
+             const int32_t* traj, int64_t n, double gamma, double lam, float* adv_out, float* rtg_out, float* rtg_sp_out);
+/* VCritic.get_loss (critics.py:42-49) of critic `critic` on s[n,S], rtg[n]: loss_out[0] (DEVICE float)
+ * = 0.5 mean((rtg / ret_den - v)^2), v the net's output (the reference's value / ret_den: the same up
+ * to an f32 ulp).  1 <= n <= cfg.buffer_capacity. */
+int sacx_vcritic_loss(sacx_handle* h, int32_t critic, const float* s, const float* rtg, int64_t n, float* loss_out);
+/* Stores s[n,S], rtg[n] (1 <= n <= cfg.buffer_capacity) as critic `critic`'s table, the rows the
+ * steps gather from (base_onpolicy_alg.py:226-229).  Tables may differ in length. */
+int sacx_vcritic_begin(sacx_handle* h, int32_t critic, const float* s, const float* rtg, int64_t n);
+/* n_steps x _apply_critic_grads (base_onpolicy_alg.py:244-251, :269-283) on the minibatches
+ * idx[n_steps, mb] (HOST array; 1 <= mb <= cfg.batch): the SAME row indices for every critic, each
+ * on its own table, so every index must be below the shortest table (n_samples = min, :231) and
+ * every critic needs a table.  Loss = the sum over the critics of get_loss; no clipping; one Keras
+ * Adam over all critics' variables (one iteration count, kept across calls; moments per variable) at
+ * critic_lr, which is written to "vc.par" in stream order and read by the launches (no constant of a
+ * captured graph).  No host synchronisation between the steps; replayed as captured graphs of
+ * 64 / 8 / 1 steps, or launched directly with SACX_STEP_EAGER (bit-identical).  A refused call
+ * touches nothing.  Each step appends a row to the "vc.stats" ring. */
+int sacx_vcritic_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, float critic_lr, int32_t flags);
+/* The tail of _update_critics (base_onpolicy_alg.py:253-264): out[k] = critic k's get_loss over its
+ * whole table with the weights as they stand (0 for k >= n_critics), out[SACX_MAX_MODELS] = the
+ * critics' Adam iteration count (every step run on the handle so far).  out: HOST
+ * double[SACX_MAX_MODELS + 1].  Synchronous. */
+int sacx_vcritic_end(sacx_handle* h, double* out);
+/* The launches of one critic step of mb rows per critic, as sacx_plan_info. */
+int sacx_vcritic_plan_info(sacx_handle* h, int32_t mb, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
+
 int sacx_sync(sacx_handle* h);
 /* Brings the arena to the state the calls so far define, without waiting: runs an alpha branch
  * the drop-in loop's one-update steps deferred (its alpha Adam, stats row and counters; see

@@ -21,6 +21,7 @@
 //   alpha.head     evaluate + alpha loss + Adam + clamp + stats   [SAC_expert.py:345-356]
 #include "sacx.h"
 #include "sacx_internal.h"
+#include "vcritic.h"
 #include "mt_jump.h"
 
 #include <rccl/rccl.h>
@@ -65,7 +66,7 @@ struct SegInfo {
 
 struct Launch {
     enum Kind { RNG, GATHER, GEMM, AHEAD, QHEAD, ABWD, FINAL, MGATHER, MLOSS, MFINAL, ALLREDUCE, APPLY, AAPPLY,
-                GNORM, LNORM, PPOGATHER, PPOHEAD, GNPART, PPOFINAL } kind;
+                GNORM, LNORM, PPOGATHER, PPOHEAD, GNPART, PPOFINAL, VCGATHER, VCHEAD, VCFINAL, VCADAM } kind;
     std::string name;
     RngArgs rng;
     GatherArgs gather;
@@ -83,6 +84,10 @@ struct Launch {
     PpoGatherArgs pg;          // PPOGATHER
     PpoHeadArgs ph;            // PPOHEAD
     PpoFinalArgs pf;           // PPOFINAL (GNPART: gn)
+    VcGatherArgs vg;           // VCGATHER
+    VcHeadArgs vh;             // VCHEAD
+    VcFinalArgs vf;            // VCFINAL
+    VcAdamArgs va;             // VCADAM
     float* ar_buf = nullptr;   // ALLREDUCE: in-place sum over the data-parallel ranks
     int64_t ar_count = 0;
     int grid = 0, block = 256;
@@ -116,6 +121,10 @@ const char* kernel_family(Launch::Kind k) {
         case Launch::PPOHEAD: return "k_ppo_head";
         case Launch::GNPART: return "k_gnorm";
         case Launch::PPOFINAL: return "k_ppo_final";
+        case Launch::VCGATHER: return "k_vc_gather";
+        case Launch::VCHEAD: return "k_vc_head";
+        case Launch::VCFINAL: return "k_vc_final";
+        case Launch::VCADAM: return "k_vc_adam";
     }
     return "?";
 }
@@ -163,6 +172,13 @@ struct sacx_handle {
     int64_t ppo_seq_host = 0; // minibatch steps issued (mirrors PpoCtl::seq: the index ring position)
     std::map<int, std::vector<Launch>> ppo_plans;                  // minibatch rows -> one step's launches
     std::map<std::pair<int, int>, hipGraphExec_t> ppo_graphs;      // (minibatch rows, steps) -> graph
+    // sacx_vcritic_init: the VCritics beside the trainable actor (sacx_vcritic_*, sacx_gae*, build_vc_plan)
+    int vc = 0;               // critics (0: none; the layout is then the handle's own)
+    int64_t vc_pstride = 0;   // floats between the critics' parameters, Adam moments and gradients
+    int64_t vc_rows[MAX_MODELS] = {0, 0, 0, 0, 0, 0, 0, 0};   // rows of each critic's table (mirrors VcCtl::n_rows)
+    int64_t vc_seq_host = 0;  // critic steps issued (mirrors VcCtl::seq: the index ring position)
+    std::map<int, std::vector<Launch>> vc_plans;
+    std::map<std::pair<int, int>, hipGraphExec_t> vc_graphs;
     // layout
     std::vector<SegInfo> segs;
     std::map<std::string, size_t> seg_index;
@@ -2739,6 +2755,10 @@ void enqueue(const Launch& L, sacx_handle* h, hipStream_t s) {
         case Launch::PPOHEAD: launch_ppo_head(L.ph, s); break;
         case Launch::GNPART: launch_gnorm_part(L.gn, s); break;
         case Launch::PPOFINAL: launch_ppo_final(L.pf, s); break;
+        case Launch::VCGATHER: launch_vc_gather(L.vg, s); break;
+        case Launch::VCHEAD: launch_vc_head(L.vh, s); break;
+        case Launch::VCFINAL: launch_vc_final(L.vf, s); break;
+        case Launch::VCADAM: launch_vc_adam(L.va, s); break;
     }
 }
 
@@ -3617,6 +3637,7 @@ void sacx_destroy(sacx_handle* h) {
         for (auto& kv : m) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->roll_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->ppo_graphs) (void)hipGraphExecDestroy(kv.second);
+    for (auto& kv : h->vc_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto e : h->events) (void)hipEventDestroy(e);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->done_host) (void)hipHostFree(h->done_host);
@@ -3803,6 +3824,12 @@ int sacx_resync(sacx_handle* h) {
         HIPCHK(h, hipMemcpy(&pc, h->ptr<PpoCtl>("ppo.ctl"), sizeof(PpoCtl), hipMemcpyDeviceToHost));
         h->ppo_seq_host = pc.seq;
         h->ppo_rows = pc.n_rows;
+    }
+    if (h->vc > 0) {
+        VcCtl vc{};
+        HIPCHK(h, hipMemcpy(&vc, h->ptr<VcCtl>("vc.ctl"), sizeof(VcCtl), hipMemcpyDeviceToHost));
+        h->vc_seq_host = vc.seq;
+        for (int k = 0; k < MAX_MODELS; ++k) h->vc_rows[k] = vc.n_rows[k];
     }
     return 0;
 }
@@ -5624,6 +5651,409 @@ int sacx_ppo_plan_info(sacx_handle* h, int32_t mb, sacx_launch_info* out, int32_
     if (!n_out) return fail(h, "null output");
     if (mb < 1 || mb > h->B) return fail(h, "minibatch rows outside [1, batch]");
     return launch_info(build_ppo_plan(h, mb), out, cap, n_out);
+}
+
+// ---------------------------------------------------------------- VCritics: value, GAE, the critic update
+// The critic side of MBRLOnPolicyAlg._update_actor_critic on a trainable GaussianActor handle:
+// VCritic._forward / value / get_loss (critics.py:30-49), gae / gae_batch (buffer_utils.py:8-83),
+// BaseOnPolicyAlg._update_critics / _apply_critic_grads (base_onpolicy_alg.py:219-283).
+int sacx_vcritic_init(sacx_handle* h, int32_t n_critics) {
+    if (!h) return -1;
+    if (h->bound) return fail(h, "sacx_vcritic_init must precede sacx_bind");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no VCritics");
+    if (h->vc > 0) return fail(h, "sacx_vcritic_init was already called on this handle");
+    if (n_critics < 1 || n_critics > SACX_MAX_MODELS)
+        return fail(h, "n_critics " + std::to_string(n_critics) + " outside [1, SACX_MAX_MODELS = " +
+                           std::to_string(SACX_MAX_MODELS) + "]");
+    static_assert(SACX_MAX_MODELS == MAX_MODELS, "VcCtl::n_rows and the statistics row hold one slot per critic");
+    static_assert(sizeof(VcCtl) == 128 && sizeof(VcPar) == 64, "vc.ctl is 16 int64, vc.par 16 words");
+    const int F = SACX_F32, S = h->S, B = h->B, nc = n_critics;
+    const int64_t cap = h->cap;
+    const NetDims& nd = h->nd[1];           // critic_layers / critic_activations (init_critic.py:10-21)
+    // behind the ppo.* segments: every segment of the handle as it was keeps its offset
+    uint64_t o0 = 0;
+    for (int k = 0; k < nc; ++k) {
+        int in = S;
+        for (int l = 0; l <= nd.D(); ++l) {
+            const int out = l < nd.D() ? nd.h[l] : 1;
+            const uint64_t o = h->add("v" + std::to_string(k) + ".l" + std::to_string(l), in + 1, out, F, SACX_ROLE_PARAM);
+            if (k == 0 && l == 0) o0 = o;
+            in = out;
+        }
+    }
+    h->arena_bytes = (h->arena_bytes + 255) & ~uint64_t(255);
+    h->vc_pstride = (int64_t)((h->arena_bytes - o0) / 4);
+    h->add("vc.adam_m", 1, h->vc_pstride, F, SACX_ROLE_STATE);      // at +1, +2, +3 vc_pstride of v0.l0
+    h->add("vc.adam_v", 1, h->vc_pstride, F, SACX_ROLE_STATE);
+    h->add("vc.grad", 1, h->vc_pstride, F, SACX_ROLE_WORK);
+    h->add("vc.ctl", 1, 16, SACX_I64, SACX_ROLE_STATE);
+    h->add("vc.par", 1, 16, F, SACX_ROLE_WORK);
+    h->add("vc.s", (int64_t)nc * cap, S, F, SACX_ROLE_STATE);       // critic k's table: rows [k cap, k cap + n_k)
+    h->add("vc.rtg", nc, cap, F, SACX_ROLE_STATE);
+    h->add("vc.stats", h->stats_cap, VC_STAT_COLS, F, SACX_ROLE_STATE);
+    h->add("vc.idx", VC_IDX_CAP, B, SACX_I32, SACX_ROLE_WORK);
+    h->add("vc.loss", 1, MAX_MODELS, F, SACX_ROLE_WORK);            // the whole-table losses (sacx_vcritic_end)
+    // a step's rows: critic k's minibatch is rows [k mb, (k + 1) mb)
+    const int64_t R = (int64_t)nc * B;
+    h->add("vc.X", R, h->ldS, F, 0);
+    h->add("vc.T", 1, R, F, 0);
+    h->add("vc.O", R, 1, F, 0);
+    h->add("vc.G", R, 1, F, 0);
+    h->add("vc.sq", 1, R, F, 0);
+    for (int l = 0; l < nd.D(); ++l) {
+        h->add("vc.H" + std::to_string(l), R, nd.h[l], F, 0);
+        h->add("vc.D" + std::to_string(l), R, nd.h[l], F, 0);
+    }
+    // the whole-table passes and the GAE scan
+    h->add("vc.tmp", 1, cap, F, 0);
+    h->add("vc.gv", 2, cap, F, 0);                                  // value(s), value(sp) of sacx_gae
+    h->add("vc.gagg", (cap + GAE_TILE - 1) / GAE_TILE, 2, SACX_F64, 0);
+    h->arena_bytes = (h->arena_bytes + 255) & ~uint64_t(255);
+    h->seed_bytes = h->arena_bytes;         // (one learner per trainable handle)
+    h->vc = nc;
+    return 0;
+}
+
+static int vc_check(sacx_handle* h) {
+    if (!h || !h->bound) return fail(h, "not bound");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no VCritics");
+    if (h->vc < 1) return fail(h, "the handle has no VCritics (sacx_vcritic_init was not called)");
+    return 0;
+}
+static int vc_check_critic(sacx_handle* h, int32_t critic) {
+    if (vc_check(h)) return -1;
+    if (critic < 0 || critic >= h->vc)
+        return fail(h, "critic " + std::to_string(critic) + " outside [0, " + std::to_string(h->vc) + ")");
+    return 0;
+}
+
+// One minibatch step of mb rows per critic (base_onpolicy_alg.py:269-283) as a launch list:
+//   vc.gather    every critic's table rows by the step's indices -> normalised states, rtg / ret_den
+//   v.fwd<i>     the hidden layers, then the output layer (N = 1), one problem per critic
+//   vc.head      g = (v - rtg_n) / mb, the rows' squared differences
+//   v.bwd<i>     dX from the output layer down
+//   v.grad[.j]   every dW stored, not applied (EPI_STORE; the fused epilogue takes its rate and
+//                iteration count from ctl / the plan's constants, which cannot point at vc.*): the
+//                n_critics x (layers + 1) problems, GEMM_MAXP to a launch -- the one stage whose
+//                launch count grows with the critics (two layers: 1 launch up to 2 critics, 2 up to 5, 3 up to 8)
+//   vc.final     each critic's loss, their sum, the statistics row, the counters
+//   v.adam       one Keras Adam over the critics' parameter range at the device-read rate
+static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
+    auto it = h->vc_plans.find(mb);
+    if (it != h->vc_plans.end()) return it->second;
+    std::vector<Launch> plan;
+    const int cur = h->probs_cursor;
+    const int S = h->S, ldS = h->ldS, nc = h->vc;
+    const NetDims& nd = h->nd[1];
+    const int D = nd.D();
+    auto W = [&](const std::string& n) { return h->f(n); };
+    auto L_ = [](int k, int i) { return "v" + std::to_string(k) + ".l" + std::to_string(i); };
+    auto Hb = [&](int i, int k) { return W("vc.H" + std::to_string(i)) + (size_t)k * mb * nd.h[i]; };
+    auto Db = [&](int i, int k) { return W("vc.D" + std::to_string(i)) + (size_t)k * mb * nd.h[i]; };
+    VcCtl* ctl = h->ptr<VcCtl>("vc.ctl");
+    VcPar* par = h->ptr<VcPar>("vc.par");
+    float *X = W("vc.X"), *O = W("vc.O"), *G = W("vc.G"), *T = W("vc.T"), *sq = W("vc.sq");
+    const int rows = nc * mb;
+    {
+        Launch L{};
+        L.kind = Launch::VCGATHER;
+        L.name = "vc.gather";
+        VcGatherArgs& g = L.vg;
+        g.s = W("vc.s"); g.s_stride = h->cap * S; g.rtg = W("vc.rtg"); g.rtg_stride = h->cap;
+        g.idx_ring = h->ptr<int32_t>("vc.idx"); g.idx_ld = h->B; g.ctl = ctl;
+        g.s_mean = W("norm.s_mean"); g.s_den = W("norm.s_den"); g.ret_den = W("norm.ret_den");
+        g.S = S; g.ldS = ldS; g.mb = mb; g.nc = nc; g.X = X; g.T = T;
+        L.grid = (rows + VC_GATHER_ROWS - 1) / VC_GATHER_ROWS;
+        L.bytes = 4.0 * rows * (S + ldS + 3);
+        plan.push_back(L);
+    }
+    for (int i = 0; i <= D; ++i) {
+        std::vector<GemmProb> ps;
+        for (int k = 0; k < nc; ++k) {
+            const float* in = i == 0 ? X + (size_t)k * mb * ldS : Hb(i - 1, k);
+            const int ldi = i == 0 ? ldS : nd.h[i - 1], K = i == 0 ? S : nd.h[i - 1];
+            ps.push_back(i < D ? prob_fwd(in, ldi, mb, K, W(L_(k, i)), nd.h[i], Hb(i, k), nd.act[i])
+                               : prob_fwd(in, ldi, mb, K, W(L_(k, i)), 1, O + (size_t)k * mb, ACT_NONE));
+        }
+        add_gemm(h, plan, "v.fwd" + std::to_string(i), ps, false);
+    }
+    {
+        Launch L{};
+        L.kind = Launch::VCHEAD;
+        L.name = "vc.head";
+        VcHeadArgs& a = L.vh;
+        a.O = O; a.T = T; a.rows = rows; a.mb = mb; a.G = G; a.sq = sq;
+        L.grid = (rows + 255) / 256;
+        L.flops = 4.0 * rows;
+        L.bytes = 16.0 * rows;
+        plan.push_back(L);
+    }
+    for (int i = D; i >= 1; --i) {
+        std::vector<GemmProb> ps;
+        for (int k = 0; k < nc; ++k)
+            ps.push_back(prob_dx(i == D ? G + (size_t)k * mb : Db(i, k), mb, i == D ? 1 : nd.h[i], W(L_(k, i)), nd.h[i - 1],
+                                 Hb(i - 1, k), Db(i - 1, k), nd.act[i - 1]));
+        add_gemm(h, plan, "v.bwd" + std::to_string(i), ps, false);
+    }
+    {
+        std::vector<GemmProb> pw;
+        for (int k = 0; k < nc; ++k)
+            for (int i = 0; i <= D; ++i) {
+                const float* Xi = i == 0 ? X + (size_t)k * mb * ldS : Hb(i - 1, k);
+                const int K = i == 0 ? S : nd.h[i - 1];
+                pw.push_back(prob_dw(Xi, i == 0 ? ldS : K, K, mb, i == D ? G + (size_t)k * mb : Db(i, k), i == D ? 1 : nd.h[i],
+                                     W(L_(k, i)), nullptr, GRP_Q));
+            }
+        const int n_dw = add_gemm_split(h, plan, "v.grad", pw, false);
+        for (int j = 0; j < n_dw; ++j) {       // the gradients go to +3 vc_pstride of the critics' own range
+            Launch& Gl = plan[plan.size() - 1 - j];
+            for (int i = 0; i < Gl.gemm.nprob; ++i) Gl.gemm.probs[i].epi = EPI_STORE;
+            Gl.gemm.p_stride = h->vc_pstride;
+        }
+    }
+    {
+        Launch L{};
+        L.kind = Launch::VCFINAL;
+        L.name = "vc.final";
+        VcFinalArgs& a = L.vf;
+        a.sq = sq; a.mb = mb; a.nc = nc; a.ctl = ctl; a.stats = W("vc.stats"); a.stats_cap = h->stats_cap;
+        L.grid = 1;
+        L.bytes = 4.0 * rows;
+        plan.push_back(L);
+    }
+    {
+        Launch U{};
+        U.kind = Launch::VCADAM;
+        U.name = "v.adam";
+        VcAdamArgs& a = U.va;
+        const SegInfo& sl = h->seg(L_(nc - 1, D));
+        a.P = W("v0.l0");
+        a.n = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("v0.l0")) / 4);
+        a.p_stride = h->vc_pstride; a.lr_dev = &par->critic_lr; a.t_dev = &ctl->t; a.t_adv = 1;   // vc.final advanced t
+        U.grid = (int)((a.n + 255) / 256);
+        U.bytes = 4.0 * a.n * 7;
+        plan.push_back(U);
+    }
+    h->probs_cursor = cur;
+    return h->vc_plans.emplace(mb, std::move(plan)).first->second;
+}
+
+// critic `critic` on m <= ACT_CAP caller rows s: normalise, hidden layers, the output layer -> act.Q [m]
+static void vc_forward(sacx_handle* h, int critic, const float* s, int m) {
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    const NetDims& nd = h->nd[1];
+    const std::string net = "v" + std::to_string(critic);
+    launch_obs_norm(s, m, h->S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), h->ldS, h->stream);
+    const float* Hl = net_hidden(h, net, nd, W("act.X"), h->ldS, h->S, m, W("act.H1"), W("act.H2"), h->stream);
+    std::vector<Launch> pl;
+    add_gemm(h, pl, "v.out", {prob_fwd(Hl, nd.h.back(), m, nd.h.back(), W(net + ".l" + std::to_string(nd.D())), 1, W("act.Q"),
+                                       ACT_NONE)}, false);
+    h->probs_cursor -= 1;
+    launch_gemm(pl[0].gemm, h->stream);
+}
+
+// the whole-table passes: n rows of s through critic `critic` in chunks of ACT_CAP, k_vc_rows on each
+// (out: the [n] outputs, x ret_den with value; sq: (rtg / ret_den - v)^2 per row)
+static int vc_rows_pass(sacx_handle* h, int critic, const float* s, int64_t n, int value, float* out, const float* rtg,
+                        float* sq) {
+    for (int64_t done = 0; done < n; done += ACT_CAP) {
+        const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
+        vc_forward(h, critic, s + done * h->S, m);
+        VcRowsArgs r{};
+        r.Q = h->f("act.Q"); r.m = m; r.value = value; r.ret_den = h->f("norm.ret_den");
+        r.rtg = rtg ? rtg + done : nullptr; r.out = out ? out + done : nullptr; r.sq = sq ? sq + done : nullptr;
+        launch_vc_rows(r, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int sacx_vcritic_value(sacx_handle* h, int32_t critic, const float* s, int64_t n, int32_t value, float* out) {
+    if (vc_check_critic(h, critic)) return -1;
+    if (n < 0 || (n > 0 && (!s || !out))) return fail(h, "bad arguments");
+    return vc_rows_pass(h, critic, s, n, value ? 1 : 0, out, nullptr, nullptr);
+}
+
+static int gae_launch(sacx_handle* h, const float* v_s, const float* v_sp, const float* r, const float* d,
+                      const int32_t* traj, int64_t n, double gamma, double lam, float* adv, float* rtg, float* rtg_sp) {
+    GaeArgs g{};
+    g.v_s = v_s; g.v_sp = v_sp; g.r = r; g.d = d; g.traj = traj; g.n = n;
+    g.gamma = gamma; g.gl = gamma * lam;
+    g.agg = h->ptr<double>("vc.gagg"); g.tiles = (int32_t)((n + GAE_TILE - 1) / GAE_TILE);
+    g.adv = adv; g.rtg = rtg; g.rtg_sp = rtg_sp;
+    launch_gae(g, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+static int gae_args_check(sacx_handle* h, const void* r, const void* d, const void* traj, int64_t n, double gamma,
+                          const void* adv, const void* rtg, const void* rtg_sp) {
+    if (!r || !d || !traj || !adv || !rtg || !rtg_sp) return fail(h, "null pointer");
+    if (n < 1 || n > h->cap)
+        return fail(h, "rows " + std::to_string(n) + " outside [1, buffer_capacity = " + std::to_string(h->cap) + "]");
+    if (!(gamma > 0.0)) return fail(h, "gamma must be positive (rtg_sp divides by it)");
+    return 0;
+}
+
+int sacx_gae_values(sacx_handle* h, const float* v_s, const float* v_sp, const float* r, const float* d,
+                    const int32_t* traj, int64_t n, double gamma, double lam, float* adv_out, float* rtg_out,
+                    float* rtg_sp_out) {
+    if (vc_check(h)) return -1;
+    if (!v_s || !v_sp) return fail(h, "null pointer");
+    if (gae_args_check(h, r, d, traj, n, gamma, adv_out, rtg_out, rtg_sp_out)) return -1;
+    return gae_launch(h, v_s, v_sp, r, d, traj, n, gamma, lam, adv_out, rtg_out, rtg_sp_out);
+}
+
+int sacx_gae(sacx_handle* h, int32_t critic, const float* s, const float* r, const float* sp, const float* d,
+             const int32_t* traj, int64_t n, double gamma, double lam, float* adv_out, float* rtg_out, float* rtg_sp_out) {
+    if (vc_check_critic(h, critic)) return -1;
+    if (!s || !sp) return fail(h, "null pointer");
+    if (gae_args_check(h, r, d, traj, n, gamma, adv_out, rtg_out, rtg_sp_out)) return -1;
+    float* gv = h->f("vc.gv");
+    if (vc_rows_pass(h, critic, s, n, 1, gv, nullptr, nullptr)) return -1;
+    if (vc_rows_pass(h, critic, sp, n, 1, gv + h->cap, nullptr, nullptr)) return -1;
+    return gae_launch(h, gv, gv + h->cap, r, d, traj, n, gamma, lam, adv_out, rtg_out, rtg_sp_out);
+}
+
+// 0.5 mean((rtg / ret_den - v)^2) of critic `critic` over n rows -> dst (device), through vc.tmp
+static int vc_loss_pass(sacx_handle* h, int critic, const float* s, const float* rtg, int64_t n, float* dst) {
+    if (vc_rows_pass(h, critic, s, n, 0, nullptr, rtg, h->f("vc.tmp"))) return -1;
+    VcReduceArgs q{};
+    q.sq = h->f("vc.tmp"); q.n = n; q.out = dst;
+    launch_vc_reduce(q, h->stream);
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int sacx_vcritic_loss(sacx_handle* h, int32_t critic, const float* s, const float* rtg, int64_t n, float* loss_out) {
+    if (vc_check_critic(h, critic)) return -1;
+    if (!s || !rtg || !loss_out) return fail(h, "null pointer");
+    if (n < 1 || n > h->cap)
+        return fail(h, "rows " + std::to_string(n) + " outside [1, buffer_capacity = " + std::to_string(h->cap) + "]");
+    return vc_loss_pass(h, critic, s, rtg, n, loss_out);
+}
+
+int sacx_vcritic_begin(sacx_handle* h, int32_t critic, const float* s, const float* rtg, int64_t n) {
+    if (vc_check_critic(h, critic)) return -1;
+    if (!s || !rtg) return fail(h, "null table pointer");
+    if (n < 1 || n > h->cap)
+        return fail(h, "table rows " + std::to_string(n) + " outside [1, buffer_capacity = " + std::to_string(h->cap) + "]");
+    const int S = h->S;
+    HIPCHK(h, hipMemcpyAsync(h->f("vc.s") + (size_t)critic * h->cap * S, s, sizeof(float) * (size_t)n * S,
+                             hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->f("vc.rtg") + (size_t)critic * h->cap, rtg, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice,
+                             h->stream));
+    launch_vc_set(nullptr, VcPar{}, h->ptr<VcCtl>("vc.ctl"), critic, n, h->stream);
+    // the gradient words of the critics' parameter range: Adam reads all of it, the dW launches write
+    // the weights' words only (not the padding between segments)
+    HIPCHK(h, hipMemsetAsync(h->f("vc.grad"), 0, sizeof(float) * (size_t)h->vc_pstride, h->stream));
+    HIPCHK(h, hipGetLastError());
+    h->vc_rows[critic] = n;
+    return 0;
+}
+
+int sacx_vcritic_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, float critic_lr, int32_t flags) {
+    if (vc_check(h)) return -1;
+    if (n_steps <= 0) return 0;
+    if (!idx) return fail(h, "null index array");
+    int64_t n_min = h->vc_rows[0];
+    for (int k = 0; k < h->vc; ++k) {
+        if (h->vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
+        n_min = std::min(n_min, h->vc_rows[k]);
+    }
+    if (mb < 1 || mb > h->B)
+        return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
+    for (int64_t i = 0; i < n_steps * (int64_t)mb; ++i)
+        if (idx[i] < 0 || idx[i] >= n_min) return fail(h, "minibatch index outside the shortest critic table");
+    if (!(critic_lr >= 0.f)) return fail(h, "critic_lr must be non-negative");
+    const std::vector<Launch>& plan = build_vc_plan(h, mb);
+    VcPar par{};
+    par.critic_lr = critic_lr;
+    launch_vc_set(h->ptr<VcPar>("vc.par"), par, h->ptr<VcCtl>("vc.ctl"), -1, 0, h->stream);
+    int32_t* ring = h->ptr<int32_t>("vc.idx");
+    const int B = h->B;
+    // each step reads its minibatch from the index ring at VcCtl::seq, so a graph of several steps
+    // replays them back to back (the capture discipline of sacx_ppo_steps)
+    auto graph_of = [&](int n, hipGraphExec_t* out) -> int {
+        auto it = h->vc_graphs.find({mb, n});
+        if (it != h->vc_graphs.end()) {
+            *out = it->second;
+            return 0;
+        }
+        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+        for (int j = 0; j < n; ++j)
+            for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
+        const hipError_t le = hipGetLastError();
+        hipGraph_t graph = nullptr;
+        const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
+        if (le != hipSuccess || ee != hipSuccess) {
+            if (graph) (void)hipGraphDestroy(graph);
+            return fail(h, std::string("critic step graph capture: ") + hipGetErrorString(le != hipSuccess ? le : ee));
+        }
+        hipGraphExec_t ex = nullptr;
+        const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) return fail(h, std::string("critic step graph instantiate: ") + hipGetErrorString(ie));
+        h->vc_graphs[{mb, n}] = ex;
+        *out = ex;
+        return 0;
+    };
+    for (int64_t done = 0; done < n_steps;) {
+        const int64_t chunk = std::min<int64_t>(n_steps - done, VC_IDX_CAP);
+        HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
+        const int64_t s0 = h->vc_seq_host % VC_IDX_CAP;
+        const int64_t first = std::min<int64_t>(chunk, VC_IDX_CAP - s0);
+        HIPCHK(h, hipMemcpy2D(ring + s0 * B, sizeof(int32_t) * B, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
+                              (size_t)first, hipMemcpyHostToDevice));
+        if (chunk > first)
+            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * B, idx + (done + first) * mb, sizeof(int32_t) * mb,
+                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
+        if (flags & SACX_STEP_EAGER) {
+            for (int64_t j = 0; j < chunk; ++j)
+                for (const Launch& L : plan) enqueue(L, h, h->stream);
+            h->vc_seq_host += chunk;
+            HIPCHK(h, hipGetLastError());
+        } else {
+            for (int64_t j = 0; j < chunk;) {
+                const int n = chunk - j >= 64 ? 64 : chunk - j >= 8 ? 8 : 1;
+                hipGraphExec_t ex = nullptr;
+                if (graph_of(n, &ex)) return -1;
+                HIPCHK(h, hipGraphLaunch(ex, h->stream));
+                h->vc_seq_host += n;
+                j += n;
+            }
+        }
+        done += chunk;
+    }
+    return 0;
+}
+
+int sacx_vcritic_end(sacx_handle* h, double* out) {
+    if (vc_check(h)) return -1;
+    if (!out) return fail(h, "null output");
+    for (int k = 0; k < h->vc; ++k)
+        if (h->vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
+    float* ls = h->f("vc.loss");
+    for (int k = 0; k < h->vc; ++k)
+        if (vc_loss_pass(h, k, h->f("vc.s") + (size_t)k * h->cap * h->S, h->f("vc.rtg") + (size_t)k * h->cap, h->vc_rows[k], ls + k))
+            return -1;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float lh[MAX_MODELS];
+    VcCtl vc{};
+    HIPCHK(h, hipMemcpy(lh, ls, sizeof(lh), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&vc, h->ptr<VcCtl>("vc.ctl"), sizeof(vc), hipMemcpyDeviceToHost));
+    for (int k = 0; k < MAX_MODELS; ++k) out[k] = k < h->vc ? (double)lh[k] : 0.0;
+    out[MAX_MODELS] = (double)vc.t;
+    return 0;
+}
+
+int sacx_vcritic_plan_info(sacx_handle* h, int32_t mb, sacx_launch_info* out, int32_t cap, int32_t* n_out) {
+    if (vc_check(h)) return -1;
+    if (!n_out) return fail(h, "null output");
+    if (mb < 1 || mb > h->B) return fail(h, "minibatch rows outside [1, batch]");
+    return launch_info(build_vc_plan(h, mb), out, cap, n_out);
 }
 
 }  // extern "C"

@@ -21,6 +21,8 @@ DTYPES = {0: "f32", 1: "i32", 2: "i64", 3: "u32", 4: "f64"}
 EXPERT_OFF, EXPERT_EO, EXPERT_BC = 0, 1, 2      # sacx_config.use_expert (SACX_EXPERT_*)
 ACTOR_SQUASHED, ACTOR_GAUSSIAN, ACTOR_GAUSSIAN_TRAIN = 0, 1, 2     # sacx_config.actor_gaussian (SACX_ACTOR_*)
 PPO_STAT_NAMES = ["loss", "ent", "grad_norm_pre", "grad_norm_post", "alpha", "pg_loss", "adv_std", "step"]
+GAE_TILE = 2048                 # rows per workgroup of the GAE scan (csrc/vcritic.h): tests place boundaries on it
+VC_STAT_NAMES = ["loss"] + [f"loss{k}" for k in range(MAX_MODELS)] + ["step"]    # a "vc.stats" row
 STEP_EXTERNAL_RANDOMS = 1
 STEP_EAGER = 2
 ROLE_WORK, ROLE_PARAM, ROLE_TARGET, ROLE_STATE = 0, 1, 2, 3
@@ -40,6 +42,8 @@ EXPORTS = [
     "sacx_model_loss", "sacx_spec_hits", "sacx_settle", "sacx_model_sample",
     "sacx_ppo_neglogp", "sacx_ppo_dist", "sacx_ppo_kl", "sacx_ppo_begin", "sacx_ppo_steps", "sacx_ppo_end",
     "sacx_ppo_plan_info",
+    "sacx_vcritic_init", "sacx_vcritic_value", "sacx_gae_values", "sacx_gae", "sacx_vcritic_loss", "sacx_vcritic_begin",
+    "sacx_vcritic_steps", "sacx_vcritic_end", "sacx_vcritic_plan_info",
 ]
 
 
@@ -203,6 +207,15 @@ def lib():
         "sacx_ppo_steps": (ctypes.c_int, [vp, vp, i64, i32, P(PpoParams), i32]),
         "sacx_ppo_end": (ctypes.c_int, [vp, f32, P(f64)]),
         "sacx_ppo_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
+        "sacx_vcritic_init": (ctypes.c_int, [vp, i32]),
+        "sacx_vcritic_value": (ctypes.c_int, [vp, i32, vp, i64, i32, vp]),
+        "sacx_gae_values": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, i64, f64, f64, vp, vp, vp]),
+        "sacx_gae": (ctypes.c_int, [vp, i32, vp, vp, vp, vp, vp, i64, f64, f64, vp, vp, vp]),
+        "sacx_vcritic_loss": (ctypes.c_int, [vp, i32, vp, vp, i64, vp]),
+        "sacx_vcritic_begin": (ctypes.c_int, [vp, i32, vp, vp, i64]),
+        "sacx_vcritic_steps": (ctypes.c_int, [vp, vp, i64, i32, f32, i32]),
+        "sacx_vcritic_end": (ctypes.c_int, [vp, P(f64)]),
+        "sacx_vcritic_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -81,6 +81,9 @@ class PPO:
         self.ent_targ = kw['ent_targ']
         self.alpha_lr = kw['alpha_lr']
         self._rollout_capacity = kw.get('rollout_capacity')
+        # VCritics (of the actor's layers) on the engine this class builds (0: none, today's engine), so that
+        # VCriticUpdate and TrajectoryBuffer.get_update_info run on the actor's engine
+        self._vcritics = int(kw.get('vcritics') or 0)
 
     @property
     def alpha(self):
@@ -99,7 +102,7 @@ class PPO:
                 actor_activations=a.activations, batch=int(n_batch),
                 buffer_capacity=int(max(n, self._rollout_capacity or 0)), per_state_std=a.per_state_std,
                 actor_gaussian="train", actor_std_mult=float(a.std_mult), actor_output_norm=a.output_norm,
-                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096)
+                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096, vcritics=self._vcritics)
             self.engine = Engine(cfg)
             w = a.get_weights()
             a._bind(self.engine, "actor", with_logstd=False)

@@ -66,9 +66,43 @@ class QCritic(_Critic):
 
 
 class VCritic(_Critic):
-    """State-value critic of the on-policy path (critics.py:6-57); kept so init_critics returns
-    the same tuple.  SAC never evaluates it (the on-policy path is out of scope), so it has
-    weights but no device network."""
+    """State-value critic of the on-policy path (critics.py:6-57).  Bound to a trainable engine with
+    critics (``EngineConfig(actor_gaussian="train", vcritics=n)``) as net ``v<k>``, ``_forward`` /
+    ``value`` / ``get_loss`` run on the GPU (``sacx_vcritic_value`` / ``sacx_vcritic_loss``), and
+    ``sac_eo.algs.model_free.VCriticUpdate`` trains it.  SAC never evaluates it."""
 
     def __init__(self, env, layers, activations, gain, rng=None):
         super().__init__(int(np.prod(env.observation_space.shape)), 1, layers, activations, gain, rng)
+
+    def _bind(self, engine, net):
+        if int(getattr(engine.cfg, "vcritics", 0)) < 1:
+            raise RuntimeError("VCritic needs an engine with critics (EngineConfig(actor_gaussian='train', vcritics=n))")
+        if not (net[:1] == "v" and net[1:].isdigit() and int(net[1:]) < int(engine.cfg.vcritics)):
+            raise ValueError(f"VCritic binds to v0 .. v{int(engine.cfg.vcritics) - 1}, not {net!r}")
+        super()._bind(engine, net)
+
+    @property
+    def _index(self):
+        return int(self._net[1:])
+
+    def set_rms(self, normalizer):
+        self.s_rms, _, _, _, self.ret_rms = normalizer.get_rms()
+
+    def _forward(self, s):
+        """Net output [n, 1] on s_rms.normalize(s) (critics.py:30-34)."""
+        eng = self._require()
+        out = eng.vcritic_value(self._index, np.asarray(s, np.float32).reshape(-1, eng.cfg.s_dim), value=False)
+        return _as_out(out.cpu().numpy().reshape(-1, 1))
+
+    def value(self, s):
+        """squeeze(_forward(s), -1) * max(ret_rms.std, 1e-8) (critics.py:36-40)."""
+        eng = self._require()
+        out = eng.vcritic_value(self._index, np.asarray(s, np.float32).reshape(-1, eng.cfg.s_dim), value=True)
+        return _as_out(out.cpu().numpy())
+
+    def get_loss(self, s, rtg):
+        """0.5 mean((rtg_norm - value_norm)^2) (critics.py:42-49)."""
+        eng = self._require()
+        out = eng.vcritic_loss(self._index, np.asarray(s, np.float32).reshape(-1, eng.cfg.s_dim),
+                               np.asarray(rtg, np.float32).reshape(-1))
+        return _as_out(out.cpu().numpy()[0])

@@ -89,6 +89,11 @@ class EngineConfig:
     # the expert path (world models, expert rows, permutations); critics, targets and alpha stay in
     # the arena untouched.  fp32, one seed, no data-parallel ranks.
     bc: bool = False
+    # VCritics beside a trainable GaussianActor (actor_gaussian="train"): n nets [S] -> critic layers -> 1
+    # named "v0" .. "v<n-1>" (num_models under --critic_ensemble, else 1; init_critic.py:10), with
+    # Engine.vcritic_* / gae / gae_values.  A host-only field: Engine makes the handle's init call
+    # right after creating it; 0 leaves the handle and its layout as they are
+    vcritics: int = 0
 
     def __post_init__(self):
         if self.bc:
@@ -220,6 +225,11 @@ class Engine:
         c = cfg.to_c()
         N.check(self.lib.sacx_create(ctypes.byref(c), ctypes.byref(h)), None, "sacx_create")
         self.h = h
+        if int(cfg.vcritics) > 0 and self.lib.sacx_vcritic_init(h, int(cfg.vcritics)) != 0:
+            msg = (self.lib.sacx_last_error(h) or b"").decode()
+            self.lib.sacx_destroy(h)                        # (nothing else holds the handle yet)
+            self.h = None
+            raise N.SacxError(f"sacx_vcritic_init: {msg}")
         total = int(self.lib.sacx_arena_bytes(h))
         self.seeds = max(1, int(cfg.seeds))
         self.seed_stride = int(self.lib.sacx_seed_stride(h))
@@ -640,6 +650,118 @@ class Engine:
         N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), None, 0, ctypes.byref(n)), self.h, "ppo_plan_info")
         arr = (N.LaunchInfo * n.value)()
         N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), arr, n.value, ctypes.byref(n)), self.h, "ppo_plan_info")
+        return [dict(name=a.name.decode(), kernel=a.kernel.decode(), grid=a.grid, block=a.block,
+                     flops=a.flops, bytes=a.bytes) for a in arr]
+
+    # ------------------------------------------------------------------ VCritics: value, GAE, the critic update
+    # (EngineConfig(actor_gaussian="train", vcritics=n); every call fails with a message on any other engine)
+    def vcritic_value(self, critic: int, s, value: bool = True) -> "torch.Tensor":
+        """VCritic._forward (value=False) / value (value=True: x ret sigma) (critics.py:30-40) of critic
+        ``critic`` on s [n, S] -> [n] (CUDA)."""
+        x = self._dev(s, (-1, self.cfg.s_dim))
+        n = int(x.shape[0])
+        out = torch.empty((n,), dtype=torch.float32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_vcritic_value(self.h, int(critic), p(x), n, int(bool(value)), p(out)), self.h, "vcritic_value")
+        self._keep_vc = (x,)
+        return out
+
+    def _gae_rows(self, r, d, traj, n):
+        rr, dd = self._dev(r, (-1,)), self._dev(d, (-1,))      # (done flags arrive as f64 0 / 1: exact in f32)
+        # the trajectory indices (floats in the reference) matter only where they change: ANY difference
+        # between neighbours starts a trajectory (buffer_utils.py:63), so the device gets a running segment id
+        tj = np.asarray(traj.cpu().numpy() if torch.is_tensor(traj) else traj).reshape(-1)
+        seg = np.zeros(tj.shape[0], np.int32)
+        if tj.shape[0] > 1:
+            seg[1:] = np.cumsum(tj[1:] != tj[:-1], dtype=np.int32)
+        tt = torch.as_tensor(seg, device=self.device)
+        if int(rr.shape[0]) != n or int(dd.shape[0]) != n or int(tt.shape[0]) != n:
+            raise ValueError("the rows of a GAE batch need the same length")
+        kw = dict(dtype=torch.float32, device=self.device)
+        return rr, dd, tt, (torch.empty((n,), **kw), torch.empty((n,), **kw), torch.empty((n,), **kw))
+
+    def gae_values(self, v_s, v_sp, r, d, traj, gamma: float, lam: float):
+        """gae (buffer_utils.py:11-42) on given values over a batch of trajectories (``traj``: the
+        trajectory index of every row; the scan restarts where it changes), f64 arithmetic on the
+        device -> (adv, rtg, rtg_sp) [n] CUDA tensors."""
+        vs, vsp = self._dev(v_s, (-1,)), self._dev(v_sp, (-1,))
+        n = int(vs.shape[0])
+        if int(vsp.shape[0]) != n:
+            raise ValueError("the rows of a GAE batch need the same length")
+        rr, dd, tt, (adv, rtg, rtg_sp) = self._gae_rows(r, d, traj, n)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_gae_values(self.h, p(vs), p(vsp), p(rr), p(dd), p(tt), n, float(gamma), float(lam),
+                                         p(adv), p(rtg), p(rtg_sp)), self.h, "gae_values")
+        self._keep_vc = (vs, vsp, rr, dd, tt)
+        return adv, rtg, rtg_sp
+
+    def gae(self, critic: int, s, r, sp, d, traj, gamma: float, lam: float):
+        """gae_batch (buffer_utils.py:44-83) with critic ``critic``: value(s), value(sp) and the scan in
+        one call, no host round trip -> (adv, rtg, rtg_sp) [n] CUDA tensors."""
+        S = self.cfg.s_dim
+        x, xp = self._dev(s, (-1, S)), self._dev(sp, (-1, S))
+        n = int(x.shape[0])
+        if int(xp.shape[0]) != n:
+            raise ValueError("the rows of a GAE batch need the same length")
+        rr, dd, tt, (adv, rtg, rtg_sp) = self._gae_rows(r, d, traj, n)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_gae(self.h, int(critic), p(x), p(rr), p(xp), p(dd), p(tt), n, float(gamma), float(lam),
+                                  p(adv), p(rtg), p(rtg_sp)), self.h, "gae")
+        self._keep_vc = (x, xp, rr, dd, tt)
+        return adv, rtg, rtg_sp
+
+    def vcritic_loss(self, critic: int, s, rtg) -> "torch.Tensor":
+        """VCritic.get_loss (critics.py:42-49) of critic ``critic`` on s [n, S], rtg [n] -> [1] (CUDA)."""
+        x, t = self._dev(s, (-1, self.cfg.s_dim)), self._dev(rtg, (-1,))
+        n = int(x.shape[0])
+        if int(t.shape[0]) != n:
+            raise ValueError("s and rtg need the same number of rows")
+        out = torch.empty((1,), dtype=torch.float32, device=self.device)
+        p = lambda u: ctypes.c_void_p(u.data_ptr())
+        N.check(self.lib.sacx_vcritic_loss(self.h, int(critic), p(x), p(t), n, p(out)), self.h, "vcritic_loss")
+        self._keep_vc = (x, t)
+        return out
+
+    def vcritic_begin(self, critic: int, s, rtg) -> int:
+        """Stores s [n, S], rtg [n] as critic ``critic``'s table (the rows the steps gather from).  Returns n."""
+        x, t = self._dev(s, (-1, self.cfg.s_dim)), self._dev(rtg, (-1,))
+        n = int(x.shape[0])
+        if int(t.shape[0]) != n:
+            raise ValueError("s and rtg need the same number of rows")
+        p = lambda u: ctypes.c_void_p(u.data_ptr())
+        N.check(self.lib.sacx_vcritic_begin(self.h, int(critic), p(x), p(t), n), self.h, "vcritic_begin")
+        self._keep_vc = (x, t)
+        return n
+
+    def vcritic_steps(self, idx: np.ndarray, *, critic_lr: float, eager: bool = False):
+        """``idx[n_steps, mb]`` (table rows, the same for every critic): n_steps x _apply_critic_grads
+        (base_onpolicy_alg.py:269-283) with no host synchronisation between them."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.ndim != 2:
+            raise ValueError("idx must be [n_steps, mb]")
+        N.check(self.lib.sacx_vcritic_steps(self.h, idx.ctypes.data, int(idx.shape[0]), int(idx.shape[1]), float(critic_lr),
+                                            N.STEP_EAGER if eager else 0), self.h, "vcritic_steps")
+
+    def vcritic_end(self) -> dict:
+        """The tail of _update_critics (base_onpolicy_alg.py:253-264): every critic's get_loss over its
+        whole table with the weights as they stand, and the critics' Adam iteration count."""
+        out = (ctypes.c_double * (N.MAX_MODELS + 1))()
+        N.check(self.lib.sacx_vcritic_end(self.h, out), self.h, "vcritic_end")
+        return dict(critic_loss=[np.float32(out[k]) for k in range(int(self.cfg.vcritics))], n_steps=int(out[N.MAX_MODELS]))
+
+    def vcritic_stats(self, n_last: int) -> np.ndarray:
+        """Last n_last rows of the critic step statistics ring (_native.VC_STAT_NAMES), oldest first."""
+        seq = int(self.v["vc.ctl"][0, 0].item())
+        cap = self.cfg.stats_capacity
+        st = self.v["vc.stats"].cpu().numpy()
+        return st[[(seq - n_last + i) % cap for i in range(n_last)]]
+
+    def vcritic_plan_info(self, mb: int) -> List[dict]:
+        """The launches of one critic step of mb rows per critic."""
+        n = ctypes.c_int32()
+        N.check(self.lib.sacx_vcritic_plan_info(self.h, int(mb), None, 0, ctypes.byref(n)), self.h, "vcritic_plan_info")
+        arr = (N.LaunchInfo * n.value)()
+        N.check(self.lib.sacx_vcritic_plan_info(self.h, int(mb), arr, n.value, ctypes.byref(n)), self.h, "vcritic_plan_info")
         return [dict(name=a.name.decode(), kernel=a.kernel.decode(), grid=a.grid, block=a.block,
                      flops=a.flops, bytes=a.bytes) for a in arr]
 

@@ -26,28 +26,45 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
 def kernel_scratch(so_path):
-    """{kernel symbol: private segment bytes per lane} of the gfx950 code object in so_path."""
+    """{kernel symbol: private segment bytes per lane} of the gfx950 code objects in so_path: every
+    offload bundle of its .hip_fatbin section (one per translation unit with kernels; the bundler
+    reads only the first of a file, so the section is cut at each bundle's magic)."""
+    out, spills = {}, {}
     with tempfile.TemporaryDirectory() as d:
-        fat, dev = os.path.join(d, "fat.bin"), os.path.join(d, "dev.o")
+        fat = os.path.join(d, "fat.bin")
         subprocess.check_call([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", so_path,
                                os.path.join(d, "copy.so")])
-        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={dev}"])
-        notes = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", dev], text=True)
-    out, spills, name = {}, {}, None
-    for line in notes.splitlines():
-        m = re.match(r"\s*\.name:\s+(\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.match(r"\s*\.private_segment_fixed_size:\s+(\d+)", line)
-        if m and name:
-            out[name] = int(m.group(1))
-        m = re.match(r"\s*\.vgpr_spill_count:\s+(\d+)", line)
-        if m and name:
-            spills[name] = int(m.group(1))
+        blob = open(fat, "rb").read()
+        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
+        for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(blob)])):
+            part, dev = os.path.join(d, f"fat{i}.bin"), os.path.join(d, f"dev{i}.o")
+            with open(part, "wb") as fh:
+                fh.write(blob[a:b])
+            subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
+                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={part}", f"--output={dev}"])
+            notes = subprocess.check_output([f"{LLVM}/llvm-readelf", "--notes", dev], text=True)
+            name = None
+            for line in notes.splitlines():
+                m = re.match(r"\s*\.name:\s+(\S+)", line)
+                if m:
+                    name = m.group(1)
+                m = re.match(r"\s*\.private_segment_fixed_size:\s+(\d+)", line)
+                if m and name:
+                    out[name] = int(m.group(1))
+                m = re.match(r"\s*\.vgpr_spill_count:\s+(\d+)", line)
+                if m and name:
+                    spills[name] = int(m.group(1))
     kernel_scratch.spills = spills
+    kernel_scratch.bundles = len(starts)
     return out
+
+
+# every translation unit with kernels must be among what was read: one name of each
+REQUIRED = ("k_gemm", "k_vc_gather", "k_gae_apply")
 
 
 def main():
@@ -61,8 +78,12 @@ def main():
     spilled = {k: v for k, v in kernel_scratch.spills.items() if v > max_spill}
     for k, v in sorted(spilled.items()):
         print(f"{v} VGPRs spilled > {max_spill}: {k}")
-    print(f"check_scratch: {len(sizes)} kernels, {len(bad)} over {limit} B/lane, {len(spilled)} spilling > {max_spill} VGPRs")
-    return 1 if bad or spilled or not sizes else 0
+    missing = [r for r in REQUIRED if not any(r in k for k in sizes)]
+    for r in missing:
+        print(f"no kernel named {r} among those read: a translation unit's code object was not checked")
+    print(f"check_scratch: {len(sizes)} kernels in {kernel_scratch.bundles} code objects, {len(bad)} over {limit} B/lane, "
+          f"{len(spilled)} spilling > {max_spill} VGPRs")
+    return 1 if bad or spilled or not sizes or missing else 0
 
 
 if __name__ == "__main__":
