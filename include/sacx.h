@@ -61,6 +61,14 @@ enum sacx_role { SACX_ROLE_WORK = 0, SACX_ROLE_PARAM = 1, SACX_ROLE_TARGET = 2, 
 #define SACX_EXPERT_OFF 0
 #define SACX_EXPERT_EO 1
 #define SACX_EXPERT_BC 2
+/* SACX_EXPERT_MODELS (MBRLOnPolicyAlg, mbrl_onpolicy_alg.py + base_onpolicy_alg.py): the world models and
+   everything that serves them -- the nets m<k>, mnorm.*, sacx_model_fit, sacx_model_forward / _sample /
+   _loss / _losses_eval, sacx_rollout, sacx_sim_collect -- beside a PPO-trained GaussianActor and its
+   VCritics, with no expert term and no SAC / BC plan.  Only with actor_gaussian ==
+   SACX_ACTOR_GAUSSIAN_TRAIN; expert_batch / expert_capacity are not used (pass 0); sacx_expert_set,
+   sacx_perm_push and sacx_expert_diag fail on it.  The replay ring holds the env data
+   (sacx_buffer_append); the rollout's actor step is GaussianActor.sample (see sacx_rollout). */
+#define SACX_EXPERT_MODELS 3
 
 /* sacx_config.actor_gaussian.
    SACX_ACTOR_GAUSSIAN_TRAIN: a plain (unsquashed) GaussianActor that is trained on-policy by the PPO
@@ -72,7 +80,7 @@ enum sacx_role { SACX_ROLE_WORK = 0, SACX_ROLE_PARAM = 1, SACX_ROLE_TARGET = 2, 
    ("ppo.stats": loss, mean entropy, grad_norm_pre, grad_norm_post, alpha, the surrogate mean, the
    minibatch advantage std + 1e-8, the step number).  It acts as a SACX_ACTOR_GAUSSIAN handle does.
    Refused at sacx_create: actor_output_norm (no backward is built for it), gemm_bf16, seeds > 1,
-   use_expert != 0; sacx_dp_init / sacx_dp_init_local fail on it.  sacx_sac_step and
+   use_expert SACX_EXPERT_EO / _BC (SACX_EXPERT_MODELS adds the world models); sacx_dp_init / sacx_dp_init_local fail on it.  sacx_sac_step and
    sacx_actor_evaluate fail on it as on a SACX_ACTOR_GAUSSIAN handle. */
 #define SACX_ACTOR_SQUASHED 0
 #define SACX_ACTOR_GAUSSIAN 1
@@ -95,7 +103,7 @@ typedef struct sacx_config {
     int32_t batch;              /* --sac_batch_size */
     int64_t buffer_capacity;    /* --env_buffer_size (ring capacity, rows) */
     int32_t per_state_std;      /* --actor_per_state_std */
-    int32_t use_expert;         /* SACX_EXPERT_OFF / _EO (alg_type sac_imit) / _BC (alg_type bc), below */
+    int32_t use_expert;         /* SACX_EXPERT_OFF / _EO (alg_type sac_imit) / _BC (alg_type bc) / _MODELS (mbrl) */
     int32_t expert_capacity;    /* --expert_buffer_size */
     int32_t expert_batch;       /* rows of expert data per update (even) */
     int32_t model_hidden[2];    /* --model_layers */
@@ -329,10 +337,34 @@ int sacx_model_loss(sacx_handle* h, int32_t model, const float* s, const float* 
  * (delta_n, r_n) = model([norm s_t, norm clip(a)]), clipped to +-delta_clip / +-reward_clip
  * when > 0 (--delta_clip_pred / --reward_clip_pred); a GaussianModel (ABI 7) then draws
  * normal(size=(n, S)) and adds exp(logstd) * u (GaussianModel.step, :36-54; n <= 4096);
- * s_{t+1} = s_t + delta_n*den + mean.  Requires use_expert (the models exist only then). */
+ * s_{t+1} = s_t + delta_n*den + mean.  Requires use_expert (the models exist only then).
+ * On a SACX_EXPERT_MODELS handle the actor step is GaussianActor.sample (continuous_actors.py:103-123,
+ * as sacx_actor_act has it: logstd_init, the log 1e-3 floor, per_state_std, layer norm): a_out gets
+ * the raw mean + exp(logstd) * u, and the model steps on actor.clip(a) = clip(a, -act_limit,
+ * act_limit) (samplers.py:93-95). */
 int sacx_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, int32_t horizon,
                  int32_t deterministic, float delta_clip, float reward_clip, float* s_out, float* a_out,
                  float* r_out, float* sp_out, uint8_t* d_out);
+/* One pass of MBRLOnPolicyAlg._collect_sim_data (mbrl_onpolicy_alg.py:89-93) on the device:
+ * idx = np.random.randint(rows_held, size=n_traj) from the device copy of the global stream
+ * (TrajectoryBuffer.get_states, buffers.py; the replay minibatch's integer draw with the bound = the
+ * rows now in the ring), s_init = the raw states of those ring rows in logical order (0 = the oldest
+ * row held, as s_all[idx] after the FIFO truncation), then sacx_rollout from them.  Outputs as
+ * sacx_rollout's ([n_traj, H, .], trajectory-major: the row order add_batch produces).  No host round
+ * trip: the draw rides in the first sampler launch ahead of step 0's normals and step 0's prep
+ * reads the indices, so the call adds at most one launch (the deterministic case's draw) to a
+ * sacx_rollout of the same shape.  Replays a captured graph per (model, shape, clips, pointers);
+ * SACX_ROLL_GRAPH=0 runs it eagerly.  Errors: an empty ring, n_traj / horizon < 0, n_traj > 65536,
+ * a GaussianModel with n_traj > 4096.  Requires use_expert. */
+int sacx_sim_collect(sacx_handle* h, int32_t model, int64_t n_traj, int32_t horizon, int32_t deterministic,
+                     float delta_clip, float reward_clip, float* s_out, float* a_out, float* r_out, float* sp_out,
+                     uint8_t* d_out);
+/* get_losses_eval (continuous_models.py:304-319, :133-148) of world model `model` on s, sp [n,S],
+ * a [n,A], r [n], from one forward (clip=False): out[0] = mean_i 0.5||norm(sp-s) - delta_pred||^2
+ * (a GaussianModel's predicted mean: the same plain squared error), out[1] = mean_i 0.5 (norm(r) -
+ * r_pred)^2.  out: DEVICE float[2].  Requires use_expert. */
+int sacx_model_losses_eval(sacx_handle* h, int32_t model, const float* s, const float* sp, const float* a,
+                           const float* r, int64_t n, float* out);
 /* Expert diagnostics on the device, n <= 2048 expert rows (device).
  * flags = 0: model_MSE_on_expert_data and _counterfactual_action (SAC_expert.py:579-608):
  *   out[0] = mean over the nm models of mean_i 0.5||model.sample(s_e, a_e) - sp_e||^2,
@@ -503,6 +535,9 @@ int sacx_dp_local_step(sacx_handle* const* handles, int32_t nranks, int64_t n_st
  * speculatively by the preceding sacx_actor_act_host (the drop-in loop's cadence act -> step ->
  * append of SAC_expert.py:779-797); the other steps drew their own.  -1 for a NULL handle. */
 int64_t sacx_spec_hits(const sacx_handle* h);
+/* Kernel launches of the sacx_rollout / sacx_sim_collect graph this handle captured last (0 before the
+ * first capture; a replayed call captures nothing).  -1 for a NULL handle. */
+int64_t sacx_rollout_launches(const sacx_handle* h);
 int sacx_plan_info(const sacx_handle* h, sacx_launch_info* out, int32_t cap, int32_t* n_out);
 /* The launches of one world-model fitting step (sacx_model_fit) of the selected seed, as
  * sacx_plan_info (use_expert handles; *n_out = 0 before the first sacx_model_fit builds them). */

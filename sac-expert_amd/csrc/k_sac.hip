@@ -4213,7 +4213,7 @@ __device__ __forceinline__ void actor_head_body(const HeadArgs& h, const FinalAr
         const float u_pf = bload(rs(sg.noise), boff(jok, (row - sg.r0) * A + lane));
         const float ls_pf = bload(rs(sr(h.logstd, so)), boff(jok && !h.per_state_std, lane));
         // sample segments (mode 1) feed the world models: their normaliser for the action columns
-        const bool msg = sg.mode == 1 && h.ma_mean != nullptr;
+        const bool msg = (sg.mode == 1 || sg.mode == 2) && h.ma_mean != nullptr;
         const float am_pf = bload(rs(sr(msg ? h.ma_mean : h.a_mean, so)), boff(jok, lane));
         const float ad_pf = bload(rs(sr(msg ? h.ma_den : h.a_den, so)), boff(jok, lane));
         const float bmu = bload(rW, boff(jok, h.H1 * Aout + lane));
@@ -4263,6 +4263,11 @@ __device__ __forceinline__ void actor_head_body(const HeadArgs& h, const FinalAr
                 l = fmaxf(l + h.logstd_init, logf(1e-3f));
                 const float a = m + expf(l) * u_pf;
                 if (sg.pi_out != nullptr) sg.pi_out[(size_t)(row - sg.r0) * A + lane] = a;
+                // the model-based rollout (samplers.py:93-95): the model steps on actor.clip(a)
+                // (continuous_actors.py:125-127), normalised into its input's action columns
+                if (sg.xq_out != nullptr)
+                    sg.xq_out[(size_t)(sg.xq_row0 + row - sg.r0) * h.ldQ + h.S + lane] =
+                        (fminf(fmaxf(a, -h.lim), h.lim) - am_pf) / ad_pf;
             }
             return;
         }
@@ -5570,9 +5575,17 @@ __global__ __launch_bounds__(256) void k_roll(RollArgs g) {
     const int64_t o = (int64_t)i * g.H + g.t;
     if (g.mode == 0) {
         const float* src = (g.t == 0 && g.s_init) ? g.s_init + (int64_t)i * S : g.s_out + o * S;
+        if (g.t == 0 && g.idx != nullptr) {
+            // sacx_sim_collect: s_init = the ring's row idx[i] in logical order (0 = the oldest held;
+            // TrajectoryBuffer.get_states, s_all[idx]); an index outside the rows held reads row 0
+            int64_t li = g.idx[i];
+            if (li < 0 || li >= g.ctl->cur_size) li = 0;
+            src = g.replay + ((g.ctl->start + li) % g.cap) * (int64_t)g.stride;
+        }
+        const bool first = g.t == 0 && (g.s_init || g.idx);
         for (int j = lane; j < S; j += 64) {
             const float v = src[j];
-            if (g.t == 0 && g.s_init) g.s_out[o * S + j] = v;
+            if (first) g.s_out[o * S + j] = v;
             g.X[(int64_t)i * g.ldS + j] = (v - g.s_mean[j]) / g.s_den[j];
             g.Xm[(int64_t)i * g.ldQ + j] = (v - g.ms_mean[j]) / g.ms_den[j];
         }
@@ -5613,7 +5626,10 @@ void launch_roll(const RollArgs& a, hipStream_t s) {
 //           r = r_rms.denormalize(r_n); one wave per row;
 //   mode 3: MSEModel.get_loss (continuous_models.py:280-302) over a chunk of rows, one
 //           workgroup; the chunk sums chain through out0 in stream order, the last chunk
-//           writes reduce_mean to out1.
+//           writes reduce_mean to out1;
+//   mode 4: get_losses_eval (continuous_models.py:304-319, :133-148): mode 3's pass with no clip and
+//           the plain squared error, the delta and the reward sums kept apart (out0[0], out0[1]);
+//           the last chunk writes the two means to out1[0], out1[1].
 __global__ __launch_bounds__(256) void k_net_io_elem(NetIOArgs g) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g.mode == 0) {
@@ -5656,6 +5672,7 @@ __global__ __launch_bounds__(256) void k_net_io_rows(NetIOArgs g) {
     // mode 3: 0.5 ||clip(norm(sp - s)) - delta_pred||^2 + coef * 0.5 (clip(norm(r)) - r_pred)^2
     // (GaussianModel: ds * 0.5 sum_j (((dn - pred) / e^l)^2 + 2 l + log 2 pi), continuous_models.py:111-129)
     __shared__ float part[4];
+    __shared__ float part_r[4];
     float ds = 1.f;
     if (g.mlogstd != nullptr && g.lscale) {      // stop_gradient(reduce_mean(square(exp(logstd))))
         float q2 = 0.f;
@@ -5665,7 +5682,7 @@ __global__ __launch_bounds__(256) void k_net_io_rows(NetIOArgs g) {
         }
         ds = wave_sum(q2) / (float)S;
     }
-    float acc = 0.f;
+    float acc = 0.f, acc_r = 0.f;
     for (int64_t i = wave; i < g.n; i += 4) {
         const float* Oi = g.O + i * g.ldO;
         float sq = 0.f;
@@ -5684,11 +5701,30 @@ __global__ __launch_bounds__(256) void k_net_io_rows(NetIOArgs g) {
         float rn = (g.r[i] - g.r_norm[0]) / g.r_norm[1];
         if (g.clip_r > 0.f) rn = fminf(fmaxf(rn, -g.clip_r), g.clip_r);
         const float er = rn - Oi[S];
-        acc = acc + (0.5f * tot + g.reward_coef * (0.5f * (er * er)));
+        if (g.mode == 4) {
+            acc = acc + 0.5f * tot;
+            acc_r = acc_r + 0.5f * (er * er);
+        } else {
+            acc = acc + (0.5f * tot + g.reward_coef * (0.5f * (er * er)));
+        }
     }
-    if (lane == 0) part[wave] = acc;
+    if (lane == 0) {
+        part[wave] = acc;
+        part_r[wave] = acc_r;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && g.mode == 4) {
+        const float sum = (part[0] + part[1]) + (part[2] + part[3]);
+        const float sum_r = (part_r[0] + part_r[1]) + (part_r[2] + part_r[3]);
+        const float run = g.first ? sum : g.out0[0] + sum;
+        const float run_r = g.first ? sum_r : g.out0[1] + sum_r;
+        g.out0[0] = run;
+        g.out0[1] = run_r;
+        if (g.last) {
+            g.out1[0] = run / (float)g.n_total;
+            g.out1[1] = run_r / (float)g.n_total;
+        }
+    } else if (threadIdx.x == 0) {
         const float sum = (part[0] + part[1]) + (part[2] + part[3]);
         const float run = g.first ? sum : g.out0[0] + sum;
         g.out0[0] = run;

@@ -158,6 +158,8 @@ struct sacx_handle {
     bool deep = false;        // a net of other than 2 hidden layers: the generic plans (build_plan_generic)
     bool wide = false;        // a used net has a hidden layer above 512 (sets deep): no fold, no k_fwd2, no ROWK
                               // variant takes such a row -- the per-layer GEMMs and the wide row kernels do
+    int64_t roll_nodes = 0;   // launches of the rollout / sim_collect graph captured last
+    bool models_only = false; // use_expert == SACX_EXPERT_MODELS: world models beside the PPO-trained actor, no expert rows
     bool bc = false;          // use_expert == SACX_EXPERT_BC: the actor-only imitation update (build_plan_bc)
     // world-model variants (ABI 7): GaussianModel (a logstd per model, the NLL fit loss, noise in
     // sample / step) and --separate_reward_nn (a reward net r<k> beside each model net m<k>)
@@ -396,6 +398,7 @@ constexpr int MFIT_GRAPH = 64;      // model-fit steps per captured graph (then 
 static_assert(MFIT_GRAPH <= MFIT_PRE, "a fit graph's steps fit one pre-gather block");
 constexpr int STAGE_CAP = SACX_STAGE_FLOATS;   // floats in the pinned host staging buffer of the _host entry points
 constexpr int ROLL_CAP = 4096;  // trajectories per sacx_rollout launch chain
+constexpr int SIM_IDX_CAP = 65536;  // trajectories per sacx_sim_collect call (the index draw's buffer)
 
 void build_layout(sacx_handle* h) {
     const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, B = h->B;
@@ -722,6 +725,8 @@ void build_layout(sacx_handle* h) {
         h->add("roll.M1", RR, h->deep ? wmax(2) : Hm0, F, 0);
         h->add("roll.M2", RR, h->deep ? wmax(2) : Hm1, F, 0);
         h->add("roll.O", RR, O, F, 0);
+        // sacx_sim_collect's drawn ring rows (only the new handle kind: the others keep their layout)
+        if (h->models_only) h->add("roll.idx", 1, SIM_IDX_CAP, SACX_I32, 0);
     }
     // the middle hidden layers (1 .. D-2) of nets deeper than two layers: <p>m<i>
     for (const Mid& m : mids)
@@ -3475,8 +3480,12 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     if (cfg->batch <= 0 || cfg->buffer_capacity <= 0) return bad("batch/buffer_capacity must be positive");
     if (cfg->buffer_capacity >= (int64_t(1) << 31)) return bad("buffer_capacity must be < 2^31");
     if (cfg->num_models < 0 || cfg->num_models > SACX_MAX_MODELS) return bad("num_models must be in [1, 8] (0 -> 2)");
-    if (cfg->use_expert < SACX_EXPERT_OFF || cfg->use_expert > SACX_EXPERT_BC)
-        return bad("use_expert must be SACX_EXPERT_OFF, SACX_EXPERT_EO or SACX_EXPERT_BC");
+    if (cfg->use_expert < SACX_EXPERT_OFF || cfg->use_expert > SACX_EXPERT_MODELS)
+        return bad("use_expert must be SACX_EXPERT_OFF, SACX_EXPERT_EO, SACX_EXPERT_BC or SACX_EXPERT_MODELS");
+    const bool models_only = cfg->use_expert == SACX_EXPERT_MODELS;
+    if (models_only && cfg->actor_gaussian != SACX_ACTOR_GAUSSIAN_TRAIN)
+        return bad("use_expert = SACX_EXPERT_MODELS (world models without an expert term) goes with "
+                   "actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN only");
     if (cfg->use_expert == SACX_EXPERT_BC) {
         if (cfg->gemm_bf16) return bad("BC (use_expert = SACX_EXPERT_BC) runs fp32 only (gemm_bf16 = 0)");
         if (cfg->seeds > 1) return bad("BC (use_expert = SACX_EXPERT_BC) runs one learner per handle (seeds <= 1)");
@@ -3490,23 +3499,25 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
         if (cfg->gemm_bf16) return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN) runs fp32 only (gemm_bf16 = 0)");
         if (cfg->seeds > 1)
             return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN) runs one learner per handle (seeds <= 1)");
-        if (cfg->use_expert)
+        if (cfg->use_expert && !models_only)
             return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN): use_expert must be SACX_EXPERT_OFF "
-                       "(the expert_reg branch of the PPO step is not built)");
+                       "or SACX_EXPERT_MODELS (the expert_reg branch of the PPO step is not built)");
         if (cfg->buffer_capacity > (int64_t(1) << 24))
             return bad("trainable GaussianActor (SACX_ACTOR_GAUSSIAN_TRAIN): buffer_capacity (rollout rows) must be <= 2^24");
     }
     if (cfg->use_expert) {
         const int nmc = cfg->num_models > 0 ? cfg->num_models : 2;
-        if (cfg->expert_batch <= 0) return bad("expert_batch must be positive");
-        // the expert term adds model 0's and model 1's rows elementwise (SAC_expert.py:329-332): the
-        // first two sections of np.array_split(perm, num_models) must hold the same number of rows
-        if (nmc == 2 && (cfg->expert_batch & 1))
-            return bad("expert_batch must be even with 2 models (SAC_expert.py:329-332 adds equal halves)");
-        if (nmc > 2 && cfg->expert_batch % nmc == 1)
-            return bad("expert_batch % num_models == 1: the two array_split sections of the expert term differ in length");
-        if (nmc >= 2 && cfg->expert_batch < nmc) return bad("expert_batch < num_models");
-        if (cfg->expert_capacity < cfg->expert_batch) return bad("expert_capacity < expert_batch");
+        if (!models_only) {               // (SACX_EXPERT_MODELS: no expert rows, expert_batch / expert_capacity unused)
+            if (cfg->expert_batch <= 0) return bad("expert_batch must be positive");
+            // the expert term adds model 0's and model 1's rows elementwise (SAC_expert.py:329-332): the
+            // first two sections of np.array_split(perm, num_models) must hold the same number of rows
+            if (nmc == 2 && (cfg->expert_batch & 1))
+                return bad("expert_batch must be even with 2 models (SAC_expert.py:329-332 adds equal halves)");
+            if (nmc > 2 && cfg->expert_batch % nmc == 1)
+                return bad("expert_batch % num_models == 1: the two array_split sections of the expert term differ in length");
+            if (nmc >= 2 && cfg->expert_batch < nmc) return bad("expert_batch < num_models");
+            if (cfg->expert_capacity < cfg->expert_batch) return bad("expert_capacity < expert_batch");
+        }
         if (cfg->model_activation < 0 || cfg->model_activation > 2) return bad("model activation invalid");
         if (cfg->s_dim + 1 > 512) return bad("s_dim > 511 unsupported by the model MSE head");
     }
@@ -3572,11 +3583,12 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
     h->macts[0] = nd[2].act.front(); h->macts[1] = nd[2].act.back();
     h->Aout = cfg->per_state_std ? 2 * h->A : h->A;
     h->nm = cfg->use_expert ? (cfg->num_models > 0 ? cfg->num_models : 2) : 0;
-    h->ne_perm = cfg->use_expert ? cfg->expert_batch : 0;
+    h->ne_perm = cfg->use_expert && !models_only ? cfg->expert_batch : 0;
     // the update's expert rows: every row with one model, else the first two array_split sections
     // (each ceil(ne / nm) rows here: their lengths agree, checked above)
     h->ne = h->nm <= 1 ? h->ne_perm : 2 * ((h->ne_perm + h->nm - 1) / h->nm);
-    h->ecap = cfg->use_expert ? cfg->expert_capacity : 0;
+    h->ecap = cfg->use_expert && !models_only ? cfg->expert_capacity : 0;
+    h->models_only = models_only;
     h->Hm0 = cfg->use_expert ? nd[2].h.front() : 0;
     h->Hm1 = cfg->use_expert ? nd[2].h.back() : 0;
     h->gm = cfg->use_expert && cfg->gaussian_model;
@@ -4297,6 +4309,7 @@ int sacx_expert_set(sacx_handle* h, const float* s_e, const float* sp_e, int32_t
     if (!h || !h->bound) return fail(h, "not bound");
     if (settle(h)) return -1;             // alpha.final reads the epsilon this sets
     if (!h->cfg.use_expert) return fail(h, "handle was created without use_expert");
+    if (h->models_only) return fail(h, "use_expert = SACX_EXPERT_MODELS: the handle holds no expert rows (sacx_expert_set)");
     if (n != h->ne_perm) return fail(h, "expert rows must equal expert_batch");
     const size_t bytes = sizeof(float) * (size_t)n * h->S;
     HIPCHK(h, hipMemcpyAsync(h->f("expert.s"), s_e, bytes, hipMemcpyDeviceToDevice, h->stream));
@@ -4312,6 +4325,7 @@ int sacx_expert_set(sacx_handle* h, const float* s_e, const float* sp_e, int32_t
 int sacx_perm_push(sacx_handle* h, const int32_t* perms, int64_t n_steps) {
     if (!h || !h->bound) return fail(h, "not bound");
     if (!h->cfg.use_expert) return 0;
+    if (h->models_only) return fail(h, "use_expert = SACX_EXPERT_MODELS: no expert permutations (sacx_perm_push)");
     if (n_steps > h->perm_cap) return fail(h, "n_steps exceeds perm_capacity");
     int32_t* ring = h->ptr<int32_t>("perm");
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -4585,6 +4599,8 @@ int sacx_sync(sacx_handle* h) {
 }
 
 int64_t sacx_spec_hits(const sacx_handle* h) { return h ? h->spec_hits : -1; }
+
+int64_t sacx_rollout_launches(const sacx_handle* h) { return h ? h->roll_nodes : -1; }
 
 static int launch_info(const std::vector<Launch>& plan, sacx_launch_info* out, int32_t cap, int32_t* n_out);
 
@@ -4956,10 +4972,24 @@ int sacx_model_loss(sacx_handle* h, int32_t model, const float* s, const float* 
     return 0;
 }
 
+static int run_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, int32_t horizon,
+                       int32_t deterministic, float delta_clip, float reward_clip, float* s_out, float* a_out,
+                       float* r_out, float* sp_out, uint8_t* d_out);
 // the launches of one rollout call on stream st (eager, or captured by sacx_rollout)
+// s_init == nullptr (sacx_sim_collect): the n start states are the ring rows np.random.randint(rows held,
+// size=n) names -- the draw rides in the first sampler launch, ahead of step 0's normals (alone when
+// deterministic), and step 0's prep reads the indices
 static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, int32_t horizon,
                      int32_t deterministic, float delta_clip, float reward_clip, float* s_out, float* a_out,
                      float* r_out, float* sp_out, uint8_t* d_out, hipStream_t st) {
+    const bool collect = s_init == nullptr;
+    auto draw = [&](int n_int, int n_norm, float* noise) {
+        RngArgs r{};
+        r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
+        r.n_int = n_int; r.n_norm = n_norm; r.out_idx = n_int ? h->ptr<int32_t>("roll.idx") : nullptr; r.out_norm = noise;
+        r.slot = -1; r.reset_seq = 0; r.nupd = 1;
+        launch_rng(r, st);
+    };
     const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS, ldQ = h->ldQ;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     const std::string mn = "m" + std::to_string(model);
@@ -4970,7 +5000,7 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
             const int m = (int)std::min<int64_t>(ROLL_CAP, n - c0);
             RollArgs ra{};
             ra.n = m; ra.S = S; ra.A = A; ra.H = horizon; ra.t = t; ra.ldS = ldS; ra.ldQ = ldQ;
-            ra.s_init = s_init + c0 * S;
+            ra.s_init = collect ? nullptr : s_init + c0 * S;
             ra.s_out = s_out + c0 * horizon * S; ra.a_out = a_out + c0 * horizon * A;
             ra.r_out = r_out + c0 * horizon; ra.sp_out = sp_out + c0 * horizon * S; ra.d_out = d_out + c0 * horizon;
             ra.O = W("roll.O"); ra.a_raw = W("roll.A"); ra.X = W("roll.X"); ra.Xm = W("roll.Xm");
@@ -4983,15 +5013,19 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
                 ra.mnoise = W("roll.mnoise");
             }
             ra.mode = 0;
-            launch_roll(ra, st);
             float* noise = deterministic ? nullptr : W("roll.noise");
-            if (!deterministic) {      // actor.sample: u = np.random.normal(size=(m, A))
-                RngArgs r{};
-                r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
-                r.n_int = 0; r.n_norm = m * A; r.out_idx = nullptr; r.out_norm = noise;
-                r.slot = -1; r.reset_seq = 0; r.nupd = 1;
-                launch_rng(r, st);
+            const bool first = collect && t == 0 && c0 == 0;
+            if (collect && t == 0) {
+                ra.idx = h->ptr<int32_t>("roll.idx") + c0; ra.replay = W("replay"); ra.cap = h->cap;
+                ra.stride = h->stride; ra.ctl = h->ctl();
+                // all n indices, then this chunk's normals, in the reference's order (get_states before
+                // the first actor.sample); the prep reads them, so it follows the draw here
+                if (first) draw((int)n, deterministic ? 0 : m * A, noise);
             }
+            launch_roll(ra, st);
+            ra.idx = nullptr;
+            // actor.sample: u = np.random.normal(size=(m, A))
+            if (!deterministic && !first) draw(0, m * A, noise);
             HeadArgs a{};
             a.H2 = actor_hidden(h, W("roll.X"), ldS, m, W("roll.H1"), W("roll.H2"), st);
             a.ldh = H1; a.W3 = W(actor_head_name(h)); a.logstd = W("actor.logstd");
@@ -5002,6 +5036,14 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
             // sample(): raw action to roll.A, normalised clip(a) (= a: |lim tanh| <= lim) into
             // the action columns of the model input
             a.seg[0] = {0, m, 1, 0, noise, W("roll.Xm"), nullptr, W("roll.A")};
+            if (h->models_only) {
+                // GaussianActor.sample (continuous_actors.py:103-123; mode 2 as sacx_actor_act has it): the
+                // raw action to roll.A, the normalised actor.clip(a) into the model input
+                a.seg[0].mode = 2;
+                const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+                a.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+                a.output_norm = h->cfg.actor_output_norm;
+            }
             a.total_rows = m;
             a.cache_row0 = 1 << 30;
             a.alpha_mode = 0;
@@ -5027,6 +5069,58 @@ int sacx_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, 
     if (h->gm && n > ROLL_CAP)   // one step's draws: the actor's (n, A), then the model's (n, S)
         return fail(h, "GaussianModel rollout: at most 4096 trajectories per call (the draws of a step interleave)");
     if (settle(h)) return -1;
+    return run_rollout(h, model, s_init, n, horizon, deterministic, delta_clip, reward_clip, s_out, a_out, r_out,
+                       sp_out, d_out);
+}
+
+int sacx_sim_collect(sacx_handle* h, int32_t model, int64_t n, int32_t horizon, int32_t deterministic,
+                     float delta_clip, float reward_clip, float* s_out, float* a_out, float* r_out, float* sp_out,
+                     uint8_t* d_out) {
+    if (!h || !h->bound) return fail(h, "not bound");
+    if (!h->cfg.use_expert) return fail(h, "sim_collect needs the world models (use_expert)");
+    if (!h->models_only)
+        return fail(h, "sim_collect: a use_expert = SACX_EXPERT_MODELS handle only (the ring holds the env data there)");
+    if (model < 0 || model >= h->nm) return fail(h, "model index out of range (num_models)");
+    if (n < 0 || horizon < 0) return fail(h, "sim_collect: n_traj and horizon must be >= 0");
+    if (n > SIM_IDX_CAP) return fail(h, "sim_collect: at most 65536 trajectories per call");
+    if (h->gm && n > ROLL_CAP)   // one step's draws: the actor's (n, A), then the model's (n, S)
+        return fail(h, "GaussianModel rollout: at most 4096 trajectories per call (the draws of a step interleave)");
+    if (flush_append(h)) return -1;
+    if (settle(h)) return -1;
+    if (h->cur_size_host <= 0) return fail(h, "sim_collect: the replay ring is empty (np.random.randint(0) raises)");
+    if (n == 0 || horizon == 0) return 0;
+    if (!s_out || !a_out || !r_out || !sp_out || !d_out) return fail(h, "null output");
+    return run_rollout(h, model, nullptr, n, horizon, deterministic, delta_clip, reward_clip, s_out, a_out, r_out,
+                       sp_out, d_out);
+}
+
+int sacx_model_losses_eval(sacx_handle* h, int32_t model, const float* s, const float* sp, const float* a,
+                           const float* r, int64_t n, float* out) {
+    if (!h || !h->bound) return fail(h, "not bound");
+    if (settle(h)) return -1;
+    if (!h->cfg.use_expert) return fail(h, "the world models exist only with use_expert");
+    if (model < 0 || model >= h->nm) return fail(h, "model index out of range (num_models)");
+    if (n <= 0 || !s || !sp || !a || !r || !out) return fail(h, "bad arguments");
+    const int S = h->S, A = h->A;
+    for (int64_t done = 0; done < n; done += ROLL_CAP) {
+        const int m = (int)std::min<int64_t>(ROLL_CAP, n - done);
+        model_net_chunk(h, model, s + done * S, a + done * A, m);      // _forward(s, a, clip=False)
+        NetIOArgs g = netio_base(h, true);
+        g.mode = 4; g.n = m; g.s = s + done * S; g.sp = sp + done * S; g.r = r + done;
+        g.O = h->f("roll.O"); g.ldO = S + 1;
+        g.out0 = h->f("roll.noise");           // the two running sums (workspace; ROLL_CAP * A >= 2 floats)
+        g.out1 = out;
+        g.first = done == 0; g.last = done + m >= n; g.n_total = n;
+        launch_net_io(g, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+// runs (or replays) the rollout's launches; s_init == nullptr: sacx_sim_collect
+static int run_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, int32_t horizon,
+                       int32_t deterministic, float delta_clip, float reward_clip, float* s_out, float* a_out,
+                       float* r_out, float* sp_out, uint8_t* d_out) {
     // one captured graph per (model, shape, clips, pointers): the Python host keeps its
     // staging / output buffers per shape, so repeated calls replay (SACX_ROLL_GRAPH=0: eager)
     const char* rg = std::getenv("SACX_ROLL_GRAPH");
@@ -5046,6 +5140,8 @@ int sacx_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, 
                         sp_out, d_out, h->cap_stream);
         hipGraph_t g;
         HIPCHK(h, hipStreamEndCapture(h->cap_stream, &g));
+        size_t nodes = 0;                           // every node is a kernel launch (sacx_rollout_launches)
+        if (hipGraphGetNodes(g, nullptr, &nodes) == hipSuccess) h->roll_nodes = (int64_t)nodes;
         const hipError_t e = hipGraphInstantiateWithFlags(&ge, g, 0);
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return fail(h, std::string("rollout graph: ") + hipGetErrorString(e));
@@ -5063,6 +5159,7 @@ int sacx_expert_diag(sacx_handle* h, const float* s_e, const float* a_e, const f
                      int32_t flags, float delta_clip, float* out) {
     if (!h || !h->bound) return fail(h, "not bound");
     if (!h->cfg.use_expert) return fail(h, "expert diagnostics need the world models (use_expert)");
+    if (h->models_only) return fail(h, "use_expert = SACX_EXPERT_MODELS: no expert term to diagnose (sacx_expert_diag)");
     if (n <= 0 || n > 2048) return fail(h, "expert rows must be in [1, 2048]");
     const bool disc = (flags & SACX_DIAG_DISC) != 0, ea = (flags & SACX_DIAG_EXPERT_ACTIONS) != 0;
     if (disc && h->nm < 2) return fail(h, "_calc_disc compares two world models (num_models >= 2)");

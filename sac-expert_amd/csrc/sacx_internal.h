@@ -283,7 +283,7 @@ struct QHeadArgs {
 struct HeadSeg {
     int32_t r0, r1;        // actor rows [r0, r1)
     int32_t mode;          // 0 = evaluate (neglogp), 1 = sample (no neglogp), 2 = GaussianActor.sample
-                           // (no squash; pi_out only)
+                           // (no squash; pi_out = the raw action, xq_out = the normalised clip(a))
     int32_t xq_row0;       // first row in xq_out
     const float* noise;    // [r1-r0, A]
     float* xq_out;         // normalised action -> xq_out[(xq_row0 + i) * ldQ + S + j]
@@ -616,7 +616,8 @@ struct AppendArgs {
 // what the reference method returns.
 struct NetIOArgs {
     int32_t mode;               // 0: prep [norm s | norm a | 0] -> X; 1: critic output; 2: model
-                                // output (sample / step); 3: model loss (get_loss) of a chunk
+                                // output (sample / step); 3: model loss (get_loss) of a chunk;
+                                // 4: get_losses_eval of a chunk (mode 3's pass, the two sums apart)
     int32_t n, S, A, ldX, ldO;
     const float *s, *a, *sp, *r;   // caller rows of this chunk (a nullable in mode 0)
     float* X;                      // mode 0: [n, ldX]
@@ -722,6 +723,9 @@ struct RollArgs {
     // GaussianModel.step (continuous_models.py:36-54): exp(mlogstd) * mnoise [n, S] added to the clipped
     // delta_n (mode 1); null: MSEModel
     const float* mlogstd; const float* mnoise;
+    // sacx_sim_collect (mode 0, t == 0; null: s_init): row i starts from the replay ring's logical row
+    // idx[i] (TrajectoryBuffer.get_states, s_all[np.random.randint(rows_held, size=n)])
+    const int32_t* idx; const float* replay; int64_t cap; int32_t stride; const Ctl* ctl;
 };
 
 // ---------------------------------------------------------------- expert diagnostics (F3)

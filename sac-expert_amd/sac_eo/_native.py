@@ -18,7 +18,7 @@ MAX_MODELS = 8                  # SACX_MAX_MODELS: --num_models
 STAGE_FLOATS = 65536            # SACX_STAGE_FLOATS (include/sacx.h)
 ACT = {"relu": 0, "tanh": 1, "elu": 2}
 DTYPES = {0: "f32", 1: "i32", 2: "i64", 3: "u32", 4: "f64"}
-EXPERT_OFF, EXPERT_EO, EXPERT_BC = 0, 1, 2      # sacx_config.use_expert (SACX_EXPERT_*)
+EXPERT_OFF, EXPERT_EO, EXPERT_BC, EXPERT_MODELS = 0, 1, 2, 3      # sacx_config.use_expert (SACX_EXPERT_*)
 ACTOR_SQUASHED, ACTOR_GAUSSIAN, ACTOR_GAUSSIAN_TRAIN = 0, 1, 2     # sacx_config.actor_gaussian (SACX_ACTOR_*)
 PPO_STAT_NAMES = ["loss", "ent", "grad_norm_pre", "grad_norm_post", "alpha", "pg_loss", "adv_std", "step"]
 GAE_TILE = 2048                 # rows per workgroup of the GAE scan (csrc/vcritic.h): tests place boundaries on it
@@ -44,6 +44,7 @@ EXPORTS = [
     "sacx_ppo_plan_info",
     "sacx_vcritic_init", "sacx_vcritic_value", "sacx_gae_values", "sacx_gae", "sacx_vcritic_loss", "sacx_vcritic_begin",
     "sacx_vcritic_steps", "sacx_vcritic_end", "sacx_vcritic_plan_info",
+    "sacx_sim_collect", "sacx_model_losses_eval", "sacx_rollout_launches",
 ]
 
 
@@ -180,6 +181,7 @@ def lib():
         "sacx_plan_info": (ctypes.c_int, [vp, P(LaunchInfo), i32, P(i32)]),
         "sacx_model_plan_info": (ctypes.c_int, [vp, P(LaunchInfo), i32, P(i32)]),
         "sacx_spec_hits": (i64, [vp]),
+        "sacx_rollout_launches": (i64, [vp]),
         "sacx_profile": (ctypes.c_int, [vp, i64, P(f64), i32]),
         "sacx_time_graph": (ctypes.c_int, [vp, i64, ctypes.c_char_p, P(f64)]),
         "sacx_actor_act": (ctypes.c_int, [vp, vp, i64, i32, vp]),
@@ -200,6 +202,8 @@ def lib():
         "sacx_dp_init_local": (ctypes.c_int, [vp, i32, i32]),
         "sacx_dp_local_step": (ctypes.c_int, [vp, i32, i64, i64, i32]),
         "sacx_rollout": (ctypes.c_int, [vp, i32, vp, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+        "sacx_sim_collect": (ctypes.c_int, [vp, i32, i64, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+        "sacx_model_losses_eval": (ctypes.c_int, [vp, i32, vp, vp, vp, vp, i64, vp]),
         "sacx_ppo_neglogp": (ctypes.c_int, [vp, vp, vp, i64, vp]),
         "sacx_ppo_dist": (ctypes.c_int, [vp, vp, i64, vp, vp, vp]),
         "sacx_ppo_kl": (ctypes.c_int, [vp, vp, vp, vp, i64, vp]),

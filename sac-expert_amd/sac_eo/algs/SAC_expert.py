@@ -20,7 +20,7 @@ import numpy as np
 from ..common.normalizer import RunningNormalizers
 from ..common.samplers import trajectory_sampler
 from ..engine import Engine, EngineConfig
-from .base import SACBase
+from .base import SACBase, epoch_minibatches
 
 
 class SAC_exp(SACBase):
@@ -205,19 +205,8 @@ class SAC_exp(SACBase):
                 np.random.shuffle(rows)
                 rows = rows[:n_train]
             for ep in range(self.model_num_epochs):
-                idx = np.arange(n_train)
-                nm = len(self.models)                 # self.B (SAC_expert.py:61)
-                if self.model_batch_shuffle:
-                    idx = np.tile(idx, (nm, 1))
-                    for row in idx:
-                        np.random.shuffle(row)
-                else:
-                    np.random.shuffle(idx)
-                    idx = np.tile(idx, (nm, 1))
-                sections = np.arange(0, n_train, self.model_batch_size)[1:]
-                parts = np.array_split(idx, sections, axis=1)
-                if n_train % self.model_batch_size != 0:
-                    parts = parts[:-1]
+                # (self.B models, SAC_expert.py:61; the draws shared with MBRLOnPolicyAlg._update_models)
+                parts = epoch_minibatches(n_train, len(self.models), self.model_batch_size, self.model_batch_shuffle)
                 for p in parts:
                     batches.append(p if rows is None else rows[p])
                     num_updates += 1

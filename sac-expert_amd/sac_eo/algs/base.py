@@ -20,6 +20,26 @@ from ..common.samplers import trajectory_sampler
 from ..engine import Engine, EngineConfig
 
 
+def epoch_minibatches(n_train, num_models, model_batch_size, model_batch_shuffle):
+    """One epoch's minibatch index draws of _update_models (mbrl_onpolicy_alg.py:216-230,
+    SAC_expert.py:519-531) from the global NumPy stream: a shuffle per model (or one shared with
+    --no_model_batch_shuffle), cut at multiples of model_batch_size, the short last part dropped.
+    -> list of [num_models, model_batch_size] index arrays.  Call under ``_host_rng``."""
+    idx = np.arange(n_train)
+    if model_batch_shuffle:
+        idx = np.tile(idx, (num_models, 1))
+        for row in idx:
+            np.random.shuffle(row)
+    else:
+        np.random.shuffle(idx)
+        idx = np.tile(idx, (num_models, 1))
+    sections = np.arange(0, n_train, model_batch_size)[1:]
+    parts = np.array_split(idx, sections, axis=1)
+    if n_train % model_batch_size != 0:
+        parts = parts[:-1]
+    return parts
+
+
 class SACBase:
     use_expert = False
 

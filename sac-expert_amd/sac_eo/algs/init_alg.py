@@ -16,5 +16,11 @@ def init_alg(idx, env, env_eval, env_expert, actor, critics, q_targets, q_critic
         return BC(idx, env, env_eval, env_expert, actor, expert, init_expert_rms_stats, critics, q_targets,
                   q_critics, models, alg_kwargs, mf_update_kwargs)
     if alg_type == "mbrl":
-        raise NotImplementedError(f"alg_type {alg_type!r} is outside the SAC / SAC-EO / BC path built here")
+        # the parser's default is 'trpo'; the reference's TRPO reads grad_final / epsilon, which exist only
+        # with expert_reg (trpo.py): there is nothing sound to port, so only PPO runs
+        mf_algo = alg_kwargs.get("mf_algo", "trpo")
+        if mf_algo != "ppo":
+            raise NotImplementedError(f"alg_type 'mbrl' with mf_algo {mf_algo!r}: TRPO is not built; pass --mf_algo ppo")
+        from .mbrl_onpolicy_alg import MBRLOnPolicyAlg
+        return MBRLOnPolicyAlg(idx, env, env_eval, actor, critics, models, alg_kwargs, mf_update_kwargs)
     raise ValueError("invalid alg_type")

@@ -20,7 +20,7 @@ import numpy as np
 
 from ...common.buffer_utils import aggregate_data
 from ...engine import Engine, EngineConfig
-from .ppo import minibatches
+from .ppo import _on_device, aggregate_rows, minibatches
 
 
 class VCriticUpdate:
@@ -100,8 +100,8 @@ class VCriticUpdate:
         """Updates critics (``base_onpolicy_alg.py:219-266``)."""
         s_all_list, _, _, rtg_all_list, _, _ = rollout_data_all
         if len(self.critics) != B:
-            s_all_list = [aggregate_data(s_all_list)]
-            rtg_all_list = [aggregate_data(rtg_all_list)]
+            s_all_list = [aggregate_rows(s_all_list)]           # (torch.cat for rows on the device)
+            rtg_all_list = [aggregate_rows(rtg_all_list)]
         if len(s_all_list) != len(self.critics):
             raise ValueError(f"VCriticUpdate: {len(s_all_list)} tables for {len(self.critics)} critics")
         n_samples = int(np.min([len(rtg_all) for rtg_all in rtg_all_list]))
@@ -113,7 +113,10 @@ class VCriticUpdate:
         eng = self.engine
         for k, (s_all, rtg_all) in enumerate(zip(s_all_list, rtg_all_list)):
             n = len(rtg_all)
-            eng.vcritic_begin(k, np.asarray(s_all, np.float32).reshape(n, -1), np.asarray(rtg_all, np.float32).reshape(n))
+            if _on_device(s_all):                          # CUDA rows: handed over without a host copy
+                eng.vcritic_begin(k, s_all.reshape(n, -1), rtg_all.reshape(n))
+            else:
+                eng.vcritic_begin(k, np.asarray(s_all, np.float32).reshape(n, -1), np.asarray(rtg_all, np.float32).reshape(n))
         with self._host_rng():                             # one np.random.shuffle per iteration (:235-242)
             parts = []
             for _ in range(self.critic_update_it):

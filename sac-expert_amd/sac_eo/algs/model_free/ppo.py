@@ -26,6 +26,20 @@ import numpy as np
 from ...engine import Engine, EngineConfig
 
 
+def _on_device(x):
+    """Whether x is a CUDA tensor (rows that are on the device already)."""
+    return hasattr(x, "is_cuda") and bool(x.is_cuda)
+
+
+def aggregate_rows(parts):
+    """aggregate_data (buffer_utils.py) for rows that may live on the device: torch.cat there."""
+    parts = list(parts)
+    if parts and _on_device(parts[0]):
+        import torch
+        return torch.cat(parts, 0)
+    return np.concatenate(parts, 0)
+
+
 def minibatches(n_samples, nminibatch, idx):
     """The split of ``ppo.py:48-62``: ``idx`` (a shuffled arange) cut at multiples of
     ``n_batch = int(n / nminibatch)``, the short last part dropped; -> [parts, n_batch]."""
@@ -135,15 +149,21 @@ class PPO:
         if expert_reg is not None:
             raise NotImplementedError("PPO.update: the expert_reg branch (ppo.py:148-223) is not built")
         s_all, a_all, adv_all, _, _, _ = rollout_data
-        s_all = np.asarray(s_all, np.float32)
+        # CUDA tensors (Engine.sim_collect / Engine.gae rows) go to ppo_begin as they are: no host copy
+        dev = _on_device(s_all)
+        if not dev:
+            s_all = np.asarray(s_all, np.float32)
         n = int(s_all.shape[0])
         n_batch = int(n / self.actor_nminibatch)
         if n_batch < 1:
             raise ValueError(f"PPO: {n} rollout rows give no minibatch with actor_nminibatch = {self.actor_nminibatch}")
         self._ensure_engine(n, n_batch)
         eng = self.engine
-        eng.ppo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, -1),
-                      np.asarray(adv_all, np.float32).reshape(n))
+        if dev:
+            eng.ppo_begin(s_all.reshape(n, -1), a_all.reshape(n, -1), adv_all.reshape(n))
+        else:
+            eng.ppo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, -1),
+                          np.asarray(adv_all, np.float32).reshape(n))
         with self._host_rng():                             # one np.random.shuffle per iteration (:55-62)
             parts = []
             for _ in range(self.actor_update_it):

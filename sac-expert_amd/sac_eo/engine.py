@@ -94,10 +94,19 @@ class EngineConfig:
     # Engine.vcritic_* / gae / gae_values.  A host-only field: Engine makes the handle's init call
     # right after creating it; 0 leaves the handle and its layout as they are
     vcritics: int = 0
+    # alg_type mbrl (MBRLOnPolicyAlg): the world models and everything that serves them (model_fit,
+    # model_forward / model_loss / model_losses_eval, rollout, sim_collect) beside the PPO-trained
+    # GaussianActor and its VCritics -- SACX_EXPERT_MODELS: no expert rows, no SAC / BC plan.  Needs
+    # actor_gaussian="train"; expert_capacity / expert_batch are not used
+    world_models: bool = False
 
     def __post_init__(self):
         if self.bc:
             self.use_expert = True
+        if self.world_models and not self.trainable_gaussian:
+            raise ValueError("world_models=True (the model-based on-policy loop) needs actor_gaussian='train'")
+        if self.world_models and (self.use_expert or self.bc):
+            raise ValueError("world_models=True holds no expert term: use_expert / bc must stay False")
 
     @property
     def trainable_gaussian(self) -> bool:
@@ -146,9 +155,9 @@ class EngineConfig:
         c.batch = int(self.batch)
         c.buffer_capacity = int(self.buffer_capacity)
         c.per_state_std = int(bool(self.per_state_std))
-        c.use_expert = N.EXPERT_BC if self.bc else int(bool(self.use_expert))
-        c.expert_capacity = int(self.expert_capacity)
-        c.expert_batch = int(self.expert_batch)
+        c.use_expert = N.EXPERT_MODELS if self.world_models else N.EXPERT_BC if self.bc else int(bool(self.use_expert))
+        c.expert_capacity = 0 if self.world_models else int(self.expert_capacity)
+        c.expert_batch = 0 if self.world_models else int(self.expert_batch)
         c.model_hidden[0], c.model_hidden[1] = [int(x) for x in two(self.model_hidden)]
         c.model_activation = N.ACT[self.model_activation]
         c.model_batch = int(self.model_batch)
@@ -670,11 +679,14 @@ class Engine:
         rr, dd = self._dev(r, (-1,)), self._dev(d, (-1,))      # (done flags arrive as f64 0 / 1: exact in f32)
         # the trajectory indices (floats in the reference) matter only where they change: ANY difference
         # between neighbours starts a trajectory (buffer_utils.py:63), so the device gets a running segment id
-        tj = np.asarray(traj.cpu().numpy() if torch.is_tensor(traj) else traj).reshape(-1)
-        seg = np.zeros(tj.shape[0], np.int32)
-        if tj.shape[0] > 1:
-            seg[1:] = np.cumsum(tj[1:] != tj[:-1], dtype=np.int32)
-        tt = torch.as_tensor(seg, device=self.device)
+        if torch.is_tensor(traj) and traj.is_cuda and traj.dtype == torch.int32:
+            tt = traj.reshape(-1).contiguous()                  # (Engine.sim_collect's ids: on the device already)
+        else:
+            tj = np.asarray(traj.cpu().numpy() if torch.is_tensor(traj) else traj).reshape(-1)
+            seg = np.zeros(tj.shape[0], np.int32)
+            if tj.shape[0] > 1:
+                seg[1:] = np.cumsum(tj[1:] != tj[:-1], dtype=np.int32)
+            tt = torch.as_tensor(seg, device=self.device)
         if int(rr.shape[0]) != n or int(dd.shape[0]) != n or int(tt.shape[0]) != n:
             raise ValueError("the rows of a GAE batch need the same length")
         kw = dict(dtype=torch.float32, device=self.device)
@@ -811,6 +823,53 @@ class Engine:
         N.check(self.lib.sacx_model_loss(self.h, int(model), p(x), p(y), p(u), p(rr), n, float(delta_clip_loss or 0.0),
                                          float(reward_clip_loss or 0.0), p(out)), self.h, "model_loss")
         return float(out.item())
+
+    def model_losses_eval(self, model: int, s, sp, a, r):
+        """get_losses_eval (continuous_models.py:304-319, :133-148) on the device, one forward ->
+        (mse_loss, r_loss) floats: the means of 0.5||norm(sp - s) - delta_pred||^2 and of
+        0.5 (norm(r) - r_pred)^2, no clip."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x, y, u = self._dev(s, (-1, S)), self._dev(sp, (-1, S)), self._dev(a, (-1, A))
+        n = int(x.shape[0])
+        rr = self._dev(r, (n,))
+        out = torch.empty((2,), dtype=torch.float32, device=self.device)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_model_losses_eval(self.h, int(model), p(x), p(y), p(u), p(rr), n, p(out)),
+                self.h, "model_losses_eval")
+        o = out.cpu().numpy()
+        return float(o[0]), float(o[1])
+
+    def sim_collect(self, model: int, n_traj: int, horizon: int, deterministic: bool = False,
+                    delta_clip: float = 0.0, reward_clip: float = 0.0):
+        """One pass of MBRLOnPolicyAlg._collect_sim_data (mbrl_onpolicy_alg.py:89-93) on the device
+        (EngineConfig(world_models=True)): n_traj start states drawn from the replay ring with
+        np.random.randint(rows held, size=n_traj) off the device stream, rolled out for `horizon`
+        steps of world model `model` under GaussianActor.sample.  -> CUDA tensors (s [n H, S],
+        a [n H, A] (raw actions), r [n H], sp [n H, S], d [n H] (bool, all False), traj [n H] (int32: the
+        running trajectory id)), trajectory-major as TrajectoryBuffer.add_batch stores them."""
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        n, H = int(n_traj), int(horizon)
+        # outputs kept per shape: stable pointers let libsacx replay its captured graph; the caller gets copies
+        if not hasattr(self, "_sim_bufs"):
+            self._sim_bufs = {}
+        bufs = self._sim_bufs.get((n, H))
+        if bufs is None:
+            kw = dict(dtype=torch.float32, device=self.device)
+            r0, c0 = max(n, 0), max(H, 0)
+            bufs = (torch.empty((r0, c0, S), **kw), torch.empty((r0, c0, A), **kw), torch.empty((r0, c0), **kw),
+                    torch.empty((r0, c0, S), **kw), torch.empty((r0, c0), dtype=torch.uint8, device=self.device),
+                    torch.arange(r0, dtype=torch.int32, device=self.device).repeat_interleave(c0))
+            if len(self._sim_bufs) >= 4:
+                self._sim_bufs.pop(next(iter(self._sim_bufs)))
+            self._sim_bufs[(n, H)] = bufs
+        s, a, r, sp, d, traj = bufs
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_sim_collect(self.h, int(model), n, H, int(bool(deterministic)),
+                                          float(delta_clip or 0.0), float(reward_clip or 0.0),
+                                          p(s), p(a), p(r), p(sp), p(d)), self.h, "sim_collect")
+        with torch.cuda.stream(self.stream):
+            return (s.reshape(-1, S).clone(), a.reshape(-1, A).clone(), r.reshape(-1).clone(),
+                    sp.reshape(-1, S).clone(), d.reshape(-1).bool(), traj.clone())
 
     def rollout(self, model: int, s_init, horizon: int, deterministic: bool = False,
                 delta_clip: float = 0.0, reward_clip: float = 0.0):
@@ -977,6 +1036,10 @@ class Engine:
 
     def sync(self):
         N.check(self.lib.sacx_sync(self.h), self.h, "sync")
+
+    def rollout_launches(self) -> int:
+        """Kernel launches of the rollout / sim_collect graph captured last (measurement)."""
+        return int(self.lib.sacx_rollout_launches(self.h))
 
     def spec_hits(self) -> int:
         """One-update steps that ran on randoms drawn speculatively by the preceding act_host."""

@@ -162,6 +162,16 @@ class BaseWorldModel:
         r2 = np.asarray(r, np.float32).reshape(-1)
         return eng.model_loss(k, s2, sp2, a2, r2, self.delta_clip_loss or 0.0, self.reward_clip_loss or 0.0)
 
+    def get_losses_eval(self, s, sp, a, r):
+        """(mse_loss, r_loss) of continuous_models.py:304-319 / :133-148: one unclipped forward on the
+        device (sacx_model_losses_eval)."""
+        eng, k = self._require()
+        s2, a2 = self._rows(s, a)
+        sp2 = np.asarray(sp, np.float32).reshape(-1, self.s_dim)
+        r2 = np.asarray(r, np.float32).reshape(-1)
+        mse, rl = eng.model_losses_eval(k, s2, sp2, a2, r2)
+        return _as_out(np.float32(mse)), _as_out(np.float32(rl))
+
 
 class MSEModel(BaseWorldModel):
     """continuous_models.py:205-349."""

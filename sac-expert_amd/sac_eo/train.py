@@ -136,6 +136,13 @@ def main(argv=None):
     if args.alg_type in ("sac", "sac_imit", "bc"):
         # SAC uses the squashed actor; the device BC trains the squashed actor only
         inputs_dict["actor_kwargs"]["actor_squash"] = True
+    if args.alg_type == "mbrl":
+        # the model-based on-policy loop trains the plain GaussianActor (actor_squash stays False); its runs
+        # train one after another (lockstep_ok), each on its own engine
+        if args.actor_squash:
+            raise ValueError("--alg_type mbrl trains the plain GaussianActor: --actor_squash is not supported")
+        if inputs_dict["actor_kwargs"].get("actor_output_norm"):
+            raise ValueError("--alg_type mbrl: --actor_output_norm has no backward on the device")
     seeds = derive_seeds(args.seed, args.runs, args.runs_start)
     runs = list(range(args.runs))
     ws = int(os.environ.get("WORLD_SIZE", "1"))
