@@ -495,6 +495,53 @@ int sacx_vcritic_end(sacx_handle* h, double* out);
 /* The launches of one critic step of mb rows per critic, as sacx_plan_info. */
 int sacx_vcritic_plan_info(sacx_handle* h, int32_t mb, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
 
+/* --- the TRPO actor update of the trainable GaussianActor ---------------------------------------
+ * TRPO.update (sac_eo/algs/model_free/trpo.py:34-317, the expert_reg is None branch, with the one
+ * reading that makes it run: grad_final := neg_pg), update_utils.cg, GaussianActor.set_weights.
+ * SACX_ACTOR_GAUSSIAN_TRAIN handles only; every call but sacx_trpo_init fails with a message on a
+ * handle without it.  "Flat" vectors are the floats of the actor's contiguous trainable range of the
+ * arena, actor.l0 .. actor.logstd (each layer as [W; b], then the layer norm's gamma ; beta, then
+ * logstd, with the padding between segments, which holds 0): sacx_layout gives the offsets.
+ *
+ * sacx_trpo_init: after sacx_create and before sacx_arena_bytes / sacx_layout / sacx_bind, in either
+ * order with sacx_vcritic_init.  Appends the "trpo.*" segments behind what the handle holds: the flat
+ * vectors ("trpo.vec": pg_vec, x, r, p, z, the saved weights, the step), the device scalars of
+ * conjugate gradient and the line search, and the rows of a chunk of a whole-table pass
+ * (min(buffer_capacity, 4096) rows).  A handle without the call keeps its layout byte for byte.
+ * Fails on another handle kind, on a bound handle and on a second call. */
+int sacx_trpo_init(sacx_handle* h);
+typedef struct sacx_trpo_params {
+    float delta;            /* delta_trpo: the trust region's KL bound */
+    float trust_damp;       /* F(x) = H x + trust_damp x */
+    float kl_maxfactor;     /* the line search accepts kl <= kl_maxfactor * delta */
+    float ent_targ;
+    float alpha_lr;
+    int32_t cg_it;          /* 1 .. 255 */
+    int32_t trust_sub;      /* the Fisher product runs on s_all[::trust_sub] */
+    int32_t ent_reg, adv_center, adv_scale;
+} sacx_trpo_params;
+/* trpo.py:36-63, :170-176: stores the rollout as sacx_ppo_begin does (neglogp_old, the reference
+ * distribution, the mean entropy), normalises the advantages over the whole table, and leaves
+ * pg_vec = -(d loss / d theta) of loss = mean(-r adv) - alpha (mean(ent) - ent_targ) in "trpo.vec"
+ * row 0; with ent_reg alpha then takes its Keras Adam step and max(alpha, 0).  No synchronisation. */
+int sacx_trpo_begin(sacx_handle* h, const float* s, const float* a, const float* adv, int64_t n,
+                    const sacx_trpo_params* params);
+/* pg_vec as sacx_trpo_begin left it -> out_dev (a flat device vector). */
+int sacx_trpo_grad(sacx_handle* h, float* out_dev);
+/* One Fisher-vector product (trpo.py:200-227) on flat device vectors: out = H x + trust_damp x with
+ * H = (1 / n_sub) sum_i J_i^T M_i J_i over the rows s_all[::trust_sub] of the table, at the weights
+ * as they stand (trust_sub, trust_damp: sacx_trpo_begin's).  flags: SACX_STEP_EAGER launches
+ * directly instead of replaying the captured graph (bit-identical).  No synchronisation. */
+int sacx_trpo_fvp(sacx_handle* h, const float* x_dev, float* out_dev, int32_t flags);
+/* trpo.py:178-198, :229-317: conjugate gradient (cg_it iterations from x = 0, the r.r < 1e-10 break
+ * as a device flag), vFv, eta, the backtracking line search (one synchronisation per trial).
+ * out[8] = ent, tv_pre, kl_pre, tv, kl, adj, improve, alpha.  A zero gradient (every |g| <= 1e-8)
+ * or delta == 0 gives the zero step.  vFv <= 0 (or not finite) fails with a message and leaves the
+ * weights untouched (the reference carries NaNs on).  flags: SACX_STEP_EAGER as above. */
+int sacx_trpo_step(sacx_handle* h, const sacx_trpo_params* params, int32_t flags, double* out);
+/* The launches of one Fisher product over `rows` rows, as sacx_plan_info. */
+int sacx_trpo_plan_info(sacx_handle* h, int64_t rows, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
+
 int sacx_sync(sacx_handle* h);
 /* Brings the arena to the state the calls so far define, without waiting: runs an alpha branch
  * the drop-in loop's one-update steps deferred (its alpha Adam, stats row and counters; see

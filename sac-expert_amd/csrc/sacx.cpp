@@ -22,6 +22,7 @@
 #include "sacx.h"
 #include "sacx_internal.h"
 #include "vcritic.h"
+#include "trpo.h"
 #include "mt_jump.h"
 
 #include <rccl/rccl.h>
@@ -66,7 +67,8 @@ struct SegInfo {
 
 struct Launch {
     enum Kind { RNG, GATHER, GEMM, AHEAD, QHEAD, ABWD, FINAL, MGATHER, MLOSS, MFINAL, ALLREDUCE, APPLY, AAPPLY,
-                GNORM, LNORM, PPOGATHER, PPOHEAD, GNPART, PPOFINAL, VCGATHER, VCHEAD, VCFINAL, VCADAM } kind;
+                GNORM, LNORM, PPOGATHER, PPOHEAD, GNPART, PPOFINAL, VCGATHER, VCHEAD, VCFINAL, VCADAM,
+                TRIN, TRTAN, TRHEAD, TRACC, TRCG } kind;
     std::string name;
     RngArgs rng;
     GatherArgs gather;
@@ -88,6 +90,11 @@ struct Launch {
     VcHeadArgs vh;             // VCHEAD
     VcFinalArgs vf;            // VCFINAL
     VcAdamArgs va;             // VCADAM
+    TrInArgs ti;               // TRIN
+    TrTanArgs tt;              // TRTAN
+    TrHeadArgs th;             // TRHEAD
+    TrAccArgs ta;              // TRACC
+    TrCgArgs tc;               // TRCG
     float* ar_buf = nullptr;   // ALLREDUCE: in-place sum over the data-parallel ranks
     int64_t ar_count = 0;
     int grid = 0, block = 256;
@@ -125,6 +132,11 @@ const char* kernel_family(Launch::Kind k) {
         case Launch::VCHEAD: return "k_vc_head";
         case Launch::VCFINAL: return "k_vc_final";
         case Launch::VCADAM: return "k_vc_adam";
+        case Launch::TRIN: return "k_trpo_in";
+        case Launch::TRTAN: return "k_trpo_tan";
+        case Launch::TRHEAD: return "k_trpo_head";
+        case Launch::TRACC: return "k_trpo_acc";
+        case Launch::TRCG: return "k_trpo_cg";
     }
     return "?";
 }
@@ -181,6 +193,16 @@ struct sacx_handle {
     int64_t vc_seq_host = 0;  // critic steps issued (mirrors VcCtl::seq: the index ring position)
     std::map<int, std::vector<Launch>> vc_plans;
     std::map<std::pair<int, int>, hipGraphExec_t> vc_graphs;
+    // sacx_trpo_init: the TRPO actor update (sacx_trpo_*)
+    bool trpo = false;
+    int trpo_chunk = 0;       // rows per launch chain of a whole-table pass
+    int64_t trpo_nv = 0;      // floats of the actor's contiguous trainable range (actor.l0 .. actor.logstd)
+    int64_t trpo_rows = 0;    // rows of the table sacx_trpo_begin took (0: none yet)
+    int32_t trpo_sub = 1;     // its trust_sub
+    hipGraphExec_t trpo_graph = nullptr;               // the captured CG solve ...
+    std::tuple<int64_t, int32_t, int32_t> trpo_gkey{0, 0, 0};   // ... of (rows, trust_sub, cg_it)
+    hipGraphExec_t trpo_fgraph = nullptr;              // one Fisher product p -> z ...
+    std::pair<int64_t, int32_t> trpo_fkey{0, 0};       // ... of (rows, trust_sub)
     // layout
     std::vector<SegInfo> segs;
     std::map<std::string, size_t> seg_index;
@@ -2764,6 +2786,11 @@ void enqueue(const Launch& L, sacx_handle* h, hipStream_t s) {
         case Launch::VCHEAD: launch_vc_head(L.vh, s); break;
         case Launch::VCFINAL: launch_vc_final(L.vf, s); break;
         case Launch::VCADAM: launch_vc_adam(L.va, s); break;
+        case Launch::TRIN: launch_trpo_in(L.ti, s); break;
+        case Launch::TRTAN: launch_trpo_tan(L.tt, s); break;
+        case Launch::TRHEAD: launch_trpo_head(L.th, s); break;
+        case Launch::TRACC: launch_trpo_acc(L.ta, s); break;
+        case Launch::TRCG: launch_trpo_cg(L.tc, s); break;
     }
 }
 
@@ -3650,6 +3677,8 @@ void sacx_destroy(sacx_handle* h) {
     for (auto& kv : h->roll_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->ppo_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->vc_graphs) (void)hipGraphExecDestroy(kv.second);
+    if (h->trpo_graph) (void)hipGraphExecDestroy(h->trpo_graph);
+    if (h->trpo_fgraph) (void)hipGraphExecDestroy(h->trpo_fgraph);
     for (auto e : h->events) (void)hipEventDestroy(e);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->done_host) (void)hipHostFree(h->done_host);
@@ -6151,6 +6180,504 @@ int sacx_vcritic_plan_info(sacx_handle* h, int32_t mb, sacx_launch_info* out, in
     if (!n_out) return fail(h, "null output");
     if (mb < 1 || mb > h->B) return fail(h, "minibatch rows outside [1, batch]");
     return launch_info(build_vc_plan(h, mb), out, cap, n_out);
+}
+
+// ---------------------------------------------------------------- TRPO actor update
+// TRPO.update (trpo.py:34-317, the expert_reg is None branch with grad_final := neg_pg) on a trainable
+// GaussianActor handle: the surrogate gradient and every Fisher-vector product as whole-table passes in
+// chunks of trpo_chunk rows, conjugate gradient on device vectors without a host round trip, the
+// backtracking line search with one synchronisation per trial.
+int sacx_trpo_init(sacx_handle* h) {
+    if (!h) return -1;
+    if (h->bound) return fail(h, "sacx_trpo_init must precede sacx_bind");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no TRPO update");
+    if (h->trpo) return fail(h, "sacx_trpo_init was already called on this handle");
+    static_assert(sizeof(TrpoPar) == 64, "trpo.par is 16 words");
+    const int F = SACX_F32, A = h->A, Aout = h->Aout;
+    const NetDims& na = h->nd[0];
+    const int64_t cap = h->cap;
+    const int C = (int)std::min<int64_t>(cap, TRPO_CHUNK);
+    const SegInfo& sl = h->seg("actor.logstd");
+    const int64_t nv = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4);
+    int wmax = std::max(Aout, h->ldS);
+    for (int w : na.h) wmax = std::max(wmax, w);
+    // behind everything the handle holds: every earlier segment keeps its offset
+    h->add("trpo.par", 1, 16, F, SACX_ROLE_WORK);
+    h->add("trpo.sc", 1, 16, SACX_F64, SACX_ROLE_WORK);
+    h->add("trpo.log", 1, 8, F, SACX_ROLE_WORK);
+    h->add("trpo.done", 1, TRPO_CG_MAX + 2, SACX_I32, SACX_ROLE_WORK);
+    h->add("trpo.rr", TRPO_CG_MAX + 1, TRPO_PARTS, SACX_F64, SACX_ROLE_WORK);
+    h->add("trpo.pz", 1, TRPO_PARTS, SACX_F64, SACX_ROLE_WORK);
+    h->add("trpo.vec", TRPO_VECS, r4(nv), F, SACX_ROLE_WORK);      // b, x, r, p, z, the saved weights, the step
+    h->add("trpo.zero", 1, wmax, F, SACX_ROLE_WORK);                // the bias of the t_in . W problems
+    h->add("trpo.ones", 1, C + 4, F, SACX_ROLE_WORK);               // the row scale of the dW problems
+    h->add("trpo.adv", 2, cap, F, SACX_ROLE_WORK);                  // the advantages normalised once / twice
+    h->add("trpo.ev", 3, cap, F, SACX_ROLE_WORK);                   // per row r adv, |r - 1|, kl
+    // a chunk's rows
+    h->add("trpo.X", C, h->ldS, F, 0);
+    for (int l = 0; l < na.D(); ++l) {
+        h->add("trpo.H" + std::to_string(l), C, na.h[l], F, 0);
+        h->add("trpo.T" + std::to_string(l), C, na.h[l], F, 0);
+        h->add("trpo.D" + std::to_string(l), C, na.h[l], F, 0);
+    }
+    h->add("trpo.G", 2 * (int64_t)C, wmax, F, 0);                   // the two halves of a layer's tangent
+    h->add("trpo.O", C, Aout, F, 0);
+    h->add("trpo.D3", C, Aout, F, 0);
+    h->add("trpo.E", C, A, F, 0);
+    if (h->ln) {
+        h->add("trpo.xhat", C, h->H0, F, 0);
+        h->add("trpo.rstd", 1, C, F, 0);
+        h->add("trpo.gy", C, h->H0, F, 0);
+        h->add("trpo.gb", C, h->H0, F, 0);
+    }
+    h->arena_bytes = (h->arena_bytes + 255) & ~uint64_t(255);
+    h->seed_bytes = h->arena_bytes;         // (one learner per trainable handle)
+    h->trpo = true;
+    h->trpo_chunk = C;
+    h->trpo_nv = nv;
+    return 0;
+}
+
+static int trpo_check(sacx_handle* h) {
+    if (!h || !h->bound) return fail(h, "not bound");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no TRPO update");
+    if (!h->trpo) return fail(h, "the handle has no TRPO update (sacx_trpo_init was not called)");
+    return 0;
+}
+
+// One chunk of a whole-table pass as a launch list.  mode 0: the surrogate gradient (rows row0 .. row0 + m),
+// 1: a Fisher-vector product (rows row0 + i * stride; dir = the direction over the flat range),
+// 2: the line search's evaluation (forward and head only).  Modes 0 and 1 end in the chunk's dW stored
+// (EPI_STORE) into the gradient words of the actor's range and k_trpo_acc adding them to `out`.
+//   trpo.in -> actor.fwd<i> (+ actor.ln) -> [actor.tan<i> + trpo.tan<i> per hidden layer, actor.tan<D>]
+//   -> trpo.head -> actor.bwd<i> (+ actor.ln.bwd) -> actor.grad -> trpo.acc
+static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode, int64_t row0, int m, int64_t stride,
+                            const float* dir, float* out, bool first, bool last) {
+    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, Aout = h->Aout, ldS = h->ldS, C = h->trpo_chunk;
+    const NetDims& na = h->nd[0];
+    const int Da = na.D();
+    auto W = [&](const std::string& n) { return h->f(n); };
+    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
+    auto Hb = [&](int i) { return W("trpo.H" + std::to_string(i)); };
+    auto Tb = [&](int i) { return W("trpo.T" + std::to_string(i)); };
+    auto Db = [&](int i) { return W("trpo.D" + std::to_string(i)); };
+    float* P0 = W("actor.l0");
+    auto dir_of = [&](const std::string& seg) { return dir + (W(seg) - P0); };     // the direction's words of a segment
+    const int t32 = h->tile32, dwl = h->dwl;
+    h->tile32 = 0; h->dwl = 0;              // 16 x 16 tiles, k_gemm: the tiles the PPO step's tests pin
+    const int cur = h->probs_cursor;
+    float *X = W("trpo.X"), *O = W("trpo.O"), *D3 = W("trpo.D3"), *E = W("trpo.E");
+    float *G0 = W("trpo.G"), *G1 = W("trpo.G") + (size_t)C * h->seg("trpo.G").cols;
+    TrpoPar* par = h->ptr<TrpoPar>("trpo.par");
+    {
+        Launch L{};
+        L.kind = Launch::TRIN;
+        L.name = "trpo.in";
+        L.ti.s = W("ppo.s"); L.ti.row0 = row0; L.ti.stride = stride;
+        L.ti.s_mean = W("norm.s_mean"); L.ti.s_den = W("norm.s_den");
+        L.ti.S = S; L.ti.ldS = ldS; L.ti.m = m; L.ti.X = X;
+        L.grid = (m + 63) / 64;
+        L.bytes = 4.0 * m * (S + ldS);
+        plan.push_back(L);
+    }
+    for (int i = 0; i < Da; ++i) {
+        const float* in = i == 0 ? X : Hb(i - 1);
+        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
+        add_gemm(h, plan, "actor.fwd" + std::to_string(i),
+                 {prob_fwd(in, ldi, m, K, W(L_("actor", i)), na.h[i], Hb(i), (i == 0 && h->ln) ? ACT_NONE : na.act[i])}, false);
+        if (i == 0 && h->ln) {
+            Launch L{};
+            L.kind = Launch::LNORM;
+            L.name = "actor.ln";
+            LNArgs& a = L.ln;
+            a.mode = 0; a.H = H0; a.Z = Hb(0); a.nrange = 1; a.r[0] = 0; a.r[1] = m;
+            a.gamma = W("actor.ln"); a.xhat = W("trpo.xhat"); a.rstd = W("trpo.rstd"); a.cache_rows = m;
+            L.grid = (m + 3) / 4;
+            L.flops = 8.0 * m * H0;
+            L.bytes = 4.0 * m * H0 * 3;
+            plan.push_back(L);
+        }
+    }
+    add_gemm(h, plan, "actor.fwd" + std::to_string(Da), {prob_fwd(Hb(Da - 1), H1, m, H1, W(L_("actor", Da)), Aout, O, ACT_NONE)},
+             false);
+    if (mode == 1) {
+        // the tangent forward: per layer h_in . V + v_b and t_in . W as the two problems of one launch
+        // (V_ext = the direction's words of the layer, so its bias row is v_b; the second problem's bias
+        // is trpo.zero), then t_out = act'(h_out) (.) (G0 + G1); layer 0's input has no tangent
+        for (int i = 0; i <= Da; ++i) {
+            const float* in = i == 0 ? X : Hb(i - 1);
+            const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
+            const int N = i < Da ? na.h[i] : Aout;
+            std::vector<GemmProb> ps;
+            ps.push_back(prob_fwd(in, ldi, m, K, dir_of(L_("actor", i)), N, G0, ACT_NONE));
+            if (i > 0) {
+                GemmProb p = prob_fwd(Tb(i - 1), K, m, K, W(L_("actor", i)), N, G1, ACT_NONE);
+                p.bias = W("trpo.zero");
+                ps.push_back(p);
+            }
+            add_gemm(h, plan, "actor.tan" + std::to_string(i), ps, false);
+            if (i == Da) break;
+            Launch L{};
+            L.kind = Launch::TRTAN;
+            L.name = "trpo.tan" + std::to_string(i);
+            TrTanArgs& a = L.tt;
+            a.G0 = G0; a.G1 = i > 0 ? G1 : nullptr; a.Hout = Hb(i); a.T = Tb(i);
+            a.m = m; a.H = N; a.act = na.act[i]; a.ln = (i == 0 && h->ln) ? 1 : 0;
+            if (a.ln) {
+                a.xhat = W("trpo.xhat"); a.rstd = W("trpo.rstd"); a.gamma = W("actor.ln"); a.vgamma = dir_of("actor.ln");
+            }
+            L.grid = a.ln ? (m + 3) / 4 : (int)(((int64_t)m * N + 255) / 256);
+            L.bytes = 4.0 * m * N * 4;
+            plan.push_back(L);
+        }
+    }
+    {
+        Launch L{};
+        L.kind = Launch::TRHEAD;
+        L.name = "trpo.head";
+        TrHeadArgs& a = L.th;
+        a.d.O = O; a.d.A = A; a.d.Aout = Aout; a.d.per_state_std = h->cfg.per_state_std;
+        a.d.logstd = W("actor.logstd");
+        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+        a.d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+        a.mode = mode; a.m = m; a.row0 = row0;
+        a.a = W("ppo.a"); a.nlp_old = W("ppo.nlp_old"); a.mean_ref = W("ppo.mean_ref"); a.ls_ref = W("ppo.ls_ref");
+        // the gradient takes the advantages normalised once, the line search twice (trpo.py:244-250)
+        a.adv = W("trpo.adv") + (mode == 2 ? (size_t)h->cap : 0);
+        a.alpha = W("ppo.alpha"); a.par = par;
+        a.TO0 = G0; a.TO1 = G1; a.vls = dir ? dir_of("actor.logstd") : nullptr;
+        a.D3 = D3; a.E = E;
+        a.o_radv = W("trpo.ev"); a.o_rdiff = W("trpo.ev") + h->cap; a.o_kl = W("trpo.ev") + 2 * (size_t)h->cap;
+        L.grid = (m + 3) / 4;
+        L.flops = 40.0 * m * A;
+        L.bytes = 4.0 * m * (3.0 * Aout + 2.0 * A + 4);
+        plan.push_back(L);
+    }
+    if (mode != 2) {
+        for (int i = Da; i >= 1; --i)
+            add_gemm(h, plan, "actor.bwd" + std::to_string(i),
+                     {prob_dx(i == Da ? D3 : Db(i), m, i == Da ? Aout : na.h[i], W(L_("actor", i)), na.h[i - 1], Hb(i - 1),
+                              Db(i - 1), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
+                     false);
+        if (h->ln) {
+            Launch N{};
+            N.kind = Launch::LNORM;
+            N.name = "actor.ln.bwd";
+            LNArgs& a = N.ln;
+            a.mode = 1; a.H = H0; a.Z = Db(0); a.r[1] = m; a.gamma = W("actor.ln");
+            a.xhat = W("trpo.xhat"); a.rstd = W("trpo.rstd"); a.xrow0 = 0;
+            a.gy = W("trpo.gy"); a.gb = W("trpo.gb");
+            N.grid = (m + 3) / 4;
+            N.flops = 8.0 * m * H0;
+            N.bytes = 4.0 * m * H0 * 5;
+            plan.push_back(N);
+        }
+        std::vector<GemmProb> pw;
+        auto dw = [&](GemmProb p) {
+            p.bscale = W("trpo.ones");
+            pw.push_back(p);
+        };
+        for (int i = 0; i < Da; ++i) {
+            const float* Xi = i == 0 ? X : Hb(i - 1);
+            const int K = i == 0 ? S : na.h[i - 1];
+            dw(prob_dw(Xi, i == 0 ? ldS : K, K, m, Db(i), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
+        }
+        dw(prob_dw(Hb(Da - 1), H1, H1, m, D3, Aout, W(L_("actor", Da)), nullptr, GRP_PI));
+        if (!h->cfg.per_state_std) {
+            GemmProb p = prob_dw(E, 1, 0, m, E, A, W("actor.logstd"), nullptr, GRP_PI);
+            p.ones_row = 0;   // single all-ones row: column sums of E
+            dw(p);
+        }
+        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
+            for (int k = 0; k < 2; ++k) {
+                float* gsrc = W(k ? "trpo.gb" : "trpo.gy");
+                GemmProb p = prob_dw(gsrc, 1, 0, m, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
+                p.ones_row = 0;
+                dw(p);
+            }
+        }
+        const int n_dw = add_gemm_split(h, plan, "actor.grad", pw, false);
+        for (int j = 0; j < n_dw; ++j) {       // stored at +3 p_stride, as the PPO step's
+            Launch& G = plan[plan.size() - 1 - j];
+            for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
+        }
+        Launch L{};
+        L.kind = Launch::TRACC;
+        L.name = "trpo.acc";
+        TrAccArgs& a = L.ta;
+        a.g = P0 + 3 * h->p_stride; a.dst = out; a.x = mode == 1 ? dir : nullptr; a.n = h->trpo_nv;
+        a.first = first; a.last = last; a.sign = mode == 0 ? -1.f : 1.f; a.par = par;
+        L.grid = (int)((h->trpo_nv + 255) / 256);
+        L.bytes = 4.0 * h->trpo_nv * 3;
+        plan.push_back(L);
+    }
+    h->probs_cursor = cur;
+    h->tile32 = t32; h->dwl = dwl;
+}
+
+// a whole-table pass: every chunk's launches in chunk order
+static void trpo_pass_plan(sacx_handle* h, std::vector<Launch>& plan, int mode, int64_t n, int64_t stride, const float* dir,
+                           float* out) {
+    const int64_t rows = (n + stride - 1) / stride;         // len(s_all[::stride])
+    const int C = h->trpo_chunk;
+    for (int64_t done = 0; done < rows; done += C) {
+        const int m = (int)std::min<int64_t>(C, rows - done);
+        trpo_chunk_plan(h, plan, mode, done * stride, m, stride, dir, out, done == 0, done + C >= rows);
+    }
+}
+
+static TrCgArgs trpo_cg_args(sacx_handle* h, int phase, int it) {
+    TrCgArgs a{};
+    a.phase = phase; a.it = it; a.n = h->trpo_nv;
+    a.vec = h->f("trpo.vec"); a.vstride = h->seg("trpo.vec").cols;
+    a.rr = h->ptr<double>("trpo.rr"); a.pz = h->ptr<double>("trpo.pz");
+    a.done = h->ptr<int32_t>("trpo.done"); a.sc = h->ptr<double>("trpo.sc");
+    a.par = h->ptr<TrpoPar>("trpo.par");
+    a.W = h->f("actor.l0");
+    a.ls_off = h->cfg.per_state_std ? 0 : (int64_t)(h->f("actor.logstd") - h->f("actor.l0"));
+    a.ls_n = h->cfg.per_state_std ? 0 : h->A;
+    a.ls_floor = (float)std::log(1e-3);
+    return a;
+}
+static Launch trpo_cg_launch(sacx_handle* h, int phase, int it, const char* name) {
+    Launch L{};
+    L.kind = Launch::TRCG;
+    L.name = name;
+    L.tc = trpo_cg_args(h, phase, it);
+    L.grid = phase == TRC_GMAX ? 1 : TRPO_PARTS;
+    L.bytes = 4.0 * h->trpo_nv * 3;
+    return L;
+}
+
+static float* trpo_vec(sacx_handle* h, int k) { return h->f("trpo.vec") + (size_t)k * h->seg("trpo.vec").cols; }
+
+static int trpo_par_check(sacx_handle* h, const sacx_trpo_params* q) {
+    if (!q) return fail(h, "null parameters");
+    if (!(q->delta >= 0.f) || !(q->trust_damp >= 0.f) || !(q->alpha_lr >= 0.f) || !(q->kl_maxfactor >= 0.f))
+        return fail(h, "delta, trust_damp, kl_maxfactor and alpha_lr must be non-negative");
+    if (q->cg_it < 1 || q->cg_it > TRPO_CG_MAX)
+        return fail(h, "cg_it " + std::to_string(q->cg_it) + " outside [1, " + std::to_string(TRPO_CG_MAX) + "]");
+    if (q->trust_sub < 1) return fail(h, "trust_sub must be at least 1");
+    return 0;
+}
+
+static void trpo_par_set(sacx_handle* h, const sacx_trpo_params* q, int64_t n, hipStream_t st) {
+    TrpoPar p{};
+    p.delta = q->delta; p.damp = q->trust_damp; p.ent_targ = q->ent_targ; p.alpha_lr = q->alpha_lr;
+    p.inv_n = (float)(1.0 / (double)n);
+    p.inv_nsub = (float)(1.0 / (double)((n + q->trust_sub - 1) / q->trust_sub));
+    p.ent_reg = q->ent_reg != 0; p.adv_center = q->adv_center != 0; p.adv_scale = q->adv_scale != 0;
+    launch_trpo_set(h->ptr<TrpoPar>("trpo.par"), p, st);
+}
+
+int sacx_trpo_begin(sacx_handle* h, const float* s, const float* a, const float* adv, int64_t n,
+                    const sacx_trpo_params* params) {
+    if (trpo_check(h)) return -1;
+    if (trpo_par_check(h, params)) return -1;
+    h->trpo_rows = 0;
+    // the table, neglogp_old, the reference distribution and the mean entropy (trpo.py:37, :240-241)
+    if (sacx_ppo_begin(h, s, a, adv, n)) return -1;
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    trpo_par_set(h, params, n, h->stream);
+    launch_trpo_fill(W("trpo.zero"), h->seg("trpo.zero").cols, 0.f, h->stream);
+    launch_trpo_fill(W("trpo.ones"), h->seg("trpo.ones").cols, 1.f, h->stream);
+    TrAdvArgs q{};
+    q.src = W("ppo.adv"); q.dst = W("trpo.adv"); q.n = n; q.par = h->ptr<TrpoPar>("trpo.par");
+    launch_trpo_advnorm(q, h->stream);
+    q.src = W("trpo.adv"); q.dst = W("trpo.adv") + h->cap;         // _backtrack normalises once more (:244-250)
+    launch_trpo_advnorm(q, h->stream);
+    std::vector<Launch> plan;
+    trpo_pass_plan(h, plan, 0, n, 1, nullptr, trpo_vec(h, TRV_B));
+    plan.push_back(trpo_cg_launch(h, TRC_GMAX, 0, "trpo.gmax"));
+    for (const Launch& L : plan) enqueue(L, h, h->stream);
+    TrAlphaArgs al{};               // behind the gradient: it takes the alpha from before this step
+    al.alpha = W("ppo.alpha"); al.ctl = h->ptr<PpoCtl>("ppo.ctl"); al.ent = W("ppo.log"); al.par = h->ptr<TrpoPar>("trpo.par");
+    launch_trpo_alpha(al, h->stream);
+    HIPCHK(h, hipGetLastError());
+    h->trpo_rows = n;
+    h->trpo_sub = params->trust_sub;
+    return 0;
+}
+
+static int trpo_capture(sacx_handle* h, const std::vector<Launch>& plan, hipGraphExec_t* out, const char* what) {
+    HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
+    for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
+    const hipError_t le = hipGetLastError();
+    hipGraph_t graph = nullptr;
+    const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
+    if (le != hipSuccess || ee != hipSuccess) {
+        if (graph) (void)hipGraphDestroy(graph);
+        return fail(h, std::string(what) + " graph capture: " + hipGetErrorString(le != hipSuccess ? le : ee));
+    }
+    hipGraphExec_t ex = nullptr;
+    const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) return fail(h, std::string(what) + " graph instantiate: " + hipGetErrorString(ie));
+    *out = ex;
+    return 0;
+}
+
+int sacx_trpo_grad(sacx_handle* h, float* out_dev) {
+    if (trpo_check(h)) return -1;
+    if (!out_dev) return fail(h, "null output");
+    if (h->trpo_rows < 1) return fail(h, "no rollout table: call sacx_trpo_begin first");
+    HIPCHK(h, hipMemcpyAsync(out_dev, trpo_vec(h, TRV_B), sizeof(float) * (size_t)h->trpo_nv, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+int sacx_trpo_fvp(sacx_handle* h, const float* x_dev, float* out_dev, int32_t flags) {
+    if (trpo_check(h)) return -1;
+    if (!x_dev || !out_dev) return fail(h, "null vector");
+    if (h->trpo_rows < 1) return fail(h, "no rollout table: call sacx_trpo_begin first");
+    const size_t nb = sizeof(float) * (size_t)h->trpo_nv;
+    HIPCHK(h, hipMemcpyAsync(trpo_vec(h, TRV_P), x_dev, nb, hipMemcpyDeviceToDevice, h->stream));
+    if (flags & SACX_STEP_EAGER) {
+        std::vector<Launch> plan;
+        trpo_pass_plan(h, plan, 1, h->trpo_rows, h->trpo_sub, trpo_vec(h, TRV_P), trpo_vec(h, TRV_Z));
+        for (const Launch& L : plan) enqueue(L, h, h->stream);
+        HIPCHK(h, hipGetLastError());
+    } else {
+        const std::pair<int64_t, int32_t> key{h->trpo_rows, h->trpo_sub};
+        if (!h->trpo_fgraph || h->trpo_fkey != key) {
+            if (h->trpo_fgraph) (void)hipGraphExecDestroy(h->trpo_fgraph);
+            h->trpo_fgraph = nullptr;
+            std::vector<Launch> plan;
+            trpo_pass_plan(h, plan, 1, h->trpo_rows, h->trpo_sub, trpo_vec(h, TRV_P), trpo_vec(h, TRV_Z));
+            if (trpo_capture(h, plan, &h->trpo_fgraph, "TRPO Fisher product")) return -1;
+            h->trpo_fkey = key;
+        }
+        HIPCHK(h, hipGraphLaunch(h->trpo_fgraph, h->stream));
+    }
+    HIPCHK(h, hipMemcpyAsync(out_dev, trpo_vec(h, TRV_Z), nb, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+// update_utils.cg from x = 0, then vFv = x . F(x), eta = sqrt(2 delta / vFv), step = eta x: one launch
+// list, no host round trip (the break is the done flag of each iteration)
+static void trpo_solve_plan(sacx_handle* h, std::vector<Launch>& plan, int cg_it) {
+    float *p = trpo_vec(h, TRV_P), *x = trpo_vec(h, TRV_X), *z = trpo_vec(h, TRV_Z);
+    plan.push_back(trpo_cg_launch(h, TRC_INIT, 0, "trpo.cg.init"));
+    for (int it = 0; it < cg_it; ++it) {
+        trpo_pass_plan(h, plan, 1, h->trpo_rows, h->trpo_sub, p, z);
+        plan.push_back(trpo_cg_launch(h, TRC_DOT, it, "trpo.cg.dot"));
+        plan.push_back(trpo_cg_launch(h, TRC_UPD1, it, "trpo.cg.xr"));
+        plan.push_back(trpo_cg_launch(h, TRC_UPD2, it, "trpo.cg.p"));
+    }
+    trpo_pass_plan(h, plan, 1, h->trpo_rows, h->trpo_sub, x, z);
+    plan.push_back(trpo_cg_launch(h, TRC_DOTX, 0, "trpo.vfv"));
+    plan.push_back(trpo_cg_launch(h, TRC_SCALE, 0, "trpo.scale"));
+}
+
+int sacx_trpo_step(sacx_handle* h, const sacx_trpo_params* params, int32_t flags, double* out) {
+    if (trpo_check(h)) return -1;
+    if (trpo_par_check(h, params)) return -1;
+    if (!out) return fail(h, "null output");
+    if (h->trpo_rows < 1) return fail(h, "no rollout table: call sacx_trpo_begin first");
+    if (params->trust_sub != h->trpo_sub) return fail(h, "trust_sub differs from sacx_trpo_begin's");
+    const int64_t n = h->trpo_rows;
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    trpo_par_set(h, params, n, h->stream);
+    double sc[16];
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(sc, h->ptr<double>("trpo.sc"), sizeof(sc), hipMemcpyDeviceToHost));
+    // np.allclose(pg_vec, 0) or delta == 0 (trpo.py:179): the zero step
+    const bool zero = !(sc[TRS_GMAX] > 1e-8) && sc[TRS_GMAX] == sc[TRS_GMAX];
+    if (zero || params->delta == 0.f) {
+        launch_trpo_cg(trpo_cg_args(h, TRC_ZERO, 0), h->stream);
+    } else {
+        if (flags & SACX_STEP_EAGER) {
+            std::vector<Launch> plan;
+            trpo_solve_plan(h, plan, params->cg_it);
+            for (const Launch& L : plan) enqueue(L, h, h->stream);
+            HIPCHK(h, hipGetLastError());
+        } else {
+            const std::tuple<int64_t, int32_t, int32_t> key{n, h->trpo_sub, params->cg_it};
+            if (!h->trpo_graph || h->trpo_gkey != key) {
+                if (h->trpo_graph) (void)hipGraphExecDestroy(h->trpo_graph);
+                h->trpo_graph = nullptr;
+                std::vector<Launch> plan;
+                trpo_solve_plan(h, plan, params->cg_it);
+                if (trpo_capture(h, plan, &h->trpo_graph, "TRPO solve")) return -1;
+                h->trpo_gkey = key;
+            }
+            HIPCHK(h, hipGraphLaunch(h->trpo_graph, h->stream));
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(sc, h->ptr<double>("trpo.sc"), sizeof(sc), hipMemcpyDeviceToHost));
+        // the reference divides by vFv and accepts the NaNs that follow; here the update is refused
+        // with the weights untouched
+        if (!(sc[TRS_VFV] > 0.0) || !(sc[TRS_ETA] == sc[TRS_ETA]) || std::isinf(sc[TRS_ETA]))
+            return fail(h, "TRPO: the step is degenerate (vFv = " + std::to_string(sc[TRS_VFV]) +
+                               " is not positive, or not finite); the weights are unchanged");
+    }
+    // _backtrack (trpo.py:229-317)
+    const size_t nb = sizeof(float) * (size_t)h->trpo_nv;
+    HIPCHK(h, hipMemcpyAsync(trpo_vec(h, TRV_SAVED), W("actor.l0"), nb, hipMemcpyDeviceToDevice, h->stream));
+    std::vector<Launch> eval;
+    trpo_pass_plan(h, eval, 2, n, 1, nullptr, nullptr);
+    float lg[8];
+    auto evaluate = [&]() -> int {          // tv, kl, mean(r adv) with the weights as they stand
+        for (const Launch& L : eval) enqueue(L, h, h->stream);
+        PpoReduceArgs q{};
+        float* ev = W("trpo.ev");
+        float* lo = W("trpo.log");
+        q.c[0] = ev + h->cap; q.out[0] = lo; q.half0 = 0.5f;        // tv
+        q.c[1] = ev + 2 * (size_t)h->cap; q.out[1] = lo + 1;        // kl
+        q.c[2] = ev; q.out[2] = lo + 2;                             // surr
+        q.n = n;
+        launch_ppo_reduce(q, h->stream);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipMemcpy(lg, lo, sizeof(lg), hipMemcpyDeviceToHost));
+        return 0;
+    };
+    auto apply = [&](int add) {
+        TrCgArgs a = trpo_cg_args(h, TRC_APPLY, 0);
+        a.add = add;
+        launch_trpo_cg(a, h->stream);
+    };
+    if (evaluate()) return -1;
+    const float surr_before = lg[2];
+    apply(1);
+    if (evaluate()) return -1;
+    const float tv_pre = lg[0], kl_pre = lg[1];
+    float tv = lg[0], kl = lg[1], improve = lg[2] - surr_before;
+    const float kl_max = (float)((double)params->kl_maxfactor * (double)params->delta);
+    double adj = 1.0;
+    bool ok = false;
+    for (int t = 0; t < 10; ++t) {
+        if (!(kl > kl_max) && !(improve < 0.f)) {
+            ok = true;
+            break;
+        }
+        adj = adj / std::sqrt(2.0);
+        launch_trpo_cg(trpo_cg_args(h, TRC_SHRINK, 0), h->stream);
+        apply(1);
+        if (evaluate()) return -1;
+        tv = lg[0]; kl = lg[1]; improve = lg[2] - surr_before;
+    }
+    if (!ok) {                              // no policy update
+        adj = 0.0;
+        apply(0);
+        if (evaluate()) return -1;
+        tv = lg[0]; kl = lg[1]; improve = lg[2] - surr_before;
+    }
+    float ent = 0.f, alpha = 0.f;
+    HIPCHK(h, hipMemcpy(&ent, W("ppo.log"), sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&alpha, W("ppo.alpha"), sizeof(float), hipMemcpyDeviceToHost));
+    out[0] = ent; out[1] = tv_pre; out[2] = kl_pre; out[3] = tv; out[4] = kl; out[5] = adj; out[6] = improve; out[7] = alpha;
+    return 0;
+}
+
+int sacx_trpo_plan_info(sacx_handle* h, int64_t rows, sacx_launch_info* out, int32_t cap, int32_t* n_out) {
+    if (trpo_check(h)) return -1;
+    if (!n_out) return fail(h, "null output");
+    if (rows < 1 || rows > h->cap) return fail(h, "rows outside [1, buffer_capacity]");
+    std::vector<Launch> plan;
+    trpo_pass_plan(h, plan, 1, rows, 1, trpo_vec(h, TRV_P), trpo_vec(h, TRV_Z));
+    return launch_info(plan, out, cap, n_out);
 }
 
 }  // extern "C"

@@ -45,6 +45,7 @@ EXPORTS = [
     "sacx_vcritic_init", "sacx_vcritic_value", "sacx_gae_values", "sacx_gae", "sacx_vcritic_loss", "sacx_vcritic_begin",
     "sacx_vcritic_steps", "sacx_vcritic_end", "sacx_vcritic_plan_info",
     "sacx_sim_collect", "sacx_model_losses_eval", "sacx_rollout_launches",
+    "sacx_trpo_init", "sacx_trpo_begin", "sacx_trpo_grad", "sacx_trpo_fvp", "sacx_trpo_step", "sacx_trpo_plan_info",
 ]
 
 
@@ -115,6 +116,22 @@ class PpoParams(ctypes.Structure):
         ("ent_targ", ctypes.c_float),
         ("alpha_lr", ctypes.c_float),
         ("actor_lr", ctypes.c_float),
+        ("ent_reg", ctypes.c_int32),
+        ("adv_center", ctypes.c_int32),
+        ("adv_scale", ctypes.c_int32),
+    ]
+
+
+class TrpoParams(ctypes.Structure):
+    """sacx_trpo_params: the run-time inputs of the TRPO update (trpo.py:15-32)."""
+    _fields_ = [
+        ("delta", ctypes.c_float),
+        ("trust_damp", ctypes.c_float),
+        ("kl_maxfactor", ctypes.c_float),
+        ("ent_targ", ctypes.c_float),
+        ("alpha_lr", ctypes.c_float),
+        ("cg_it", ctypes.c_int32),
+        ("trust_sub", ctypes.c_int32),
         ("ent_reg", ctypes.c_int32),
         ("adv_center", ctypes.c_int32),
         ("adv_scale", ctypes.c_int32),
@@ -220,6 +237,12 @@ def lib():
         "sacx_vcritic_steps": (ctypes.c_int, [vp, vp, i64, i32, f32, i32]),
         "sacx_vcritic_end": (ctypes.c_int, [vp, P(f64)]),
         "sacx_vcritic_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
+        "sacx_trpo_init": (ctypes.c_int, [vp]),
+        "sacx_trpo_begin": (ctypes.c_int, [vp, vp, vp, vp, i64, P(TrpoParams)]),
+        "sacx_trpo_grad": (ctypes.c_int, [vp, vp]),
+        "sacx_trpo_fvp": (ctypes.c_int, [vp, vp, vp, i32]),
+        "sacx_trpo_step": (ctypes.c_int, [vp, P(TrpoParams), i32, P(f64)]),
+        "sacx_trpo_plan_info": (ctypes.c_int, [vp, i64, P(LaunchInfo), i32, P(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -67,20 +67,43 @@ class GaussianActor:
     def trainable(self):
         return self.get_weights()
 
-    def get_weights(self):
+    def get_weights(self, flat=False):
+        """``continuous_actors.py:201-209``; ``flat``: ``list_to_flat`` -- the arrays raveled and joined."""
         if self._engine is not None:
             w = self._engine.get_net(self._net)
             if not self.per_state_std:
                 w.append(self._engine.v["actor.logstd"].cpu().numpy().copy())
-            return w
-        return [x.copy() for x in self._w] + ([] if self.per_state_std else [self._logstd.copy()])
+        else:
+            w = [x.copy() for x in self._w] + ([] if self.per_state_std else [self._logstd.copy()])
+        if flat:
+            return np.concatenate([np.asarray(x).reshape(-1) for x in w], -1)
+        return w
 
-    def set_weights(self, weights):
+    def set_weights(self, weights, from_flat=False, increment=False):
+        """``continuous_actors.py:211-234``.  ``from_flat``: a flat vector over the trainables
+        (``flat_to_list``); ``increment``: added to the current weights.  With either keyword the raw
+        state-independent ``logstd`` is floored at ``log 1e-3`` as the reference floors it on every set;
+        the plain call keeps the values it is given (today's behaviour)."""
+        literal = bool(from_flat or increment)
+        if from_flat:
+            flat = np.asarray(weights).reshape(-1)
+            cur = self.get_weights()
+            if flat.size != sum(x.size for x in cur):
+                raise ValueError(f"a flat weight vector holds {sum(x.size for x in cur)} values, got {flat.size}")
+            weights, o = [], 0
+            for x in cur:
+                weights.append(flat[o:o + x.size].reshape(x.shape))
+                o += x.size
+        if increment:
+            weights = [np.asarray(x) + y for x, y in zip(weights, self.get_weights())]
         weights = [np.asarray(x, np.float32) for x in weights]
         nw = len(self._w)
         self._w = weights[:nw]
         if not self.per_state_std and len(weights) > nw:
-            self._logstd = weights[nw].reshape(1, -1)
+            ls = weights[nw].reshape(1, -1)
+            if literal:
+                ls = np.maximum(ls, np.log(1e-3)).astype(np.float32)
+            self._logstd = ls
         if self._engine is not None:
             self._engine.set_net(self._net, self._w)
             if not self.per_state_std:

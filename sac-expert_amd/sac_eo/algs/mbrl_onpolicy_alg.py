@@ -14,7 +14,9 @@ the PPO-trained GaussianActor, the VCritics and the world models; the replay rin
   model (index draw, ring rows, rollout: one device call), ``Engine.gae`` per model, the critic update
   and the PPO update on ``torch.cat`` of the parts.  The rollout rows never leave the device.
 
-TRPO (``mf_algo='trpo'``) is not built: ``init_alg`` refuses it.
+TRPO (``alg_kwargs['mf_algo'] == 'trpo'``) runs when the class is constructed directly: it builds
+``sac_eo.algs.model_free.trpo.TRPO`` and an engine with ``trpo=True``, and the loop logs whatever keys
+``update`` returns.  ``init_alg`` (the front door of ``python -m sac_eo.train``) still refuses it.
 """
 import contextlib
 import time
@@ -61,7 +63,11 @@ class MBRLOnPolicyAlg:
         self.checkpoint_name = f"{self.checkpoint_file}_{idx}"
         self.current_reward = 0
         self.engine = self._build_engine(alg_kwargs, mf_update_kwargs)
-        self.mf_algo = PPO(self.actor, mf_update_kwargs)
+        if self.mf_algo_name == "trpo":                 # (reached by direct construction only: init_alg refuses it)
+            from .model_free.trpo import TRPO
+            self.mf_algo = TRPO(self.actor, mf_update_kwargs)
+        else:
+            self.mf_algo = PPO(self.actor, mf_update_kwargs)
         self.critic_update = VCriticUpdate(self.critics, dict(critic_lr=self.critic_lr,
                                                               critic_update_it=self.critic_update_it,
                                                               critic_nminibatch=self.critic_nminibatch), self.actor)
@@ -133,14 +139,16 @@ class MBRLOnPolicyAlg:
     def _build_engine(self, k, mf):
         a, c0, m0 = self.actor, self.critics[0], self.models[0]
         sim = self._sim_rows()
-        batch = max(1, int(sim / max(1, min(int(mf["actor_nminibatch"]), int(self.critic_nminibatch)))))
+        trpo = self.mf_algo_name == "trpo"              # no actor minibatches: the critics' alone size the batch
+        nmb = int(self.critic_nminibatch) if trpo else min(int(mf["actor_nminibatch"]), int(self.critic_nminibatch))
+        batch = max(1, int(sim / max(1, nmb)))
         gm = bool(getattr(m0, "gaussian", False))
         cfg = EngineConfig(
             s_dim=self.s_dim, a_dim=self.a_dim, hidden=tuple(a.layers), activation=a.activation,
             actor_activations=a.activations, critic_hidden=tuple(c0.layers), critic_activations=c0.activations,
             batch=batch, buffer_capacity=self._capacity(), per_state_std=a.per_state_std, actor_gaussian="train",
             actor_std_mult=float(a.std_mult), actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096,
-            vcritics=self.num_critics, world_models=True, act_limit=float(np.max(a.act_limit)), gamma=self.gamma,
+            vcritics=self.num_critics, world_models=True, trpo=trpo, act_limit=float(np.max(a.act_limit)), gamma=self.gamma,
             model_hidden=tuple(m0.layers), model_activation=m0.activation, model_activations=m0.activations,
             model_batch=int(self.model_batch_size), lr_model=self.model_lr, reward_loss_coef=m0.reward_loss_coef,
             num_models=self.B, model_max_grad_norm=float(self.model_max_grad_norm or 0.0),

@@ -16,8 +16,8 @@ whose rollouts grow passes ``update_kwargs['rollout_capacity']`` (rows).
 Readable state: ``.alpha`` (a float, the reference's ``self.alpha.numpy()``), ``.actor_lr``
 (the CURRENT rate of the actor's Adam; the reference's
 ``self.actor_optimizer.learning_rate`` is served as ``.actor_optimizer.learning_rate`` with
-a ``.numpy()`` too).  ``expert_reg`` (the reference's unreachable regulariser branch) and
-``TRPO`` are not built.
+a ``.numpy()`` too).  ``expert_reg`` (the reference's unreachable regulariser branch) is not built;
+``TRPO`` is ``sac_eo.algs.model_free.trpo.TRPO``.
 """
 import contextlib
 

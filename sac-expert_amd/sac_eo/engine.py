@@ -99,8 +99,14 @@ class EngineConfig:
     # GaussianActor and its VCritics -- SACX_EXPERT_MODELS: no expert rows, no SAC / BC plan.  Needs
     # actor_gaussian="train"; expert_capacity / expert_batch are not used
     world_models: bool = False
+    # the TRPO actor update beside the trainable GaussianActor (actor_gaussian="train"): Engine.trpo_begin /
+    # trpo_grad / trpo_fvp / trpo_step.  A host-only field, as vcritics: Engine makes the handle's init call
+    # right after creating it; False leaves the handle and its layout as they are
+    trpo: bool = False
 
     def __post_init__(self):
+        if self.trpo and not self.trainable_gaussian:
+            raise ValueError("trpo=True (the TRPO actor update) needs actor_gaussian='train'")
         if self.bc:
             self.use_expert = True
         if self.world_models and not self.trainable_gaussian:
@@ -239,6 +245,11 @@ class Engine:
             self.lib.sacx_destroy(h)                        # (nothing else holds the handle yet)
             self.h = None
             raise N.SacxError(f"sacx_vcritic_init: {msg}")
+        if bool(getattr(cfg, "trpo", False)) and self.lib.sacx_trpo_init(h) != 0:
+            msg = (self.lib.sacx_last_error(h) or b"").decode()
+            self.lib.sacx_destroy(h)
+            self.h = None
+            raise N.SacxError(f"sacx_trpo_init: {msg}")
         total = int(self.lib.sacx_arena_bytes(h))
         self.seeds = max(1, int(cfg.seeds))
         self.seed_stride = int(self.lib.sacx_seed_stride(h))
@@ -659,6 +670,131 @@ class Engine:
         N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), None, 0, ctypes.byref(n)), self.h, "ppo_plan_info")
         arr = (N.LaunchInfo * n.value)()
         N.check(self.lib.sacx_ppo_plan_info(self.h, int(mb), arr, n.value, ctypes.byref(n)), self.h, "ppo_plan_info")
+        return [dict(name=a.name.decode(), kernel=a.kernel.decode(), grid=a.grid, block=a.block,
+                     flops=a.flops, bytes=a.bytes) for a in arr]
+
+    # ------------------------------------------------------------------ TRPO actor update
+    # (EngineConfig(actor_gaussian="train", trpo=True); every call raises on an engine without it)
+    def _trpo_need(self):
+        if not bool(getattr(self.cfg, "trpo", False)):
+            raise RuntimeError("this engine has no TRPO update: build it with EngineConfig(actor_gaussian='train', trpo=True)")
+
+    def _trpo_slices(self):
+        """[(float offset in the flat range, shape)] of the actor's trainables in the Keras order
+        ([W0, b0, (gamma, beta,) W1, b1, ..., logstd]) and the range's length in floats."""
+        seg = self.segments
+        base = seg["actor.l0"]["offset"]
+        out = []
+        i = 0
+        while f"actor.l{i}" in seg:
+            d = seg[f"actor.l{i}"]
+            o = (d["offset"] - base) // 4
+            out += [(o, (d["rows"] - 1, d["cols"])), (o + (d["rows"] - 1) * d["cols"], (d["cols"],))]
+            if i == 0 and self.cfg.actor_layer_norm:
+                g = seg["actor.ln"]
+                og = (g["offset"] - base) // 4
+                out += [(og, (g["cols"],)), (og + g["cols"], (g["cols"],))]
+            i += 1
+        ls = seg["actor.logstd"]
+        ol = (ls["offset"] - base) // 4
+        if not self.cfg.per_state_std:
+            out.append((ol, (1, ls["cols"])))
+        return out, ol + ls["rows"] * ls["cols"]
+
+    def trpo_flat_len(self) -> int:
+        return self._trpo_slices()[1]
+
+    def trpo_pack(self, arrays) -> "torch.Tensor":
+        """The trainables' list (Keras order) -> a flat device vector over the actor's range (padding 0)."""
+        sl, nv = self._trpo_slices()
+        arrays = list(arrays)
+        if len(arrays) != len(sl):
+            raise ValueError(f"expected {len(sl)} arrays, got {len(arrays)}")
+        flat = np.zeros(nv, np.float32)
+        for (o, shp), a in zip(sl, arrays):
+            a = np.asarray(a, np.float32)
+            if a.size != int(np.prod(shp)):
+                raise ValueError(f"expected an array of shape {shp}, got {a.shape}")
+            flat[o:o + a.size] = a.reshape(-1)
+        return torch.as_tensor(flat).to(self.device)
+
+    def trpo_unpack(self, flat) -> List[np.ndarray]:
+        f = flat.detach().cpu().numpy() if hasattr(flat, "detach") else np.asarray(flat, np.float32)
+        return [f[o:o + int(np.prod(shp))].reshape(shp).copy() for o, shp in self._trpo_slices()[0]]
+
+    @staticmethod
+    def _trpo_par(kw) -> "N.TrpoParams":
+        return N.TrpoParams(delta=float(kw["delta"]), trust_damp=float(kw["trust_damp"]),
+                            kl_maxfactor=float(kw["kl_maxfactor"]), ent_targ=float(kw.get("ent_targ", 0.0)),
+                            alpha_lr=float(kw.get("alpha_lr", 0.0)), cg_it=int(kw["cg_it"]), trust_sub=int(kw["trust_sub"]),
+                            ent_reg=int(bool(kw.get("ent_reg", False))), adv_center=int(bool(kw.get("adv_center", True))),
+                            adv_scale=int(bool(kw.get("adv_scale", True))))
+
+    def trpo_begin(self, s, a, adv, **params) -> int:
+        """trpo.py:36-63, :170-176: the rollout becomes the table; neglogp_old, the reference distribution and
+        the mean entropy as ppo_begin; the surrogate gradient pg_vec stays on the device (trpo_grad); alpha's
+        step with ent_reg.  params: delta, cg_it, trust_sub, trust_damp, kl_maxfactor, ent_reg, ent_targ,
+        alpha_lr, adv_center, adv_scale.  Returns n."""
+        self._trpo_need()
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        n = int(x.shape[0])
+        w = self._dev(adv, (-1,))
+        if int(u.shape[0]) != n or int(w.shape[0]) != n:
+            raise ValueError("s, a and adv need the same number of rows")
+        par = self._trpo_par(params)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        N.check(self.lib.sacx_trpo_begin(self.h, p(x), p(u), p(w), n, ctypes.byref(par)), self.h, "trpo_begin")
+        self._keep_ppo = (x, u, w)
+        return n
+
+    def trpo_grad(self, flat: bool = False):
+        """pg_vec of the last trpo_begin: the trainables' list (Keras order), or the flat device vector."""
+        self._trpo_need()
+        out = torch.empty((self.trpo_flat_len(),), dtype=torch.float32, device=self.device)
+        N.check(self.lib.sacx_trpo_grad(self.h, ctypes.c_void_p(out.data_ptr())), self.h, "trpo_grad")
+        return out if flat else self.trpo_unpack(out)
+
+    def trpo_fvp(self, x, eager: bool = False, flat: bool = False):
+        """One Fisher-vector product F(x) = H x + trust_damp x (trpo.py:200-227) at the weights as they
+        stand, on the rows s_all[::trust_sub] of the last trpo_begin.  x: the trainables' list (Keras order)
+        or a flat device vector; the result in the same form unless ``flat``."""
+        self._trpo_need()
+        is_flat = hasattr(x, "is_cuda")
+        xv = x.contiguous() if is_flat else self.trpo_pack(x)
+        if int(xv.numel()) != self.trpo_flat_len():
+            raise ValueError(f"a flat direction holds {self.trpo_flat_len()} floats")
+        out = torch.empty_like(xv)
+        N.check(self.lib.sacx_trpo_fvp(self.h, ctypes.c_void_p(xv.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                       N.STEP_EAGER if eager else 0), self.h, "trpo_fvp")
+        self._keep_trpo = (xv,)
+        return out if (flat or is_flat) else self.trpo_unpack(out)
+
+    def trpo_step(self, eager: bool = False, **params) -> dict:
+        """trpo.py:178-198, :229-317: conjugate gradient, the scaling, the backtracking line search.
+        Returns ent, tv_pre, kl_pre, tv, kl, adj, improve, alpha.  Synchronous."""
+        self._trpo_need()
+        par = self._trpo_par(params)
+        out = (ctypes.c_double * 8)()
+        N.check(self.lib.sacx_trpo_step(self.h, ctypes.byref(par), N.STEP_EAGER if eager else 0, out), self.h, "trpo_step")
+        keys = ("ent", "tv_pre", "kl_pre", "tv", "kl", "adj", "improve", "alpha")
+        d = {k: np.float32(out[i]) for i, k in enumerate(keys)}
+        d["adj"] = float(out[5])
+        return d
+
+    def trpo_solve_info(self) -> dict:
+        """Device scalars of the last trpo_step's solve: vFv, eta, the CG iterations run, the last r.r."""
+        self._trpo_need()
+        sc = self.v["trpo.sc"].cpu().numpy().reshape(-1)
+        return dict(gmax=float(sc[0]), vFv=float(sc[1]), eta=float(sc[2]), cg_iters=int(sc[3]), rr=float(sc[4]))
+
+    def trpo_plan_info(self, rows: int) -> List[dict]:
+        """The launches of one Fisher product over ``rows`` rows."""
+        self._trpo_need()
+        n = ctypes.c_int32()
+        N.check(self.lib.sacx_trpo_plan_info(self.h, int(rows), None, 0, ctypes.byref(n)), self.h, "trpo_plan_info")
+        arr = (N.LaunchInfo * n.value)()
+        N.check(self.lib.sacx_trpo_plan_info(self.h, int(rows), arr, n.value, ctypes.byref(n)), self.h, "trpo_plan_info")
         return [dict(name=a.name.decode(), kernel=a.kernel.decode(), grid=a.grid, block=a.block,
                      flops=a.flops, bytes=a.bytes) for a in arr]
 

@@ -64,7 +64,7 @@ def kernel_scratch(so_path):
 
 
 # every translation unit with kernels must be among what was read: one name of each
-REQUIRED = ("k_gemm", "k_vc_gather", "k_gae_apply")
+REQUIRED = ("k_gemm", "k_vc_gather", "k_gae_apply", "k_trpo_cg")
 
 
 def main():
