@@ -1841,6 +1841,225 @@ int add_gemm_split(sacx_handle* h, std::vector<Launch>& plan, const std::string&
     return n;
 }
 
+// ---------------------------------------------------------------- shared plan builders
+// What the per-layer plans (generic SAC / SAC-EO, BC, the PPO step, a TRPO chunk) have in common: the
+// actor's forward, dX and dW chains over a caller's buffers, and the world models' expert-row problems.
+// What is specific to a caller (EPI_STORE, bscale, t_adv, the data-parallel split, folds) it applies to
+// what these return.
+
+// hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
+float* chain_buf(sacx_handle* h, const std::string& p, int i, int D) {
+    if (i == 0) return h->f(p + "1");
+    if (i == D - 1) return h->f(p + "2");
+    return h->f(p + "m" + std::to_string(i));
+}
+
+std::string layer_name(const std::string& net, int i) { return net + ".l" + std::to_string(i); }
+
+// --actor_layer_norm puts Dense -> LayerNorm -> tanh on layer 0 (nn_utils.py:110-119).  Forward: k_ln on
+// rows [r0, r1) of the pre-norm output Z, caching xhat / rstd for the rows below cache_rows
+Launch ln_fwd_launch(sacx_handle* h, const std::string& name, float* Z, int r0, int r1, float* xhat, float* rstd,
+                     int cache_rows) {
+    const int M = r1 - r0, H0 = h->H0;
+    Launch L{};
+    L.kind = Launch::LNORM;
+    L.name = name;
+    LNArgs& a = L.ln;
+    a.mode = 0; a.H = H0; a.Z = Z; a.nrange = 1; a.r[0] = r0; a.r[1] = r1;
+    a.gamma = h->f("actor.ln"); a.xhat = xhat; a.rstd = rstd; a.cache_rows = cache_rows;
+    L.grid = (M + 3) / 4;
+    L.flops = 8.0 * M * H0;
+    L.bytes = 4.0 * M * H0 * 3;
+    return L;
+}
+
+// Backward: dY -> dZ through the norm on rows [0, M) of dY (cache rows from xrow0); dY*xhat, dY for gamma / beta
+Launch ln_bwd_launch(sacx_handle* h, float* dY, int M, float* xhat, float* rstd, int xrow0, float* gy, float* gb) {
+    const int H0 = h->H0;
+    Launch N{};
+    N.kind = Launch::LNORM;
+    N.name = "actor.ln.bwd";
+    LNArgs& a = N.ln;
+    a.mode = 1; a.H = H0; a.Z = dY; a.r[1] = M; a.gamma = h->f("actor.ln");
+    a.xhat = xhat; a.rstd = rstd; a.xrow0 = xrow0;
+    a.gy = gy; a.gb = gb;
+    N.grid = (M + 3) / 4;
+    N.flops = 8.0 * M * H0;
+    N.bytes = 4.0 * M * H0 * 5;
+    return N;
+}
+
+// Where one pass through the actor lives.  The forward reads M rows of X and writes rows
+// [hrow0, hrow0 + M) of the hidden buffers H[i]; the dX and dW problems read those rows beside rows
+// [0, M) of the delta buffers D[i], of D3 (the delta at the output layer) and of E (the logstd rows).
+struct ActorPass {
+    const float* X; int ldx;                // the input rows and their leading dimension
+    int M;                                  // rows
+    int hrow0;                              // first row of the pass in H[i] (and in the layer-norm cache: xrow0)
+    std::vector<float*> H, D;               // per hidden layer: output, delta
+    float *D3, *E;
+    float *xhat, *rstd; int cache_rows;     // layer norm: the forward's cache
+    float *gy, *gb;                         //             the backward's rows for the gamma / beta sums
+};
+
+// the update plans' workspace: ws.Ha / ws.Da, ws.Da3, ws.E, ws.ln_*
+ActorPass actor_pass_ws(sacx_handle* h, const float* X, int M, int hrow0, int cache_rows) {
+    const int Da = h->nd[0].D();
+    ActorPass c{};
+    c.X = X; c.ldx = h->ldS; c.M = M; c.hrow0 = hrow0; c.cache_rows = cache_rows;
+    for (int i = 0; i < Da; ++i) {
+        c.H.push_back(chain_buf(h, "ws.Ha", i, Da));
+        c.D.push_back(chain_buf(h, "ws.Da", i, Da));
+    }
+    c.D3 = h->f("ws.Da3"); c.E = h->f("ws.E");
+    if (h->ln) {
+        c.xhat = h->f("ws.ln_xhat"); c.rstd = h->f("ws.ln_rstd"); c.gy = h->f("ws.ln_gy"); c.gb = h->f("ws.ln_gb");
+    }
+    return c;
+}
+
+// <name><i> for every hidden layer, k_ln (`ln_name`) behind layer 0's
+void actor_fwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass& c, const std::string& name,
+                     const std::string& ln_name, bool record_probs) {
+    const NetDims& na = h->nd[0];
+    for (int i = 0; i < na.D(); ++i) {
+        const float* in = i == 0 ? c.X : c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1];
+        const int ldi = i == 0 ? c.ldx : na.h[i - 1], K = i == 0 ? h->S : na.h[i - 1];
+        add_gemm(h, plan, name + std::to_string(i),
+                 {prob_fwd(in, ldi, c.M, K, h->f(layer_name("actor", i)), na.h[i], c.H[i] + (size_t)c.hrow0 * na.h[i],
+                           (i == 0 && h->ln) ? ACT_NONE : na.act[i])},
+                 record_probs);
+        if (i == 0 && h->ln)
+            plan.push_back(ln_fwd_launch(h, ln_name, c.H[0], c.hrow0, c.hrow0 + c.M, c.xhat, c.rstd, c.cache_rows));
+    }
+}
+
+// actor.bwd<i> from layer `from` down to 1: the delta at layer i's output (D3 at the output layer) to
+// layer i - 1's, with tanh' at the norm's output under layer norm; then actor.ln.bwd
+void actor_bwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass& c, int from, bool record_probs) {
+    const NetDims& na = h->nd[0];
+    const int Da = na.D();
+    for (int i = from; i >= 1; --i)
+        add_gemm(h, plan, "actor.bwd" + std::to_string(i),
+                 {prob_dx(i == Da ? c.D3 : c.D[i], c.M, i == Da ? h->Aout : na.h[i], h->f(layer_name("actor", i)), na.h[i - 1],
+                          c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1], c.D[i - 1], (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
+                 record_probs);
+    if (h->ln) plan.push_back(ln_bwd_launch(h, c.D[0], c.M, c.xhat, c.rstd, c.hrow0, c.gy, c.gb));
+}
+
+// the actor's dW problems in parameter order: layers 0 .. Da-1, the output layer, logstd unless
+// per_state_std, gamma and beta under layer norm
+std::vector<GemmProb> actor_dw_probs(sacx_handle* h, const ActorPass& c) {
+    const NetDims& na = h->nd[0];
+    const int Da = na.D(), H0 = h->H0, H1 = h->H1;
+    std::vector<GemmProb> pw;
+    for (int i = 0; i < Da; ++i) {
+        const float* Xi = i == 0 ? c.X : c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1];
+        const int K = i == 0 ? h->S : na.h[i - 1];
+        pw.push_back(prob_dw(Xi, i == 0 ? c.ldx : K, K, c.M, c.D[i], na.h[i], h->f(layer_name("actor", i)), nullptr, GRP_PI));
+    }
+    pw.push_back(prob_dw(c.H[Da - 1] + (size_t)c.hrow0 * H1, H1, H1, c.M, c.D3, h->Aout, h->f(layer_name("actor", Da)), nullptr,
+                         GRP_PI));
+    if (!h->cfg.per_state_std) {
+        GemmProb p = prob_dw(c.E, 1, 0, c.M, c.E, h->A, h->f("actor.logstd"), nullptr, GRP_PI);
+        p.ones_row = 0;   // single all-ones row: column sums of E
+        pw.push_back(p);
+    }
+    if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
+        for (int k = 0; k < 2; ++k) {
+            float* gsrc = k ? c.gb : c.gy;
+            GemmProb p = prob_dw(gsrc, 1, 0, c.M, gsrc, H0, h->f("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
+            p.ones_row = 0;
+            pw.push_back(p);
+        }
+    }
+    return pw;
+}
+
+// The actor's trainables are one contiguous parameter range, actor.l0 .. actor.logstd (with per_state_std
+// the logstd variable is no trainable: its gradient stays 0 and Adam leaves it): its base (null before
+// sacx_bind) and float count
+struct ParamRange { float* P; int64_t n; };
+ParamRange actor_range(const sacx_handle* h) {
+    const SegInfo& sl = h->seg("actor.logstd");
+    return {h->arena ? h->f("actor.l0") : nullptr,
+            (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4)};
+}
+
+// the trainable GaussianActor's distribution over the output rows O [m, Aout]
+PpoDist ppo_dist(sacx_handle* h, const float* O) {
+    PpoDist d{};
+    d.O = O; d.A = h->A; d.Aout = h->Aout; d.per_state_std = h->cfg.per_state_std;
+    d.logstd = h->f("actor.logstd");
+    // logstd_init (continuous_actors.py:39-44), f32, as sacx_actor_act's
+    const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+    d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    return d;
+}
+
+// The expert term's world models (at most two) and their sections of the ne expert rows: model k takes
+// rows [k * half, k * half + mrows) of Xm and of the ws.Hm / ws.Dm chain
+struct ExpertSplit { int nm, mrows, half; };
+ExpertSplit expert_split(const sacx_handle* h) {
+    const int nm = std::min(h->nm, 2);
+    return {nm, nm == 1 ? h->ne : h->ne / 2, h->ne / 2};
+}
+
+// model k's hidden layer i on its rows of Xm = [s_e | pi(s_e)]
+GemmProb model_fwd_prob(sacx_handle* h, const float* Xm, int k, int i) {
+    const ExpertSplit e = expert_split(h);
+    const NetDims& nmd = h->nd[2];
+    const int Dm = nmd.D(), ldQ = h->ldQ;
+    const float* in = i == 0 ? Xm + (size_t)k * e.half * ldQ : chain_buf(h, "ws.Hm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1];
+    return prob_fwd(in, i == 0 ? ldQ : nmd.h[i - 1], e.mrows, i == 0 ? h->S + h->A : nmd.h[i - 1],
+                    h->f(layer_name("m" + std::to_string(k), i)), nmd.h[i], chain_buf(h, "ws.Hm", i, Dm) + (size_t)k * e.half * nmd.h[i],
+                    nmd.act[i]);
+}
+
+// the models' head on the expert rows + the MSE against sp_e (SAC_expert.py:319-332, BC.py:340-352), `mse`
+// its epilogue's flags
+std::vector<GemmProb> model_head_probs(sacx_handle* h, int mse, const float* se_raw, const float* spe_raw) {
+    const ExpertSplit e = expert_split(h);
+    const int S = h->S, Hm1 = h->Hm1, Dm = h->nd[2].D(), mtn = (S + 15) / 16;
+    std::vector<GemmProb> pm;
+    for (int k = 0; k < e.nm; ++k) {
+        float* Wh = h->f(layer_name("m" + std::to_string(k), Dm));
+        GemmProb p{};
+        p.A = h->f("ws.Hm2") + (size_t)k * e.half * Hm1; p.lda = Hm1; p.a_kc = 1; p.ones_row = -1;
+        p.B = Wh; p.ldb = h->Om; p.b_kc = 0;                 // W_ext [(Hm1+1) x Om], Om = S (+1)
+        p.M = e.mrows; p.N = S; p.K = Hm1;                   // delta-s columns only
+        p.bias = Wh + (size_t)Hm1 * h->Om;
+        p.C = h->f("ws.dout") + (size_t)k * e.half * S; p.ldc = S;
+        p.epi = EPI_FWD; p.act = ACT_NONE;
+        p.mse = mse; p.grad_scale = 1.f / (float)e.mrows;    // the mean over the section's rows
+        p.dclip = h->cfg.delta_clip_pred > 0.f ? h->cfg.delta_clip_pred : 0.f;
+        p.se_raw = se_raw + (size_t)k * e.half * S; p.spe_raw = spe_raw + (size_t)k * e.half * S;
+        p.dmean = h->f("mnorm.d_mean"); p.dden = h->f("mnorm.d_den");
+        p.part = h->f("ws.mse") + (size_t)k * e.half * mtn;
+        pm.push_back(p);
+    }
+    return pm;
+}
+
+// the models' dX problems at level i (Dm: from the head's delta-s columns) down to their layer-0 output,
+// the expert rows' action gradient
+std::vector<GemmProb> model_bwd_probs(sacx_handle* h, int i) {
+    const ExpertSplit e = expert_split(h);
+    const NetDims& nmd = h->nd[2];
+    const int Dm = nmd.D(), S = h->S;
+    std::vector<GemmProb> pb;
+    for (int k = 0; k < e.nm; ++k) {
+        const float* D = i == Dm ? h->f("ws.dout") + (size_t)k * e.half * S
+                                 : chain_buf(h, "ws.Dm", i, Dm) + (size_t)k * e.half * nmd.h[i];
+        GemmProb p = prob_dx(D, e.mrows, i == Dm ? S : nmd.h[i], h->f(layer_name("m" + std::to_string(k), i)), nmd.h[i - 1],
+                             chain_buf(h, "ws.Hm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1],
+                             chain_buf(h, "ws.Dm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1], nmd.act[i - 1]);
+        if (i == Dm) p.ldb = h->Om;          // the head's delta-s columns: B[n][k] = W_ext[n][k], stride Om
+        pb.push_back(p);
+    }
+    return pb;
+}
+
 // ---------------------------------------------------------------- the generic update plan
 // Nets of any depth (create_nn's layers list, nn_utils.py:100-138; SACX_GENERIC=1 also at two layers,
 // the parity check of this plan against the fused one): the update of build_plan in the reference's
@@ -1856,22 +2075,16 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
     h->probs_cursor = 0;
-    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, B = h->B, ne = h->ne, Aout = h->Aout;
-    const int Hm1 = h->Hm1, half = ne / 2, Hc1 = h->Hc1;
-    const int nm = std::min(h->nm, 2), mrows = nm == 1 ? ne : half;   // the expert term's models
+    const int S = h->S, A = h->A, H1 = h->H1, B = h->B, ne = h->ne, Aout = h->Aout;
+    const int Hc1 = h->Hc1;
+    const int nm = expert_split(h).nm;      // the expert term's models
     const int ldS = h->ldS, ldQ = h->ldQ, Rb = h->Rb;
     const bool eo = h->cfg.use_expert != 0;
     const NetDims &na = h->nd[0], &nc = h->nd[1], &nmd = h->nd[2];
     const int Da = na.D(), Dc = nc.D(), Dm = eo ? nmd.D() : 0;
     const std::string sl = "slot" + std::to_string(slot);
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
-    // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
-    auto ch = [&](const std::string& p, int i, int D) -> float* {
-        if (i == 0) return W(p + "1");
-        if (i == D - 1) return W(p + "2");
-        return W(p + "m" + std::to_string(i));
-    };
+    auto L_ = layer_name;
     float* noise = h->f(sl + ".noise");
     float* noise_t = noise;
     float* noise_pi = noise + (size_t)B * A;
@@ -1883,31 +2096,8 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     const int Ra4 = (h->Ra + 3) & ~3;       // first row of the alpha rows in the actor chain's buffers
 
     plan_inputs(h, plan, slot);
-    // ---- actor forward on rows [r0, r0 + M) of its chain from X: --actor_layer_norm puts Dense ->
-    // LayerNorm -> tanh on layer 0 (k_ln on the pre-norm output, nn_utils.py:110-119)
-    auto actor_fwd = [&](const std::string& name, const float* X, int r0, int M, bool alpha) {
-        for (int i = 0; i < Da; ++i) {
-            const float* in = i == 0 ? X : ch("ws.Ha", i - 1, Da) + (size_t)r0 * na.h[i - 1];
-            const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
-            const int act = (i == 0 && h->ln) ? ACT_NONE : na.act[i];
-            add_gemm(h, plan, name + std::to_string(i),
-                     {prob_fwd(in, ldi, M, K, W(L_("actor", i)), na.h[i], ch("ws.Ha", i, Da) + (size_t)r0 * na.h[i], act)},
-                     record_probs);
-            if (i == 0 && h->ln) {
-                Launch L{};
-                L.kind = Launch::LNORM;
-                L.name = alpha ? "alpha.ln" : "actor.ln";
-                LNArgs& a = L.ln;
-                a.mode = 0; a.H = H0; a.Z = W("ws.Ha1"); a.nrange = 1; a.r[0] = r0; a.r[1] = r0 + M;
-                a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = h->Ra;
-                L.grid = (M + 3) / 4;
-                L.flops = 8.0 * M * H0;
-                L.bytes = 4.0 * M * H0 * 3;
-                plan.push_back(L);
-            }
-        }
-    };
-    actor_fwd("actor.fwd", Xa, 0, h->Ra, false);
+    // ---- actor forward on all Ra rows of Xa (the layer-norm cache holds them all)
+    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa, h->Ra, 0, h->Ra), "actor.fwd", "actor.ln", record_probs);
     float* Ha_last = W("ws.Ha2");
     auto head_base = [&](HeadArgs& a, const float* H2) {
         a.H2 = H2; a.ldh = H1; a.W3 = W(L_("actor", Da)); a.logstd = W("actor.logstd");
@@ -1943,40 +2133,16 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
         std::vector<GemmProb> ps;
         if (i < Dc)
             for (int k = 0; k < 4; ++k) {
-                const float* in = i == 0 ? (k < 2 ? Xt : Xq) : ch("ws.Hq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
+                const float* in = i == 0 ? (k < 2 ? Xt : Xq) : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
                 ps.push_back(prob_fwd(in, i == 0 ? ldQ : nc.h[i - 1], B, i == 0 ? S + A : nc.h[i - 1], W(L_(qn[k], i)),
-                                      nc.h[i], ch("ws.Hq", i, Dc) + (size_t)k * B * nc.h[i], nc.act[i]));
+                                      nc.h[i], chain_buf(h, "ws.Hq", i, Dc) + (size_t)k * B * nc.h[i], nc.act[i]));
             }
         if (i < Dm)
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                const float* in = i == 0 ? Xm + (size_t)k * half * ldQ : ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1];
-                ps.push_back(prob_fwd(in, i == 0 ? ldQ : nmd.h[i - 1], mrows, i == 0 ? S + A : nmd.h[i - 1], W(L_(n, i)),
-                                      nmd.h[i], ch("ws.Hm", i, Dm) + (size_t)k * half * nmd.h[i], nmd.act[i]));
-            }
+            for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
         add_gemm(h, plan, "q.fwd" + std::to_string(i), ps, record_probs);
     }
-    const int mtn = (S + 15) / 16;
-    if (eo) {   // the world models' head on the expert rows + the expert MSE (SAC_expert.py:319-332)
-        std::vector<GemmProb> pm;
-        for (int k = 0; k < nm; ++k) {
-            const std::string n = "m" + std::to_string(k);
-            GemmProb p{};
-            p.A = W("ws.Hm2") + (size_t)k * half * Hm1; p.lda = Hm1; p.a_kc = 1; p.ones_row = -1;
-            p.B = W(L_(n, Dm)); p.ldb = h->Om; p.b_kc = 0;       // W_ext [(Hm1+1) x Om], Om = S (+1)
-            p.M = mrows; p.N = S; p.K = Hm1;                     // delta-s columns only
-            p.bias = W(L_(n, Dm)) + (size_t)Hm1 * h->Om;
-            p.C = W("ws.dout") + (size_t)k * half * S; p.ldc = S;
-            p.epi = EPI_FWD; p.act = ACT_NONE;
-            p.mse = 1; p.grad_scale = 1.f / (float)mrows;       // MSE_loss = mean over the rows
-            p.dclip = h->cfg.delta_clip_pred > 0.f ? h->cfg.delta_clip_pred : 0.f;
-            p.se_raw = se_raw + (size_t)k * half * S; p.spe_raw = spe_raw + (size_t)k * half * S;
-            p.dmean = W("mnorm.d_mean"); p.dden = W("mnorm.d_den");
-            p.part = W("ws.mse") + (size_t)k * half * mtn;
-            pm.push_back(p);
-        }
-        add_gemm(h, plan, "model.head", pm, record_probs);
-    }
+    if (eo)     // the world models' head on the expert rows + the expert MSE (SAC_expert.py:319-332)
+        add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT, se_raw, spe_raw), record_probs);
     {   // ---- q.head: min target, TD target, critic losses and the delta at the critics' last hidden layer
         Launch L{};
         L.kind = Launch::QHEAD;
@@ -1997,9 +2163,9 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
         for (int k = 0; k < 2; ++k)
-            pb.push_back(prob_dx(ch("ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_(qn[2 + k], i)), nc.h[i - 1],
-                                 ch("ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1],
-                                 ch("ws.Dq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
+            pb.push_back(prob_dx(chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_(qn[2 + k], i)), nc.h[i - 1],
+                                 chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1],
+                                 chain_buf(h, "ws.Dq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
         add_gemm(h, plan, "critic.bwd" + std::to_string(i), pb, record_probs);
     }
     {
@@ -2007,9 +2173,9 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
         for (int k = 0; k < 2; ++k) {
             const std::string n = "q" + std::to_string(k), t = "t" + std::to_string(k);
             for (int i = 0; i < Dc; ++i) {
-                const float* X = i == 0 ? Xq : ch("ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1];
+                const float* X = i == 0 ? Xq : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1];
                 const int K = i == 0 ? S + A : nc.h[i - 1];
-                pw.push_back(prob_dw(X, i == 0 ? ldQ : K, K, B, ch("ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], nc.h[i],
+                pw.push_back(prob_dw(X, i == 0 ? ldQ : K, K, B, chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], nc.h[i],
                                      W(L_(n, i)), W(L_(t, i)), GRP_Q));
             }
             pw.push_back(prob_dw(W("ws.Hq2") + (size_t)(2 + k) * B * Hc1, Hc1, Hc1, B, W("ws.gq") + (size_t)k * B, 1,
@@ -2022,9 +2188,9 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (int i = 0; i < Dc; ++i) {
         std::vector<GemmProb> ps;
         for (int k = 0; k < 2; ++k) {
-            const float* in = i == 0 ? Xp : ch("ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
+            const float* in = i == 0 ? Xp : chain_buf(h, "ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
             ps.push_back(prob_fwd(in, i == 0 ? ldQ : nc.h[i - 1], B, i == 0 ? S + A : nc.h[i - 1],
-                                  W(L_("q" + std::to_string(k), i)), nc.h[i], ch("ws.Hp", i, Dc) + (size_t)k * B * nc.h[i],
+                                  W(L_("q" + std::to_string(k), i)), nc.h[i], chain_buf(h, "ws.Hp", i, Dc) + (size_t)k * B * nc.h[i],
                                   nc.act[i]));
         }
         add_gemm(h, plan, "pi.q.fwd" + std::to_string(i), ps, record_probs);
@@ -2049,25 +2215,13 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
         for (int k = 0; k < 2; ++k)
-            pb.push_back(prob_dx(ch("ws.Dp", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_("q" + std::to_string(k), i)),
-                                 nc.h[i - 1], ch("ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1],
-                                 ch("ws.Dp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
+            pb.push_back(prob_dx(chain_buf(h, "ws.Dp", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_("q" + std::to_string(k), i)),
+                                 nc.h[i - 1], chain_buf(h, "ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1],
+                                 chain_buf(h, "ws.Dp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
         add_gemm(h, plan, "pi.q.bwd" + std::to_string(i), pb, record_probs);
     }
     if (eo)     // the world models' backward to their layer-0 output (the expert rows' action gradient)
-        for (int i = Dm; i >= 1; --i) {
-            std::vector<GemmProb> pb;
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                const float* D = i == Dm ? W("ws.dout") + (size_t)k * half * S : ch("ws.Dm", i, Dm) + (size_t)k * half * nmd.h[i];
-                GemmProb p = prob_dx(D, mrows, i == Dm ? S : nmd.h[i], W(L_(n, i)), nmd.h[i - 1],
-                                     ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1],
-                                     ch("ws.Dm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1], nmd.act[i - 1]);
-                if (i == Dm) p.ldb = h->Om;          // the head's delta-s columns: B[n][k] = W_ext[n][k], stride Om
-                pb.push_back(p);
-            }
-            add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
-        }
+        for (int i = Dm; i >= 1; --i) add_gemm(h, plan, "model.bwd" + std::to_string(i), model_bwd_probs(h, i), record_probs);
     // ---- actor backward: action gradients -> tanh-Gaussian backward -> the delta at the last hidden
     // layer (k_actor_bwd, from the loss-scaled deltas: gpol = null), dX to layer 0, dW + Adam
     {
@@ -2091,52 +2245,15 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
         L.bytes = 4.0 * (2.0 * B * h->Hc0 + ne * h->Hm0 + 2.0 * Rb * H1);
         plan.push_back(L);
     }
-    for (int i = Da - 1; i >= 1; --i)
-        add_gemm(h, plan, "actor.bwd" + std::to_string(i),
-                 {prob_dx(ch("ws.Da", i, Da), Rb, na.h[i], W(L_("actor", i)), na.h[i - 1],
-                          ch("ws.Ha", i - 1, Da) + (size_t)B * na.h[i - 1], ch("ws.Da", i - 1, Da),
-                          (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
-                 record_probs);
-    if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
-        Launch N{};
-        N.kind = Launch::LNORM;
-        N.name = "actor.ln.bwd";
-        LNArgs& a = N.ln;
-        a.mode = 1; a.H = H0; a.Z = W("ws.Da1"); a.r[1] = Rb; a.gamma = W("actor.ln");
-        a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = B;
-        a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
-        N.grid = (Rb + 3) / 4;
-        N.flops = 8.0 * Rb * H0;
-        N.bytes = 4.0 * Rb * H0 * 5;
-        plan.push_back(N);
-    }
-    {
-        std::vector<GemmProb> pw;
-        for (int i = 0; i < Da; ++i) {
-            const float* X = i == 0 ? Xa + (size_t)B * ldS : ch("ws.Ha", i - 1, Da) + (size_t)B * na.h[i - 1];
-            const int K = i == 0 ? S : na.h[i - 1];
-            pw.push_back(prob_dw(X, i == 0 ? ldS : K, K, Rb, ch("ws.Da", i, Da), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
-        }
-        pw.push_back(prob_dw(Ha_last + (size_t)B * H1, H1, H1, Rb, W("ws.Da3"), Aout, W(L_("actor", Da)), nullptr, GRP_PI));
-        if (!h->cfg.per_state_std) {
-            GemmProb p = prob_dw(W("ws.E"), 1, 0, Rb, W("ws.E"), A, W("actor.logstd"), nullptr, GRP_PI);
-            p.ones_row = 0;   // single all-ones row: column sums of E
-            pw.push_back(p);
-        }
-        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
-            for (int k = 0; k < 2; ++k) {
-                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
-                GemmProb p = prob_dw(gsrc, 1, 0, Rb, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
-                p.ones_row = 0;
-                pw.push_back(p);
-            }
-        }
-        const int n = add_gemm_split(h, plan, "actor.adam", pw, record_probs);
+    {   // the policy and expert rows: rows [B, B + Rb) of Xa and of the hidden buffers, [0, Rb) of the deltas
+        const ActorPass bw = actor_pass_ws(h, Xa + (size_t)B * ldS, Rb, B, h->Ra);
+        actor_bwd_chain(h, plan, bw, Da - 1, record_probs);
+        const int n = add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, bw), record_probs);
         if (h->dp_ranks > 0) dp_split_adam(h, plan, "actor.l0", "actor.logstd", "", GRP_PI, n);
     }
     // ---- alpha: the updated actor on s, evaluate, Adam on alpha, statistics
     const size_t alpha_first = plan.size();
-    actor_fwd("alpha.fwd", Xa + (size_t)B * ldS, Ra4, B, true);
+    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa + (size_t)B * ldS, B, Ra4, h->Ra), "alpha.fwd", "alpha.ln", record_probs);
     {
         Launch L{};
         L.kind = Launch::AHEAD;
@@ -2183,52 +2300,32 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     plan.clear();
     h->probs_cursor = 0;
     const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, ne = h->ne, Aout = h->Aout;
-    const int Hm0 = h->Hm0, Hm1 = h->Hm1, half = ne / 2;
-    const int nm = std::min(h->nm, 2), mrows = nm == 1 ? ne : half;   // the expert term's models
-    const int ldS = h->ldS, ldQ = h->ldQ;
+    const int Hm0 = h->Hm0, half = ne / 2;
+    const int nm = expert_split(h).nm;      // the expert term's models
+    const int ldQ = h->ldQ;
     const bool fold = !h->deep;
     const NetDims &na = h->nd[0], &nmd = h->nd[2];
     const int Da = na.D(), Dm = nmd.D();
     const std::string sl = "slot" + std::to_string(slot);
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
-    auto ch = [&](const std::string& p, int i, int D) -> float* {     // as build_plan_generic's
-        if (i == 0) return W(p + "1");
-        if (i == D - 1) return W(p + "2");
-        return W(p + "m" + std::to_string(i));
-    };
+    auto L_ = layer_name;
     float* noise_e = h->f(sl + ".noise");
     float *Xa = W(sl + ".Xa"), *Xm = W(sl + ".Xm"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
     float* Ha_last = W("ws.Ha2");
 
     plan_inputs(h, plan, slot);
     const size_t body0 = plan.size();
-    // ---- actor forward on the expert rows
+    // ---- actor forward on the expert rows: rows [0, ne) of every actor-side buffer
+    const ActorPass ap = actor_pass_ws(h, Xa, ne, 0, ne);
     const int tqh = (H1 + 15) / 16;
     const bool head_part = fold && Aout <= 8 && H1 <= 256 && H1 % 64 == 0 && h->tile32_plan == 0;
-    for (int i = 0; i < Da; ++i) {
-        const float* in = i == 0 ? Xa : ch("ws.Ha", i - 1, Da);
-        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
-        GemmProb p = prob_fwd(in, ldi, ne, K, W(L_("actor", i)), na.h[i], ch("ws.Ha", i, Da),
-                              (i == 0 && h->ln) ? ACT_NONE : na.act[i]);
-        if (head_part && i == Da - 1) {      // the head's Ha2 . W3 as per-column-tile partials (rowk 5)
-            p.pw = W(L_("actor", Da)); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;
-            p.ppart = W("ws.hpart");
-        }
-        add_gemm(h, plan, "actor.fwd" + std::to_string(i), {p}, record_probs);
-        if (head_part && i == Da - 1) plan.back().gemm.rowk = 5;
-        if (i == 0 && h->ln) {
-            Launch L{};
-            L.kind = Launch::LNORM;
-            L.name = "actor.ln";
-            LNArgs& a = L.ln;
-            a.mode = 0; a.H = H0; a.Z = W("ws.Ha1"); a.nrange = 1; a.r[0] = 0; a.r[1] = ne;
-            a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = ne;
-            L.grid = (ne + 3) / 4;
-            L.flops = 8.0 * ne * H0;
-            L.bytes = 4.0 * ne * H0 * 3;
-            plan.push_back(L);
-        }
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", record_probs);
+    if (head_part) {                         // the head's Ha2 . W3 as per-column-tile partials of the last layer (rowk 5)
+        GemmArgs& g = plan.back().gemm;      // (two layers: the norm's launch is behind layer 0's)
+        GemmProb& p = g.probs[0];
+        p.pw = W(L_("actor", Da)); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;
+        p.ppart = W("ws.hpart");
+        g.rowk = 5;
     }
     if (fold && !h->ln && h->fwd2) fuse_fwd2(h, plan, "actor.fwd01");
     {   // ---- actor head: sample(s_e) into the models' input rows (their normaliser for the action columns)
@@ -2256,12 +2353,7 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     // ---- world models 0 / 1 forward on [s_e | pi(s_e)]
     for (int i = 0; i < Dm; ++i) {
         std::vector<GemmProb> ps;
-        for (int k = 0; k < nm; ++k) {
-            const std::string n = "m" + std::to_string(k);
-            const float* in = i == 0 ? Xm + (size_t)k * half * ldQ : ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1];
-            ps.push_back(prob_fwd(in, i == 0 ? ldQ : nmd.h[i - 1], mrows, i == 0 ? S + A : nmd.h[i - 1], W(L_(n, i)),
-                                  nmd.h[i], ch("ws.Hm", i, Dm) + (size_t)k * half * nmd.h[i], nmd.act[i]));
-        }
+        for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
         add_gemm(h, plan, "model.fwd" + std::to_string(i), ps, record_probs);
     }
     if (fold && h->fwd2 && S + A <= 32) {    // the pair as one k_fwd2 launch (rowk 9: layer 0 up to 512 wide)
@@ -2272,26 +2364,8 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         }
     }
     const int mtn = (S + 15) / 16;
-    {   // ---- the models' head + the MSE (BC.py:340-352), weight 1
-        std::vector<GemmProb> pm;
-        for (int k = 0; k < nm; ++k) {
-            const std::string n = "m" + std::to_string(k);
-            GemmProb p{};
-            p.A = W("ws.Hm2") + (size_t)k * half * Hm1; p.lda = Hm1; p.a_kc = 1; p.ones_row = -1;
-            p.B = W(L_(n, Dm)); p.ldb = h->Om; p.b_kc = 0;       // W_ext [(Hm1+1) x Om], Om = S (+1)
-            p.M = mrows; p.N = S; p.K = Hm1;                     // delta-s columns only
-            p.bias = W(L_(n, Dm)) + (size_t)Hm1 * h->Om;
-            p.C = W("ws.dout") + (size_t)k * half * S; p.ldc = S;
-            p.epi = EPI_FWD; p.act = ACT_NONE;
-            p.mse = MSE_EXPERT | MSE_BC; p.grad_scale = 1.f / (float)mrows;   // the mean over the section's rows
-            p.dclip = h->cfg.delta_clip_pred > 0.f ? h->cfg.delta_clip_pred : 0.f;
-            p.se_raw = se_raw + (size_t)k * half * S; p.spe_raw = spe_raw + (size_t)k * half * S;
-            p.dmean = W("mnorm.d_mean"); p.dden = W("mnorm.d_den");
-            p.part = W("ws.mse") + (size_t)k * half * mtn;
-            pm.push_back(p);
-        }
-        add_gemm(h, plan, "model.head", pm, record_probs);
-    }
+    // ---- the models' head + the MSE (BC.py:340-352), weight 1
+    add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT | MSE_BC, se_raw, spe_raw), record_probs);
     FinalArgs fin{};
     fin.alpha = W("alpha"); fin.alpha_m = fin.alpha + h->p_stride; fin.alpha_v = fin.alpha + 2 * h->p_stride;
     fin.ctl = h->ctl();
@@ -2304,23 +2378,15 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     const bool fold_hbw = fold && Aout <= 8 && H1 <= 256 && H1 % 16 == 0 && Hm0 <= 512 && Hm0 % 64 == 0 &&
                           h->tile32_plan == 0;
     for (int i = Dm; i >= 1; --i) {
-        std::vector<GemmProb> pb;
-        for (int k = 0; k < nm; ++k) {
-            const std::string n = "m" + std::to_string(k);
-            const float* D = i == Dm ? W("ws.dout") + (size_t)k * half * S : ch("ws.Dm", i, Dm) + (size_t)k * half * nmd.h[i];
-            GemmProb p = prob_dx(D, mrows, i == Dm ? S : nmd.h[i], W(L_(n, i)), nmd.h[i - 1],
-                                 ch("ws.Hm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1],
-                                 ch("ws.Dm", i - 1, Dm) + (size_t)k * half * nmd.h[i - 1], nmd.act[i - 1]);
-            if (i == Dm) p.ldb = h->Om;          // the head's delta-s columns: B[n][k] = W_ext[n][k], stride Om
-            if (i == 1 && fold_hbw) {            // partial action gradients instead of Dm1 (read by no one else)
-                p.pw = W(L_(n, 0)) + (size_t)S * Hm0;   // action rows of W_ext
-                p.pw_ld = Hm0;
-                p.pw_cs = 1;
-                p.pw_n = A;
-                p.ppart = W("ws.mpart") + (size_t)k * half * A * tqm;
-                p.C = nullptr;
-            }
-            pb.push_back(p);
+        std::vector<GemmProb> pb = model_bwd_probs(h, i);
+        for (int k = 0; k < nm && i == 1 && fold_hbw; ++k) {   // partial action gradients instead of Dm1 (read by no one else)
+            GemmProb& p = pb[k];
+            p.pw = W(L_("m" + std::to_string(k), 0)) + (size_t)S * Hm0;   // action rows of W_ext
+            p.pw_ld = Hm0;
+            p.pw_cs = 1;
+            p.pw_n = A;
+            p.ppart = W("ws.mpart") + (size_t)k * half * A * tqm;
+            p.C = nullptr;
         }
         add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
         Launch& L = plan.back();
@@ -2370,48 +2436,12 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         L.flops = 2.0 * ne * Hm0 * A + 2.0 * ne * H1 * Aout;
         L.bytes = 4.0 * (ne * Hm0 + 2.0 * ne * H1);
         plan.push_back(L);
-        for (int i = Da - 1; i >= 1; --i)
-            add_gemm(h, plan, "actor.bwd" + std::to_string(i),
-                     {prob_dx(ch("ws.Da", i, Da), ne, na.h[i], W(L_("actor", i)), na.h[i - 1], ch("ws.Ha", i - 1, Da),
-                              ch("ws.Da", i - 1, Da), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
-                     record_probs);
     }
-    if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
-        Launch N{};
-        N.kind = Launch::LNORM;
-        N.name = "actor.ln.bwd";
-        LNArgs& a = N.ln;
-        a.mode = 1; a.H = H0; a.Z = W("ws.Da1"); a.r[1] = ne; a.gamma = W("actor.ln");
-        a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = 0;
-        a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
-        N.grid = (ne + 3) / 4;
-        N.flops = 8.0 * ne * H0;
-        N.bytes = 4.0 * ne * H0 * 5;
-        plan.push_back(N);
-    }
+    // (the folded head backward is layer 1's dX already: the norm's backward alone follows it)
+    actor_bwd_chain(h, plan, ap, fold_hbw ? 0 : Da - 1, record_probs);
     {
-        std::vector<GemmProb> pw;
-        for (int i = 0; i < Da; ++i) {
-            const float* X = i == 0 ? Xa : ch("ws.Ha", i - 1, Da);
-            const int K = i == 0 ? S : na.h[i - 1];
-            pw.push_back(prob_dw(X, i == 0 ? ldS : K, K, ne, ch("ws.Da", i, Da), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
-        }
-        pw.push_back(prob_dw(Ha_last, H1, H1, ne, W("ws.Da3"), Aout, W(L_("actor", Da)), nullptr, GRP_PI));
-        if (!h->cfg.per_state_std) {
-            GemmProb p = prob_dw(W("ws.E"), 1, 0, ne, W("ws.E"), A, W("actor.logstd"), nullptr, GRP_PI);
-            p.ones_row = 0;   // single all-ones row: column sums of E
-            pw.push_back(p);
-        }
-        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
-            for (int k = 0; k < 2; ++k) {
-                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
-                GemmProb p = prob_dw(gsrc, 1, 0, ne, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
-                p.ones_row = 0;
-                pw.push_back(p);
-            }
-        }
         const size_t first = plan.size();
-        add_gemm_split(h, plan, "actor.adam", pw, record_probs);
+        add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, ap), record_probs);
         for (size_t i = first; i < plan.size(); ++i) plan[i].gemm.t_adv = fin_folded ? 1 : 0;
     }
     if (!fin_folded) {
@@ -2456,11 +2486,6 @@ void build_model_plan(sacx_handle* h) {
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
     // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
-    auto ch = [&](const std::string& p, int i, int D) -> float* {
-        if (i == 0) return W(p + "1");
-        if (i == D - 1) return W(p + "2");
-        return W(p + "m" + std::to_string(i));
-    };
     float *Xf = W("ws.Xf"), *Tf = W("ws.Tf"), *Of = W("ws.Of");
     float *Df3 = W("ws.Df3");
     MGatherArgs mg{};
@@ -2512,11 +2537,11 @@ void build_model_plan(sacx_handle* h) {
         const size_t r0 = (size_t)k * mb;
         for (int i = 0; i <= Dm; ++i) {
             const bool head = i == Dm;
-            const float* in = i == 0 ? Xin + r0 * ldQ : ch("ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
+            const float* in = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
             const int K = i == 0 ? S + A : nmd.h[i - 1];
             if (!head) {
                 f[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, mb, K, W(L_(n, i)), nmd.h[i],
-                                        ch("ws.Hf", i, Dm) + r0 * nmd.h[i], nmd.act[i]));
+                                        chain_buf(h, "ws.Hf", i, Dm) + r0 * nmd.h[i], nmd.act[i]));
             } else {
                 f[i].push_back(prob_fwd(in, K, mb, K, W(L_(n, i)), Om, fuse ? Df3 + r0 * ldO : Of + r0 * O, ACT_NONE));
                 if (fuse) {   // MSEModel / GaussianModel.get_loss as the head's epilogue: C = d loss / d out, partials
@@ -2534,9 +2559,9 @@ void build_model_plan(sacx_handle* h) {
         }
         for (int i = Dm; i >= 1; --i) {
             const bool head = i == Dm;
-            GemmProb p = prob_dx(head ? Df3 + r0 * ldO : ch("ws.Df", i, Dm) + r0 * nmd.h[i], mb, head ? Om : nmd.h[i],
-                                 W(L_(n, i)), nmd.h[i - 1], ch("ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1],
-                                 ch("ws.Df", i - 1, Dm) + r0 * nmd.h[i - 1], nmd.act[i - 1]);
+            GemmProb p = prob_dx(head ? Df3 + r0 * ldO : chain_buf(h, "ws.Df", i, Dm) + r0 * nmd.h[i], mb, head ? Om : nmd.h[i],
+                                 W(L_(n, i)), nmd.h[i - 1], chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1],
+                                 chain_buf(h, "ws.Df", i - 1, Dm) + r0 * nmd.h[i - 1], nmd.act[i - 1]);
             if (head) p.lda = ldO;
             if (bfold && i == 1) {   // A = D2 generated from H2, D3 and W2 on load; column tile 0 stores it for model.adam
                 p.A = W("ws.Hf2") + r0 * nmd.h[1]; p.wgen = W(L_(n, 2)); p.gen_act = nmd.act[1];
@@ -2546,9 +2571,9 @@ void build_model_plan(sacx_handle* h) {
         }
         for (int i = 0; i <= Dm; ++i) {
             const bool head = i == Dm;
-            const float* X = i == 0 ? Xin + r0 * ldQ : ch("ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
+            const float* X = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
             const int K = i == 0 ? S + A : nmd.h[i - 1];
-            w.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Df3 + r0 * ldO : ch("ws.Df", i, Dm) + r0 * nmd.h[i],
+            w.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Df3 + r0 * ldO : chain_buf(h, "ws.Df", i, Dm) + r0 * nmd.h[i],
                                 head ? Om : nmd.h[i], W(L_(n, i)), nullptr, GRP_MODEL));
             if (head) w.back().ldb = ldO;
         }
@@ -2562,11 +2587,11 @@ void build_model_plan(sacx_handle* h) {
             const std::string n = "r" + std::to_string(k);
             const size_t r0 = (size_t)k * mb;
             for (int i = 0; i <= Dr; ++i) {
-                const float* in = i == 0 ? Xin + r0 * ldQ : ch("ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
+                const float* in = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
                 const int K = i == 0 ? S + A : nrd.h[i - 1];
                 if (i < Dr) {
                     f[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, mb, K, W(L_(n, i)), nrd.h[i],
-                                            ch("ws.Hrf", i, Dr) + r0 * nrd.h[i], nrd.act[i]));
+                                            chain_buf(h, "ws.Hrf", i, Dr) + r0 * nrd.h[i], nrd.act[i]));
                 } else {
                     f[i].push_back(prob_fwd(in, K, mb, K, W(L_(n, i)), 1, Dr3 + r0 * 4, ACT_NONE));
                     GemmProb& p = f[i].back();
@@ -2578,17 +2603,17 @@ void build_model_plan(sacx_handle* h) {
             }
             for (int i = Dr; i >= 1; --i) {
                 const bool head = i == Dr;
-                GemmProb p = prob_dx(head ? Dr3 + r0 * 4 : ch("ws.Drf", i, Dr) + r0 * nrd.h[i], mb, head ? 1 : nrd.h[i],
-                                     W(L_(n, i)), nrd.h[i - 1], ch("ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1],
-                                     ch("ws.Drf", i - 1, Dr) + r0 * nrd.h[i - 1], nrd.act[i - 1]);
+                GemmProb p = prob_dx(head ? Dr3 + r0 * 4 : chain_buf(h, "ws.Drf", i, Dr) + r0 * nrd.h[i], mb, head ? 1 : nrd.h[i],
+                                     W(L_(n, i)), nrd.h[i - 1], chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1],
+                                     chain_buf(h, "ws.Drf", i - 1, Dr) + r0 * nrd.h[i - 1], nrd.act[i - 1]);
                 if (head) p.lda = 4;
                 b[Dr - i].push_back(p);
             }
             for (int i = 0; i <= Dr; ++i) {
                 const bool head = i == Dr;
-                const float* X = i == 0 ? Xin + r0 * ldQ : ch("ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
+                const float* X = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
                 const int K = i == 0 ? S + A : nrd.h[i - 1];
-                wr.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Dr3 + r0 * 4 : ch("ws.Drf", i, Dr) + r0 * nrd.h[i],
+                wr.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Dr3 + r0 * 4 : chain_buf(h, "ws.Drf", i, Dr) + r0 * nrd.h[i],
                                      head ? 1 : nrd.h[i], W(L_(n, i)), nullptr, GRP_MODEL));
                 if (head) wr.back().ldb = 4;
             }
@@ -2963,6 +2988,97 @@ bool merged_body(sacx_handle* h, int slot, int prev_slot, std::vector<Launch>& o
     return gi == pg.size() && head_done && final_done && ln_done && !afin_next;
 }
 
+// Every captured graph of the handle: what body(cap_stream) hands to the capture stream, instantiated
+// into *out.  The body returns non-zero to abort, having reported its error (fail).  The capture is
+// ended and the captured graph destroyed on every path, so a failure leaves the stream usable for the
+// next capture; every HIP failure is reported with its error text.  upload: the exec goes to the
+// stream's device now, so the first replay does not pay for it; nodes: the captured graph's node count.
+template <class F>
+int capture_graph(sacx_handle* h, const char* what, F&& body, hipGraphExec_t* out, bool upload = false,
+                  int64_t* nodes = nullptr) {
+    hipStream_t cs = h->cap_stream;
+    (void)hipGetLastError();              // (an earlier call's error is that call's: not this capture's)
+    HIPCHK(h, hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    const int rc = body(cs);
+    const hipError_t le = hipGetLastError();
+    hipGraph_t graph = nullptr;
+    const hipError_t ee = hipStreamEndCapture(cs, &graph);
+    const bool captured = rc == 0 && le == hipSuccess && ee == hipSuccess;
+    hipGraphExec_t ex = nullptr;
+    hipError_t ie = hipSuccess;
+    if (captured) {
+        size_t nn = 0;
+        if (nodes && hipGraphGetNodes(graph, nullptr, &nn) == hipSuccess) *nodes = (int64_t)nn;
+        ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc) return -1;
+    if (!captured) return fail(h, std::string(what) + " graph capture: " + hipGetErrorString(le != hipSuccess ? le : ee));
+    if (ie != hipSuccess) return fail(h, std::string(what) + " graph instantiate: " + hipGetErrorString(ie));
+    if (upload) {
+        const hipError_t ue = hipGraphUpload(ex, h->stream);
+        if (ue != hipSuccess) {
+            (void)hipGraphExecDestroy(ex);
+            return fail(h, std::string(what) + " graph upload: " + hipGetErrorString(ue));
+        }
+    }
+    *out = ex;
+    return 0;
+}
+
+// `n` back-to-back runs of a launch list as one graph (each run finds its inputs through a device-side
+// counter: the index rings of the PPO / critic steps)
+int capture_plan(sacx_handle* h, const char* what, const std::vector<Launch>& plan, int n, hipGraphExec_t* out) {
+    return capture_graph(h, what, [&](hipStream_t cs) {
+        for (int j = 0; j < n; ++j)
+            for (const Launch& L : plan) enqueue(L, h, cs);
+        return 0;
+    }, out);
+}
+
+// n_steps minibatch steps of `plan` (the PPO actor step, the critic step), each reading its mb indices
+// from the device's index ring [cap, ld] at its control block's step counter, which *seq_host mirrors:
+// it advances with every step handed to the stream, so a failure midway leaves the two in step.  The
+// ring is filled a chunk of at most cap steps at a time; a chunk replays as graphs of 64, 8 and 1
+// back-to-back steps, cached in `graphs` by (mb, steps), or runs as plain launches (SACX_STEP_EAGER).
+int run_ring_steps(sacx_handle* h, const std::vector<Launch>& plan, int32_t* ring, int ld, int64_t cap, int64_t* seq_host,
+                   std::map<std::pair<int, int>, hipGraphExec_t>& graphs, const char* what, const int32_t* idx,
+                   int64_t n_steps, int mb, int32_t flags) {
+    for (int64_t done = 0; done < n_steps;) {
+        const int64_t chunk = std::min<int64_t>(n_steps - done, cap);
+        HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
+        // the chunk's rows are contiguous modulo the ring: at most two copies
+        const int64_t s0 = *seq_host % cap;
+        const int64_t first = std::min<int64_t>(chunk, cap - s0);
+        HIPCHK(h, hipMemcpy2D(ring + s0 * ld, sizeof(int32_t) * ld, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
+                              (size_t)first, hipMemcpyHostToDevice));
+        if (chunk > first)
+            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * ld, idx + (done + first) * mb, sizeof(int32_t) * mb,
+                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
+        if (flags & SACX_STEP_EAGER) {
+            for (int64_t j = 0; j < chunk; ++j)
+                for (const Launch& L : plan) enqueue(L, h, h->stream);
+            *seq_host += chunk;
+            HIPCHK(h, hipGetLastError());
+        } else {
+            for (int64_t j = 0; j < chunk;) {
+                const int n = chunk - j >= 64 ? 64 : chunk - j >= 8 ? 8 : 1;
+                auto it = graphs.find({mb, n});
+                if (it == graphs.end()) {
+                    hipGraphExec_t ex = nullptr;
+                    if (capture_plan(h, what, plan, n, &ex)) return -1;
+                    it = graphs.emplace(std::make_pair(mb, n), ex).first;
+                }
+                HIPCHK(h, hipGraphLaunch(it->second, h->stream));
+                *seq_host += n;
+                j += n;
+            }
+        }
+        done += chunk;
+    }
+    return 0;
+}
+
 // Captured chain of G updates on two streams (see the fork branch below):
 //   cs: the updates, alpha branches folded one update later (merged_body) + a tail;
 //   rs: sampler + gather, two updates ahead (slot double buffer).
@@ -2993,16 +3109,8 @@ std::vector<std::pair<int, int>> sampler_batches(const sacx_handle* h, int G) {
     return batches;
 }
 
-int get_graph(sacx_handle* h, int G, bool with_rng, hipGraphExec_t* out, int skip_kind = -1,
-              KTimeMap* kt = nullptr) {
-    auto key = std::make_tuple(G, with_rng ? 1 : 0, skip_kind);
-    if (!kt) {
-        auto it = h->graphs.find(key);
-        if (it != h->graphs.end()) {
-            *out = it->second;
-            return 0;
-        }
-    }
+// what get_graph captures; the caller has created the 3 G + 1 events
+int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt) {
     auto emit = [&](const Launch& L, hipStream_t st) {
         const bool timed = kt && (L.kind == Launch::GEMM || (kt->rows && (L.kind == Launch::AHEAD || L.kind == Launch::ABWD)));
         if (timed) {
@@ -3038,17 +3146,10 @@ int get_graph(sacx_handle* h, int G, bool with_rng, hipGraphExec_t* out, int ski
         }
     };
     hipStream_t cs = h->cap_stream, rs = h->rng_stream;
-    const int nev = 3 * G + 1;
-    for (int i = (int)h->events.size(); i < nev; ++i) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->events.push_back(e);
-    }
     hipEvent_t* evR = h->events.data();          // inputs of update j ready
     hipEvent_t* evS = h->events.data() + G;      // update j's body done
     hipEvent_t* evF = h->events.data() + 2 * G;  // alpha.final of update j done
     hipEvent_t evFork = h->events[3 * G];
-    HIPCHK(h, hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
     if (with_rng) {
         // cs: the updates, each with the previous update's alpha branch folded into its first
         //     launches (merged_body), plus the last update's alpha branch as a tail;
@@ -3162,15 +3263,32 @@ int get_graph(sacx_handle* h, int G, bool with_rng, hipGraphExec_t* out, int ski
         if (skip_kind >= 0) return fail(h, "kernel ablation needs the forked sampler graph");
         for (int j = 0; j < G; ++j) enqueue_step(h, 0, with_rng, cs);
     }
-    hipGraph_t graph;
-    HIPCHK(h, hipStreamEndCapture(cs, &graph));
-    hipGraphExec_t exec;
-    HIPCHK(h, hipGraphInstantiateWithFlags(&exec, graph, 0));
-    HIPCHK(h, hipGraphDestroy(graph));
-    HIPCHK(h, hipGraphUpload(exec, h->stream));   // the first replay does not pay the upload
-    if (!kt) h->graphs[key] = exec;
-    *out = exec;
     return 0;
+}
+
+// the SAC update graphs live in h->graphs: a key's graph, captured (and uploaded) on its first use
+template <class F>
+int cached_graph(sacx_handle* h, const std::tuple<int, int, int>& key, const char* what, F&& body, hipGraphExec_t* out) {
+    auto it = h->graphs.find(key);
+    if (it == h->graphs.end()) {
+        hipGraphExec_t exec = nullptr;
+        if (capture_graph(h, what, body, &exec, true)) return -1;
+        it = h->graphs.emplace(key, exec).first;
+    }
+    *out = it->second;
+    return 0;
+}
+
+int get_graph(sacx_handle* h, int G, bool with_rng, hipGraphExec_t* out, int skip_kind = -1,
+              KTimeMap* kt = nullptr) {
+    for (int i = (int)h->events.size(); i < 3 * G + 1; ++i) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->events.push_back(e);
+    }
+    auto body = [&](hipStream_t) { return chain_body(h, G, with_rng, skip_kind, kt); };
+    if (kt) return capture_graph(h, "update", body, out, true);      // measurement only: uncached
+    return cached_graph(h, std::make_tuple(G, with_rng ? 1 : 0, skip_kind), "update", body, out);
 }
 
 // The one-update graphs of the drop-in loop's speculative path: gather + update of slot `slot`
@@ -3180,35 +3298,23 @@ int get_graph(sacx_handle* h, int G, bool with_rng, hipGraphExec_t* out, int ski
 // and the update's own alpha branch left out (deferred to the next one, or to settle()).
 int get_spec_graph(sacx_handle* h, int slot, int prev, hipGraphExec_t* out) {
     const auto key = std::make_tuple(-1, 64 * slot + (prev + 1), -1);   // < 0: never a get_graph key
-    auto it = h->graphs.find(key);
-    if (it != h->graphs.end()) {
-        *out = it->second;
+    return cached_graph(h, key, "speculative update", [&](hipStream_t cs) -> int {
+        if (h->nslot <= slot || h->plan[slot].empty()) return fail(h, "internal: no spare slot for the speculative draw");
+        std::vector<Launch> body;
+        if (!merged_body(h, slot, prev, body)) {   // plans that do not fold: the branch, then the body
+            std::vector<Launch> own;
+            if (!merged_body(h, slot, -1, own)) return fail(h, "internal: speculative update body");
+            body.clear();
+            for (const Launch& L : h->plan[prev])
+                if (L.alpha_branch) body.push_back(L);
+            body.insert(body.end(), own.begin(), own.end());
+        }
+        if (h->cfg.use_expert)                     // plain SAC: the speculative draw gathered too
+            for (const Launch& L : h->plan[slot])  // (the draw stamped pseq[slot] itself)
+                if (L.kind == Launch::GATHER) enqueue(L, h, cs);
+        for (const Launch& L : body) enqueue(L, h, cs);
         return 0;
-    }
-    if (h->nslot <= slot || h->plan[slot].empty()) return fail(h, "internal: no spare slot for the speculative draw");
-    std::vector<Launch> body;
-    if (!merged_body(h, slot, prev, body)) {   // plans that do not fold: the branch, then the body
-        std::vector<Launch> own;
-        if (!merged_body(h, slot, -1, own)) return fail(h, "internal: speculative update body");
-        body.clear();
-        for (const Launch& L : h->plan[prev])
-            if (L.alpha_branch) body.push_back(L);
-        body.insert(body.end(), own.begin(), own.end());
-    }
-    HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-    if (h->cfg.use_expert)                     // plain SAC: the speculative draw gathered too
-        for (const Launch& L : h->plan[slot])  // (the draw stamped pseq[slot] itself)
-            if (L.kind == Launch::GATHER) enqueue(L, h, h->cap_stream);
-    for (const Launch& L : body) enqueue(L, h, h->cap_stream);
-    hipGraph_t graph;
-    HIPCHK(h, hipStreamEndCapture(h->cap_stream, &graph));
-    hipGraphExec_t exec;
-    HIPCHK(h, hipGraphInstantiateWithFlags(&exec, graph, 0));
-    HIPCHK(h, hipGraphDestroy(graph));
-    HIPCHK(h, hipGraphUpload(exec, h->stream));
-    h->graphs[key] = exec;
-    *out = exec;
-    return 0;
+    }, out);
 }
 
 // Single-stream segments (round 4).  A graph that forks the sampler onto a second stream pays
@@ -3227,36 +3333,18 @@ int get_seg_graph(sacx_handle* h, int s0, int n, bool has_prev, bool is_last, hi
     const int nslot = h->nslot;
     // (first element -4: get_graph's keys start with G > 0, so a segment never replays a G-update graph)
     const auto key = std::make_tuple(-4, (s0 % nslot) * 1024 + n, (has_prev ? 2 : 0) + (is_last ? 1 : 0));
-    auto it = h->graphs.find(key);
-    if (it != h->graphs.end()) {
-        *out = it->second;
-        return 0;
-    }
-    hipStream_t cs = h->cap_stream;
-    HIPCHK(h, hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    std::vector<Launch> body;
-    for (int j = s0; j < s0 + n; ++j) {
-        const int slot = j % nslot, prev = (j > s0 || has_prev) ? (j - 1 + nslot) % nslot : -1;
-        if (!merged_body(h, slot, prev, body)) {
-            hipGraph_t g;
-            (void)hipStreamEndCapture(cs, &g);
-            if (g) (void)hipGraphDestroy(g);
-            return fail(h, "internal: segment body");
+    return cached_graph(h, key, "segment", [&](hipStream_t cs) -> int {
+        std::vector<Launch> body;
+        for (int j = s0; j < s0 + n; ++j) {
+            const int slot = j % nslot, prev = (j > s0 || has_prev) ? (j - 1 + nslot) % nslot : -1;
+            if (!merged_body(h, slot, prev, body)) return fail(h, "internal: segment body");
+            for (const Launch& L : body) enqueue(L, h, cs);
         }
-        for (const Launch& L : body) enqueue(L, h, cs);
-    }
-    if (is_last)
-        for (const Launch& L : h->plan[(s0 + n - 1) % nslot])
-            if (L.alpha_branch) enqueue(L, h, cs);
-    hipGraph_t graph;
-    HIPCHK(h, hipStreamEndCapture(cs, &graph));
-    hipGraphExec_t exec;
-    HIPCHK(h, hipGraphInstantiateWithFlags(&exec, graph, 0));
-    HIPCHK(h, hipGraphDestroy(graph));
-    HIPCHK(h, hipGraphUpload(exec, h->stream));
-    h->graphs[key] = exec;
-    *out = exec;
-    return 0;
+        if (is_last)
+            for (const Launch& L : h->plan[(s0 + n - 1) % nslot])
+                if (L.alpha_branch) enqueue(L, h, cs);
+        return 0;
+    }, out);
 }
 
 // whether step(n) takes the single-stream segments (SACX_SEGMENTS, default on)
@@ -4504,31 +4592,20 @@ int sacx_model_fit(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t 
     int32_t* ring = h->ptr<int32_t>("mfit.idx");
     // every step's launches read their minibatch rows from the index ring at ctl->mfit_seq, so a
     // graph of several steps replays them back to back (one graph launch per MFIT_GRAPH steps)
-    // (every HIP failure is reported with its error text; the capture is ended and the captured graph
-    // destroyed on every exit path, so a failed capture leaves the stream usable for the next fit)
     auto graph_of = [&](int n, hipGraphExec_t* out) -> int {
         auto it = h->mgraphs[k].find(n);
-        if (it != h->mgraphs[k].end()) {
-            *out = it->second;
-            return 0;
+        if (it == h->mgraphs[k].end()) {
+            hipGraphExec_t ex = nullptr;
+            if (capture_graph(h, "model-fit", [&](hipStream_t cs) {
+                    enqueue_fit_pre(h, n, cs);     // (n <= MFIT_PRE)
+                    for (int j = 0; j < n; ++j)
+                        for (const Launch& L : mplan) enqueue(fit_step_launch(h, L, j), h, cs);
+                    return 0;
+                }, &ex))
+                return -1;
+            it = h->mgraphs[k].emplace(n, ex).first;
         }
-        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        enqueue_fit_pre(h, n, h->cap_stream);     // (n <= MFIT_PRE)
-        for (int j = 0; j < n; ++j)
-            for (const Launch& L : mplan) enqueue(fit_step_launch(h, L, j), h, h->cap_stream);
-        const hipError_t le = hipGetLastError();
-        hipGraph_t graph = nullptr;
-        const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
-        if (le != hipSuccess || ee != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(h, std::string("model-fit graph capture: ") + hipGetErrorString(le != hipSuccess ? le : ee));
-        }
-        hipGraphExec_t ex = nullptr;
-        const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail(h, std::string("model-fit graph instantiate: ") + hipGetErrorString(ie));
-        h->mgraphs[k][n] = ex;
-        *out = ex;
+        *out = it->second;
         return 0;
     };
     for (int64_t done = 0; done < n_steps;) {
@@ -5164,16 +5241,13 @@ static int run_rollout(sacx_handle* h, int32_t model, const float* s_init, int64
     for (auto& kv : h->roll_graphs)
         if (std::memcmp(&kv.first, &key, sizeof(RollKey)) == 0) ge = kv.second;
     if (!ge) {
-        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        enqueue_rollout(h, model, s_init, n, horizon, deterministic, delta_clip, reward_clip, s_out, a_out, r_out,
-                        sp_out, d_out, h->cap_stream);
-        hipGraph_t g;
-        HIPCHK(h, hipStreamEndCapture(h->cap_stream, &g));
-        size_t nodes = 0;                           // every node is a kernel launch (sacx_rollout_launches)
-        if (hipGraphGetNodes(g, nullptr, &nodes) == hipSuccess) h->roll_nodes = (int64_t)nodes;
-        const hipError_t e = hipGraphInstantiateWithFlags(&ge, g, 0);
-        (void)hipGraphDestroy(g);
-        if (e != hipSuccess) return fail(h, std::string("rollout graph: ") + hipGetErrorString(e));
+        auto body = [&](hipStream_t cs) {
+            enqueue_rollout(h, model, s_init, n, horizon, deterministic, delta_clip, reward_clip, s_out, a_out, r_out,
+                            sp_out, d_out, cs);
+            return 0;
+        };
+        // (every node is a kernel launch: sacx_rollout_launches)
+        if (capture_graph(h, "rollout", body, &ge, false, &h->roll_nodes)) return -1;
         if (h->roll_graphs.size() >= 4) {          // a few shapes live at once; drop the oldest
             (void)hipGraphExecDestroy(h->roll_graphs.front().second);
             h->roll_graphs.erase(h->roll_graphs.begin());
@@ -5401,20 +5475,13 @@ static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
     if (it != h->ppo_plans.end()) return it->second;
     std::vector<Launch> plan;
     const int cur = h->probs_cursor;
-    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, Aout = h->Aout, ldS = h->ldS;
-    const NetDims& na = h->nd[0];
-    const int Da = na.D();
+    const int S = h->S, A = h->A, H1 = h->H1, Aout = h->Aout, ldS = h->ldS;
+    const int Da = h->nd[0].D();
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
-    auto ch = [&](const std::string& p, int i, int D) -> float* {     // as build_plan_generic's
-        if (i == 0) return W(p + "1");
-        if (i == D - 1) return W(p + "2");
-        return W(p + "m" + std::to_string(i));
-    };
     PpoCtl* pctl = h->ptr<PpoCtl>("ppo.ctl");
     PpoPar* par = h->ptr<PpoPar>("ppo.par");
-    float *X = W("ppo.X"), *O = W("ppo.O"), *D3 = W("ws.Da3"), *E = W("ws.E"), *acc = W("ppo.acc");
-    float* Ha_last = W("ws.Ha2");
+    float *X = W("ppo.X"), *O = W("ppo.O"), *acc = W("ppo.acc");
+    const ActorPass ap = actor_pass_ws(h, X, mb, 0, mb);     // the minibatch: rows [0, mb) of the update's workspace
     {
         Launch L{};
         L.kind = Launch::PPOGATHER;
@@ -5430,98 +5497,34 @@ static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
         L.bytes = 4.0 * mb * (S + ldS + 2.0 * A + 4);
         plan.push_back(L);
     }
-    for (int i = 0; i < Da; ++i) {
-        const float* in = i == 0 ? X : ch("ws.Ha", i - 1, Da);
-        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
-        add_gemm(h, plan, "actor.fwd" + std::to_string(i),
-                 {prob_fwd(in, ldi, mb, K, W(L_("actor", i)), na.h[i], ch("ws.Ha", i, Da),
-                           (i == 0 && h->ln) ? ACT_NONE : na.act[i])}, false);
-        if (i == 0 && h->ln) {
-            Launch L{};
-            L.kind = Launch::LNORM;
-            L.name = "actor.ln";
-            LNArgs& a = L.ln;
-            a.mode = 0; a.H = H0; a.Z = W("ws.Ha1"); a.nrange = 1; a.r[0] = 0; a.r[1] = mb;
-            a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = mb;
-            L.grid = (mb + 3) / 4;
-            L.flops = 8.0 * mb * H0;
-            L.bytes = 4.0 * mb * H0 * 3;
-            plan.push_back(L);
-        }
-    }
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", false);
     add_gemm(h, plan, "actor.fwd" + std::to_string(Da),
-             {prob_fwd(Ha_last, H1, mb, H1, W(L_("actor", Da)), Aout, O, ACT_NONE)}, false);
-    PpoDist dist{};
-    dist.O = O; dist.A = A; dist.Aout = Aout; dist.per_state_std = h->cfg.per_state_std;
-    dist.logstd = W("actor.logstd");
-    {   // logstd_init (continuous_actors.py:39-44), f32, as sacx_actor_act's
-        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-        dist.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
-    }
+             {prob_fwd(ap.H[Da - 1], H1, mb, H1, W(actor_head_name(h)), Aout, O, ACT_NONE)}, false);
     {
         Launch L{};
         L.kind = Launch::PPOHEAD;
         L.name = "ppo.head";
         PpoHeadArgs& a = L.ph;
-        a.d = dist; a.mb = mb;
+        a.d = ppo_dist(h, O); a.mb = mb;
         a.Arow = W("ppo.A"); a.advn = W("ppo.advn"); a.nlpo = W("ppo.nlpo");
         a.alpha = W("ppo.alpha"); a.par = par;
-        a.D3 = D3; a.E = E; a.row_loss = W("ppo.rl"); a.row_ent = W("ppo.rl") + h->B;
+        a.D3 = ap.D3; a.E = ap.E; a.row_loss = W("ppo.rl"); a.row_ent = W("ppo.rl") + h->B;
         L.grid = (mb + 3) / 4;
         L.flops = 40.0 * mb * A;
         L.bytes = 4.0 * mb * (2.0 * Aout + 2.0 * A + 4);
         plan.push_back(L);
     }
-    for (int i = Da; i >= 1; --i)
-        add_gemm(h, plan, "actor.bwd" + std::to_string(i),
-                 {prob_dx(i == Da ? D3 : ch("ws.Da", i, Da), mb, i == Da ? Aout : na.h[i], W(L_("actor", i)), na.h[i - 1],
-                          ch("ws.Ha", i - 1, Da), ch("ws.Da", i - 1, Da), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
-                 false);
-    if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
-        Launch N{};
-        N.kind = Launch::LNORM;
-        N.name = "actor.ln.bwd";
-        LNArgs& a = N.ln;
-        a.mode = 1; a.H = H0; a.Z = W("ws.Da1"); a.r[1] = mb; a.gamma = W("actor.ln");
-        a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = 0;
-        a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
-        N.grid = (mb + 3) / 4;
-        N.flops = 8.0 * mb * H0;
-        N.bytes = 4.0 * mb * H0 * 5;
-        plan.push_back(N);
-    }
+    actor_bwd_chain(h, plan, ap, Da, false);
     {
-        std::vector<GemmProb> pw;
-        for (int i = 0; i < Da; ++i) {
-            const float* Xi = i == 0 ? X : ch("ws.Ha", i - 1, Da);
-            const int K = i == 0 ? S : na.h[i - 1];
-            pw.push_back(prob_dw(Xi, i == 0 ? ldS : K, K, mb, ch("ws.Da", i, Da), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
-        }
-        pw.push_back(prob_dw(Ha_last, H1, H1, mb, D3, Aout, W(L_("actor", Da)), nullptr, GRP_PI));
-        if (!h->cfg.per_state_std) {
-            GemmProb p = prob_dw(E, 1, 0, mb, E, A, W("actor.logstd"), nullptr, GRP_PI);
-            p.ones_row = 0;   // single all-ones row: column sums of E
-            pw.push_back(p);
-        }
-        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
-            for (int k = 0; k < 2; ++k) {
-                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
-                GemmProb p = prob_dw(gsrc, 1, 0, mb, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
-                p.ones_row = 0;
-                pw.push_back(p);
-            }
-        }
-        const int n_dw = add_gemm_split(h, plan, "actor.grad", pw, false);
+        const int n_dw = add_gemm_split(h, plan, "actor.grad", actor_dw_probs(h, ap), false);
         for (int j = 0; j < n_dw; ++j) {       // store the gradients (+3 p_stride): the clip comes first
             Launch& G = plan[plan.size() - 1 - j];
             for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
         }
     }
-    // the actor's trainables are one contiguous parameter range: actor.l0 .. actor.logstd (with
-    // per_state_std the logstd variable is no trainable: its gradient stays 0 and Adam leaves it)
-    float* P = W("actor.l0");
-    const SegInfo& sl = h->seg("actor.logstd");
-    const int64_t n = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4);
+    const ParamRange ar = actor_range(h);
+    float* P = ar.P;
+    const int64_t n = ar.n;
     {
         Launch N{};
         N.kind = Launch::GNPART;
@@ -5576,12 +5579,7 @@ static PpoDist ppo_forward(sacx_handle* h, const float* s, int m) {
     add_gemm(h, pl, "actor.out", {prob_fwd(Hl, h->H1, m, h->H1, W(actor_head_name(h)), h->Aout, W("ppo.O"), ACT_NONE)}, false);
     h->probs_cursor -= 1;
     launch_gemm(pl[0].gemm, h->stream);
-    PpoDist d{};
-    d.O = W("ppo.O"); d.A = h->A; d.Aout = h->Aout; d.per_state_std = h->cfg.per_state_std;
-    d.logstd = W("actor.logstd");
-    const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-    d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
-    return d;
+    return ppo_dist(h, W("ppo.O"));
 }
 
 // the whole-rollout passes: n rows of s through the actor in chunks, k_ppo_rows on each; the
@@ -5641,9 +5639,8 @@ int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* 
     {   // the gradient words of the actor's parameter range: the norm and Adam read all of it, the dW
         // launches write the weights' words only (not the padding between segments, nor logstd's with
         // per_state_std), so the rest must hold 0 whatever the caller's arena held before
-        const SegInfo& sl = h->seg("actor.logstd");
-        const size_t nb = (size_t)(sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0"));
-        HIPCHK(h, hipMemsetAsync(W("actor.l0") + 3 * h->p_stride, 0, nb, h->stream));
+        const ParamRange ar = actor_range(h);
+        HIPCHK(h, hipMemsetAsync(ar.P + 3 * h->p_stride, 0, sizeof(float) * (size_t)ar.n, h->stream));
     }
     PpoRowsArgs r{};                  // neglogp_old, kl_info_ref, the entropy rows (ppo.py:44-46)
     r.a = W("ppo.a"); r.nlp_out = W("ppo.nlp_old"); r.mean_out = W("ppo.mean_ref"); r.ls_out = W("ppo.ls_ref");
@@ -5677,64 +5674,8 @@ int sacx_ppo_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t 
     par.ent_targ = params->ent_targ; par.alpha_lr = params->alpha_lr; par.actor_lr = params->actor_lr;
     par.ent_reg = params->ent_reg != 0; par.adv_center = params->adv_center != 0; par.adv_scale = params->adv_scale != 0;
     launch_ppo_set(h->ptr<PpoPar>("ppo.par"), par, h->ptr<PpoCtl>("ppo.ctl"), h->f("ppo.acc"), -1, h->stream);
-    int32_t* ring = h->ptr<int32_t>("ppo.idx");
-    const int B = h->B;
-    // each step reads its minibatch from the index ring at PpoCtl::seq, so a graph of several steps
-    // replays them back to back (the capture discipline of sacx_model_fit)
-    auto graph_of = [&](int n, hipGraphExec_t* out) -> int {
-        auto it = h->ppo_graphs.find({mb, n});
-        if (it != h->ppo_graphs.end()) {
-            *out = it->second;
-            return 0;
-        }
-        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        for (int j = 0; j < n; ++j)
-            for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
-        const hipError_t le = hipGetLastError();
-        hipGraph_t graph = nullptr;
-        const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
-        if (le != hipSuccess || ee != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(h, std::string("PPO step graph capture: ") + hipGetErrorString(le != hipSuccess ? le : ee));
-        }
-        hipGraphExec_t ex = nullptr;
-        const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail(h, std::string("PPO step graph instantiate: ") + hipGetErrorString(ie));
-        h->ppo_graphs[{mb, n}] = ex;
-        *out = ex;
-        return 0;
-    };
-    // ppo_seq_host mirrors PpoCtl::seq: it advances with every step handed to the stream, so a failure
-    // midway leaves the two in step
-    for (int64_t done = 0; done < n_steps;) {
-        const int64_t chunk = std::min<int64_t>(n_steps - done, PPO_IDX_CAP);
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
-        const int64_t s0 = h->ppo_seq_host % PPO_IDX_CAP;
-        const int64_t first = std::min<int64_t>(chunk, PPO_IDX_CAP - s0);
-        HIPCHK(h, hipMemcpy2D(ring + s0 * B, sizeof(int32_t) * B, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
-                              (size_t)first, hipMemcpyHostToDevice));
-        if (chunk > first)
-            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * B, idx + (done + first) * mb, sizeof(int32_t) * mb,
-                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
-        if (flags & SACX_STEP_EAGER) {
-            for (int64_t j = 0; j < chunk; ++j)
-                for (const Launch& L : plan) enqueue(L, h, h->stream);
-            h->ppo_seq_host += chunk;
-            HIPCHK(h, hipGetLastError());
-        } else {
-            for (int64_t j = 0; j < chunk;) {
-                const int n = chunk - j >= 64 ? 64 : chunk - j >= 8 ? 8 : 1;
-                hipGraphExec_t ex = nullptr;
-                if (graph_of(n, &ex)) return -1;
-                HIPCHK(h, hipGraphLaunch(ex, h->stream));
-                h->ppo_seq_host += n;
-                j += n;
-            }
-        }
-        done += chunk;
-    }
-    return 0;
+    return run_ring_steps(h, plan, h->ptr<int32_t>("ppo.idx"), h->B, PPO_IDX_CAP, &h->ppo_seq_host, h->ppo_graphs, "PPO step",
+                          idx, n_steps, mb, flags);
 }
 
 int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out) {
@@ -6098,62 +6039,8 @@ int sacx_vcritic_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int3
     VcPar par{};
     par.critic_lr = critic_lr;
     launch_vc_set(h->ptr<VcPar>("vc.par"), par, h->ptr<VcCtl>("vc.ctl"), -1, 0, h->stream);
-    int32_t* ring = h->ptr<int32_t>("vc.idx");
-    const int B = h->B;
-    // each step reads its minibatch from the index ring at VcCtl::seq, so a graph of several steps
-    // replays them back to back (the capture discipline of sacx_ppo_steps)
-    auto graph_of = [&](int n, hipGraphExec_t* out) -> int {
-        auto it = h->vc_graphs.find({mb, n});
-        if (it != h->vc_graphs.end()) {
-            *out = it->second;
-            return 0;
-        }
-        HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-        for (int j = 0; j < n; ++j)
-            for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
-        const hipError_t le = hipGetLastError();
-        hipGraph_t graph = nullptr;
-        const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
-        if (le != hipSuccess || ee != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return fail(h, std::string("critic step graph capture: ") + hipGetErrorString(le != hipSuccess ? le : ee));
-        }
-        hipGraphExec_t ex = nullptr;
-        const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail(h, std::string("critic step graph instantiate: ") + hipGetErrorString(ie));
-        h->vc_graphs[{mb, n}] = ex;
-        *out = ex;
-        return 0;
-    };
-    for (int64_t done = 0; done < n_steps;) {
-        const int64_t chunk = std::min<int64_t>(n_steps - done, VC_IDX_CAP);
-        HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
-        const int64_t s0 = h->vc_seq_host % VC_IDX_CAP;
-        const int64_t first = std::min<int64_t>(chunk, VC_IDX_CAP - s0);
-        HIPCHK(h, hipMemcpy2D(ring + s0 * B, sizeof(int32_t) * B, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
-                              (size_t)first, hipMemcpyHostToDevice));
-        if (chunk > first)
-            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * B, idx + (done + first) * mb, sizeof(int32_t) * mb,
-                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
-        if (flags & SACX_STEP_EAGER) {
-            for (int64_t j = 0; j < chunk; ++j)
-                for (const Launch& L : plan) enqueue(L, h, h->stream);
-            h->vc_seq_host += chunk;
-            HIPCHK(h, hipGetLastError());
-        } else {
-            for (int64_t j = 0; j < chunk;) {
-                const int n = chunk - j >= 64 ? 64 : chunk - j >= 8 ? 8 : 1;
-                hipGraphExec_t ex = nullptr;
-                if (graph_of(n, &ex)) return -1;
-                HIPCHK(h, hipGraphLaunch(ex, h->stream));
-                h->vc_seq_host += n;
-                j += n;
-            }
-        }
-        done += chunk;
-    }
-    return 0;
+    return run_ring_steps(h, plan, h->ptr<int32_t>("vc.idx"), h->B, VC_IDX_CAP, &h->vc_seq_host, h->vc_graphs, "critic step", idx,
+                          n_steps, mb, flags);
 }
 
 int sacx_vcritic_end(sacx_handle* h, double* out) {
@@ -6198,8 +6085,7 @@ int sacx_trpo_init(sacx_handle* h) {
     const NetDims& na = h->nd[0];
     const int64_t cap = h->cap;
     const int C = (int)std::min<int64_t>(cap, TRPO_CHUNK);
-    const SegInfo& sl = h->seg("actor.logstd");
-    const int64_t nv = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4);
+    const int64_t nv = actor_range(h).n;
     int wmax = std::max(Aout, h->ldS);
     for (int w : na.h) wmax = std::max(wmax, w);
     // behind everything the handle holds: every earlier segment keeps its offset
@@ -6255,22 +6141,31 @@ static int trpo_check(sacx_handle* h) {
 //   -> trpo.head -> actor.bwd<i> (+ actor.ln.bwd) -> actor.grad -> trpo.acc
 static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode, int64_t row0, int m, int64_t stride,
                             const float* dir, float* out, bool first, bool last) {
-    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, Aout = h->Aout, ldS = h->ldS, C = h->trpo_chunk;
+    const int S = h->S, A = h->A, H1 = h->H1, Aout = h->Aout, ldS = h->ldS, C = h->trpo_chunk;
     const NetDims& na = h->nd[0];
     const int Da = na.D();
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
-    auto Hb = [&](int i) { return W("trpo.H" + std::to_string(i)); };
+    auto L_ = layer_name;
     auto Tb = [&](int i) { return W("trpo.T" + std::to_string(i)); };
-    auto Db = [&](int i) { return W("trpo.D" + std::to_string(i)); };
     float* P0 = W("actor.l0");
     auto dir_of = [&](const std::string& seg) { return dir + (W(seg) - P0); };     // the direction's words of a segment
     const int t32 = h->tile32, dwl = h->dwl;
     h->tile32 = 0; h->dwl = 0;              // 16 x 16 tiles, k_gemm: the tiles the PPO step's tests pin
     const int cur = h->probs_cursor;
-    float *X = W("trpo.X"), *O = W("trpo.O"), *D3 = W("trpo.D3"), *E = W("trpo.E");
+    float *X = W("trpo.X"), *O = W("trpo.O");
     float *G0 = W("trpo.G"), *G1 = W("trpo.G") + (size_t)C * h->seg("trpo.G").cols;
     TrpoPar* par = h->ptr<TrpoPar>("trpo.par");
+    ActorPass ap{};                         // the chunk's rows: rows [0, m) of the trpo.* buffers
+    ap.X = X; ap.ldx = ldS; ap.M = m; ap.cache_rows = m;
+    for (int i = 0; i < Da; ++i) {
+        ap.H.push_back(W("trpo.H" + std::to_string(i)));
+        ap.D.push_back(W("trpo.D" + std::to_string(i)));
+    }
+    ap.D3 = W("trpo.D3"); ap.E = W("trpo.E");
+    if (h->ln) {
+        ap.xhat = W("trpo.xhat"); ap.rstd = W("trpo.rstd"); ap.gy = W("trpo.gy"); ap.gb = W("trpo.gb");
+    }
+    auto Hb = [&](int i) { return ap.H[i]; };
     {
         Launch L{};
         L.kind = Launch::TRIN;
@@ -6282,24 +6177,7 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         L.bytes = 4.0 * m * (S + ldS);
         plan.push_back(L);
     }
-    for (int i = 0; i < Da; ++i) {
-        const float* in = i == 0 ? X : Hb(i - 1);
-        const int ldi = i == 0 ? ldS : na.h[i - 1], K = i == 0 ? S : na.h[i - 1];
-        add_gemm(h, plan, "actor.fwd" + std::to_string(i),
-                 {prob_fwd(in, ldi, m, K, W(L_("actor", i)), na.h[i], Hb(i), (i == 0 && h->ln) ? ACT_NONE : na.act[i])}, false);
-        if (i == 0 && h->ln) {
-            Launch L{};
-            L.kind = Launch::LNORM;
-            L.name = "actor.ln";
-            LNArgs& a = L.ln;
-            a.mode = 0; a.H = H0; a.Z = Hb(0); a.nrange = 1; a.r[0] = 0; a.r[1] = m;
-            a.gamma = W("actor.ln"); a.xhat = W("trpo.xhat"); a.rstd = W("trpo.rstd"); a.cache_rows = m;
-            L.grid = (m + 3) / 4;
-            L.flops = 8.0 * m * H0;
-            L.bytes = 4.0 * m * H0 * 3;
-            plan.push_back(L);
-        }
-    }
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", false);
     add_gemm(h, plan, "actor.fwd" + std::to_string(Da), {prob_fwd(Hb(Da - 1), H1, m, H1, W(L_("actor", Da)), Aout, O, ACT_NONE)},
              false);
     if (mode == 1) {
@@ -6338,17 +6216,14 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         L.kind = Launch::TRHEAD;
         L.name = "trpo.head";
         TrHeadArgs& a = L.th;
-        a.d.O = O; a.d.A = A; a.d.Aout = Aout; a.d.per_state_std = h->cfg.per_state_std;
-        a.d.logstd = W("actor.logstd");
-        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-        a.d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+        a.d = ppo_dist(h, O);
         a.mode = mode; a.m = m; a.row0 = row0;
         a.a = W("ppo.a"); a.nlp_old = W("ppo.nlp_old"); a.mean_ref = W("ppo.mean_ref"); a.ls_ref = W("ppo.ls_ref");
         // the gradient takes the advantages normalised once, the line search twice (trpo.py:244-250)
         a.adv = W("trpo.adv") + (mode == 2 ? (size_t)h->cap : 0);
         a.alpha = W("ppo.alpha"); a.par = par;
         a.TO0 = G0; a.TO1 = G1; a.vls = dir ? dir_of("actor.logstd") : nullptr;
-        a.D3 = D3; a.E = E;
+        a.D3 = ap.D3; a.E = ap.E;
         a.o_radv = W("trpo.ev"); a.o_rdiff = W("trpo.ev") + h->cap; a.o_kl = W("trpo.ev") + 2 * (size_t)h->cap;
         L.grid = (m + 3) / 4;
         L.flops = 40.0 * m * A;
@@ -6356,48 +6231,9 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         plan.push_back(L);
     }
     if (mode != 2) {
-        for (int i = Da; i >= 1; --i)
-            add_gemm(h, plan, "actor.bwd" + std::to_string(i),
-                     {prob_dx(i == Da ? D3 : Db(i), m, i == Da ? Aout : na.h[i], W(L_("actor", i)), na.h[i - 1], Hb(i - 1),
-                              Db(i - 1), (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
-                     false);
-        if (h->ln) {
-            Launch N{};
-            N.kind = Launch::LNORM;
-            N.name = "actor.ln.bwd";
-            LNArgs& a = N.ln;
-            a.mode = 1; a.H = H0; a.Z = Db(0); a.r[1] = m; a.gamma = W("actor.ln");
-            a.xhat = W("trpo.xhat"); a.rstd = W("trpo.rstd"); a.xrow0 = 0;
-            a.gy = W("trpo.gy"); a.gb = W("trpo.gb");
-            N.grid = (m + 3) / 4;
-            N.flops = 8.0 * m * H0;
-            N.bytes = 4.0 * m * H0 * 5;
-            plan.push_back(N);
-        }
-        std::vector<GemmProb> pw;
-        auto dw = [&](GemmProb p) {
-            p.bscale = W("trpo.ones");
-            pw.push_back(p);
-        };
-        for (int i = 0; i < Da; ++i) {
-            const float* Xi = i == 0 ? X : Hb(i - 1);
-            const int K = i == 0 ? S : na.h[i - 1];
-            dw(prob_dw(Xi, i == 0 ? ldS : K, K, m, Db(i), na.h[i], W(L_("actor", i)), nullptr, GRP_PI));
-        }
-        dw(prob_dw(Hb(Da - 1), H1, H1, m, D3, Aout, W(L_("actor", Da)), nullptr, GRP_PI));
-        if (!h->cfg.per_state_std) {
-            GemmProb p = prob_dw(E, 1, 0, m, E, A, W("actor.logstd"), nullptr, GRP_PI);
-            p.ones_row = 0;   // single all-ones row: column sums of E
-            dw(p);
-        }
-        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
-            for (int k = 0; k < 2; ++k) {
-                float* gsrc = W(k ? "trpo.gb" : "trpo.gy");
-                GemmProb p = prob_dw(gsrc, 1, 0, m, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
-                p.ones_row = 0;
-                dw(p);
-            }
-        }
+        actor_bwd_chain(h, plan, ap, Da, false);
+        std::vector<GemmProb> pw = actor_dw_probs(h, ap);
+        for (GemmProb& p : pw) p.bscale = W("trpo.ones");       // the chunk's row scale
         const int n_dw = add_gemm_split(h, plan, "actor.grad", pw, false);
         for (int j = 0; j < n_dw; ++j) {       // stored at +3 p_stride, as the PPO step's
             Launch& G = plan[plan.size() - 1 - j];
@@ -6501,24 +6337,6 @@ int sacx_trpo_begin(sacx_handle* h, const float* s, const float* a, const float*
     return 0;
 }
 
-static int trpo_capture(sacx_handle* h, const std::vector<Launch>& plan, hipGraphExec_t* out, const char* what) {
-    HIPCHK(h, hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-    for (const Launch& L : plan) enqueue(L, h, h->cap_stream);
-    const hipError_t le = hipGetLastError();
-    hipGraph_t graph = nullptr;
-    const hipError_t ee = hipStreamEndCapture(h->cap_stream, &graph);
-    if (le != hipSuccess || ee != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        return fail(h, std::string(what) + " graph capture: " + hipGetErrorString(le != hipSuccess ? le : ee));
-    }
-    hipGraphExec_t ex = nullptr;
-    const hipError_t ie = hipGraphInstantiateWithFlags(&ex, graph, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) return fail(h, std::string(what) + " graph instantiate: " + hipGetErrorString(ie));
-    *out = ex;
-    return 0;
-}
-
 int sacx_trpo_grad(sacx_handle* h, float* out_dev) {
     if (trpo_check(h)) return -1;
     if (!out_dev) return fail(h, "null output");
@@ -6545,7 +6363,7 @@ int sacx_trpo_fvp(sacx_handle* h, const float* x_dev, float* out_dev, int32_t fl
             h->trpo_fgraph = nullptr;
             std::vector<Launch> plan;
             trpo_pass_plan(h, plan, 1, h->trpo_rows, h->trpo_sub, trpo_vec(h, TRV_P), trpo_vec(h, TRV_Z));
-            if (trpo_capture(h, plan, &h->trpo_fgraph, "TRPO Fisher product")) return -1;
+            if (capture_plan(h, "TRPO Fisher product", plan, 1, &h->trpo_fgraph)) return -1;
             h->trpo_fkey = key;
         }
         HIPCHK(h, hipGraphLaunch(h->trpo_fgraph, h->stream));
@@ -6599,7 +6417,7 @@ int sacx_trpo_step(sacx_handle* h, const sacx_trpo_params* params, int32_t flags
                 h->trpo_graph = nullptr;
                 std::vector<Launch> plan;
                 trpo_solve_plan(h, plan, params->cg_it);
-                if (trpo_capture(h, plan, &h->trpo_graph, "TRPO solve")) return -1;
+                if (capture_plan(h, "TRPO solve", plan, 1, &h->trpo_graph)) return -1;
                 h->trpo_gkey = key;
             }
             HIPCHK(h, hipGraphLaunch(h->trpo_graph, h->stream));
