@@ -81,7 +81,9 @@ enum sacx_role { SACX_ROLE_WORK = 0, SACX_ROLE_PARAM = 1, SACX_ROLE_TARGET = 2, 
    minibatch advantage std + 1e-8, the step number).  It acts as a SACX_ACTOR_GAUSSIAN handle does.
    Refused at sacx_create: actor_output_norm (no backward is built for it), gemm_bf16, seeds > 1,
    use_expert SACX_EXPERT_EO / _BC (SACX_EXPERT_MODELS adds the world models); sacx_dp_init / sacx_dp_init_local fail on it.  sacx_sac_step and
-   sacx_actor_evaluate fail on it as on a SACX_ACTOR_GAUSSIAN handle. */
+   sacx_actor_evaluate fail on it as on a SACX_ACTOR_GAUSSIAN handle.
+   sacx_softmax_init (below) turns such a handle into SoftMaxActor's (discrete_actors.py:8-117): the same
+   layout, the net's outputs read as logits, the action rows one index each; sacx_config is unchanged. */
 #define SACX_ACTOR_SQUASHED 0
 #define SACX_ACTOR_GAUSSIAN 1
 #define SACX_ACTOR_GAUSSIAN_TRAIN 2
@@ -541,6 +543,35 @@ int sacx_trpo_fvp(sacx_handle* h, const float* x_dev, float* out_dev, int32_t fl
 int sacx_trpo_step(sacx_handle* h, const sacx_trpo_params* params, int32_t flags, double* out);
 /* The launches of one Fisher product over `rows` rows, as sacx_plan_info. */
 int sacx_trpo_plan_info(sacx_handle* h, int64_t rows, struct sacx_launch_info* out, int32_t cap, int32_t* n_out);
+
+/* --- SoftMaxActor on the trainable handle: discrete actions for PPO and TRPO --------------------
+ * SoftMaxActor (sac_eo/actors/discrete_actors.py:8-117) with the one reading that makes the class
+ * construct: _nn = create_nn(s_dim, a_dim, layers, activations, gain), a_dim = n of Discrete(n), the
+ * trainables the net's variables only.  After sacx_create and before sacx_arena_bytes / sacx_layout /
+ * sacx_bind, in any order with sacx_vcritic_init and sacx_trpo_init.  The layout does not change
+ * ("actor.logstd" keeps its words and is no trainable: no gradient, no Adam, in neither norm); a
+ * handle without the call keeps its layout and results byte for byte.  Fails on a handle that is
+ * not SACX_ACTOR_GAUSSIAN_TRAIN, with per_state_std, with SACX_EXPERT_MODELS (the world models take
+ * continuous actions and the reference defines no encoding) or any other use_expert, on a bound
+ * handle and on a second call.
+ * After the call the actor net's a_dim outputs are logits and the entry points above carry the
+ * categorical meaning, every value on the row's max-shifted logits (:33, :49, :58, :82):
+ *   sacx_ppo_neglogp, sacx_ppo_begin, sacx_trpo_begin: a is a[n], one action index per row stored
+ *     as float; neglogp = softmax_cross_entropy_with_logits(one_hot(a), logits) (:47-54) = -log p_a.
+ *     An index outside [0, a_dim) is tf.one_hot's all-zero row: neglogp 0, no gradient through r.
+ *   sacx_ppo_dist: mean_out[n,A] = the raw logits (get_kl_info, :98-100), logstd_out must be NULL,
+ *     ent_out[n] = -sum_j p_j log p_j (:56-66).
+ *   sacx_ppo_kl: mean_ref[n,A] = the reference logits, logstd_ref must be NULL; kl_out[n] =
+ *     sum_j p_j ((l_j - lse) - (l_ref_j - lse_ref)) (:68-96).
+ *   sacx_ppo_steps, sacx_ppo_end: ppo.py:122-239, :91-106 with that neglogp and entropy; the same
+ *     statistics, alpha step and global-norm clip; Adam over the net's variables.
+ *   sacx_trpo_grad, sacx_trpo_fvp, sacx_trpo_step: flat vectors span actor.l0 up to where
+ *     actor.logstd begins; the Fisher product is (1 / n_sub) sum_i J_i^T (diag(p_i) - p_i p_i^T) J_i,
+ *     the Hessian of the mean kl at cur = ref; the line search uses the categorical kl; set_weights
+ *     (:109-117) floors nothing.
+ *   sacx_actor_act, its _host forms, sacx_rollout and sacx_sim_collect fail: a softmax handle samples
+ *     on the host from sacx_ppo_dist's logits (:22-42; off the hot path). */
+int sacx_softmax_init(sacx_handle* h);
 
 int sacx_sync(sacx_handle* h);
 /* Brings the arena to the state the calls so far define, without waiting: runs an alpha branch

@@ -6167,6 +6167,56 @@ __device__ __forceinline__ float ppo_ent(const PpoCol& c, bool jok) {
     return 0.5f * wave_sum(jok ? (2.f * c.ls + LOG2PI_F) + 1.f : 0.f);
 }
 
+// SoftMaxActor's row (discrete_actors.py:47-96), lane j < A holding logit j: everything on the
+// max-shifted logits x = l - max, log p = x - log(sum exp x) (no exp of an unshifted logit, no log of
+// a probability), ent = -sum p log p (wave-uniform).  A lane whose exp underflows has p = 0 and a
+// finite log p.
+__device__ __forceinline__ float wave_max(float v) {
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+struct SmRow {
+    float p, logp, ent;
+};
+__device__ __forceinline__ float sm_logp(float l, bool jok, float& e, float& z) {
+    const float m = wave_max(jok ? l : -INFINITY);
+    const float x = jok ? l - m : 0.f;
+    e = jok ? expf(x) : 0.f;
+    z = wave_sum(e);
+    return x - logf(z);
+}
+__device__ __forceinline__ SmRow sm_row(float l, bool jok) {
+    SmRow r;
+    float e, z;
+    r.logp = sm_logp(l, jok, e, z);
+    r.p = e / z;
+    r.ent = 0.f - wave_sum(jok ? r.p * r.logp : 0.f);
+    return r;
+}
+// softmax_cross_entropy_with_logits(one_hot(a), logits) (:47-54): -log p_a; an index outside [0, A) is
+// tf.one_hot's all-zero row (index -1 here): 0
+__device__ __forceinline__ int sm_index(float af, int A) {
+    return (af >= 0.f && af < (float)A) ? (int)af : -1;
+}
+__device__ __forceinline__ float sm_nlp(const SmRow& r, int ai, int lane) {
+    return 0.f - wave_sum(lane == ai ? r.logp : 0.f);
+}
+// sum_j p_cur ((l_cur - lse_cur) - (l_ref - lse_ref)) (:68-96) from the f32 logits, the arithmetic in f64:
+// the two log-sum-exps are of order 1 and cancel down to the kl, 1e-4 .. 1e-2 after an update, and in f32
+// their rounding (the same on every lane, so the p-weighted sum keeps it whole) is 1e-7 absolute, which
+// measured 2.8e-5 of a mean kl of 4e-4.  These are the whole-rollout rows, not the minibatch step.
+__device__ __forceinline__ double wave_sum_d(double v) {
+    for (int o = 32; o >= 1; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float sm_kl(float l, float lref, bool jok) {
+    const float m = wave_max(jok ? l : -INFINITY), mr = wave_max(jok ? lref : -INFINITY);
+    const double x = jok ? (double)l - (double)m : 0.0, xr = jok ? (double)lref - (double)mr : 0.0;
+    const double e = jok ? exp(x) : 0.0, er = jok ? exp(xr) : 0.0;
+    const double z = wave_sum_d(e), zr = wave_sum_d(er);
+    return (float)wave_sum_d(jok ? (e / z) * ((x - log(z)) - (xr - log(zr))) : 0.0);
+}
+
 __global__ __launch_bounds__(256) void k_ppo_gather(PpoGatherArgs g) {
     __shared__ float red[4];
     const int mb = g.mb, S = g.S, A = g.A, ldS = g.ldS;
@@ -6218,6 +6268,29 @@ __global__ __launch_bounds__(256) void k_ppo_head(PpoHeadArgs g) {
     if (row >= g.mb) return;
     const int A = g.d.A;
     const bool jok = lane < A;
+    if (g.d.softmax) {
+        // the same surrogate with the categorical neglogp and entropy: d nlp / d l_j = p_j - onehot_j
+        // (0 on a row without a label), d ent / d l_j = -p_j (log p_j + ent)
+        const SmRow sr = sm_row(jok ? g.d.O[(size_t)row * g.d.Aout + lane] : 0.f, jok);
+        const int ai = sm_index(g.Arow[row], A);
+        const float nlp = sm_nlp(sr, ai, lane);
+        const float adv = g.advn[row], old = g.nlpo[row];
+        const float lo = g.par->clip_lo, hi = g.par->clip_hi;
+        const float r = expf(old - nlp);
+        const float rc = fminf(fmaxf(r, lo), hi);
+        const float surr = (r * adv) * -1.f, clp = (rc * adv) * -1.f;
+        const bool take = surr >= clp;
+        const float inv_mb = 1.f / (float)g.mb;
+        const float gn = (take && ai >= 0) ? (adv * r) * inv_mb : 0.f;
+        const float alpha = g.alpha[0];
+        const float dent = -(sr.p * (sr.logp + sr.ent));
+        if (jok) g.D3[(size_t)row * g.d.Aout + lane] = gn * (sr.p - (lane == ai ? 1.f : 0.f)) - (alpha * inv_mb) * dent;
+        if (lane == 0) {
+            g.row_loss[row] = fmaxf(surr, clp);
+            g.row_ent[row] = sr.ent;
+        }
+        return;
+    }
     const PpoCol c = ppo_col(g.d, row, lane, jok);
     const float a = jok ? g.Arow[(size_t)row * A + lane] : 0.f;
     float z, sd;
@@ -6303,6 +6376,22 @@ __global__ __launch_bounds__(256) void k_ppo_rows(PpoRowsArgs g) {
     if (row >= g.m) return;
     const int A = g.d.A;
     const bool jok = lane < A;
+    if (g.d.softmax) {              // SoftMaxActor: get_kl_info's raw logits, entropy, neglogp, kl (discrete_actors.py:47-100)
+        const float l = jok ? g.d.O[(size_t)row * g.d.Aout + lane] : 0.f;
+        if (jok && g.mean_out != nullptr) g.mean_out[(size_t)row * A + lane] = l;
+        const SmRow sr = sm_row(l, jok);
+        if (lane == 0 && g.ent_out != nullptr) g.ent_out[row] = sr.ent;
+        if (g.a != nullptr) {
+            const float nlp = sm_nlp(sr, sm_index(g.a[row], A), lane);
+            if (lane == 0 && g.nlp_out != nullptr) g.nlp_out[row] = nlp;
+            if (lane == 0 && g.rdiff_out != nullptr) g.rdiff_out[row] = fabsf(expf(g.nlp_old[row] - nlp) - 1.f);
+        }
+        if (g.mean_ref != nullptr) {
+            const float kl = sm_kl(l, jok ? g.mean_ref[(size_t)row * A + lane] : 0.f, jok);
+            if (lane == 0) g.kl_out[row] = kl;
+        }
+        return;
+    }
     const PpoCol c = ppo_col(g.d, row, lane, jok);
     if (jok && g.mean_out != nullptr) g.mean_out[(size_t)row * A + lane] = c.mean;
     if (jok && g.ls_out != nullptr) g.ls_out[(size_t)row * A + lane] = c.ls;

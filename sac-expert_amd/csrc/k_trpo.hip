@@ -78,6 +78,28 @@ __device__ __forceinline__ TrCol tr_col(const PpoDist& d, int row, int lane, boo
     return c;
 }
 
+// SoftMaxActor's row (discrete_actors.py:47-96), as the PPO rows compute it: lane j < A holds logit j,
+// everything on the max-shifted logits, log p = (l - max) - log(sum exp(l - max))
+struct TrSm {
+    float p, logp;
+};
+__device__ __forceinline__ TrSm tr_sm(float l, bool jok) {
+    const float m = tr_wave_max(jok ? l : -INFINITY);
+    const float x = jok ? l - m : 0.f;
+    const float e = jok ? expf(x) : 0.f;
+    const float z = tr_wave_sum(e);
+    return TrSm{e / z, x - logf(z)};
+}
+// the categorical kl (:68-96) from the f32 logits with the arithmetic in f64, as the PPO rows compute it
+// (the two log-sum-exps cancel down to a kl of 1e-4 .. 1e-2: f32 leaves 1e-7 absolute on each)
+__device__ __forceinline__ float tr_sm_kl(float l, float lref, bool jok) {
+    const float m = tr_wave_max(jok ? l : -INFINITY), mr = tr_wave_max(jok ? lref : -INFINITY);
+    const double x = jok ? (double)l - (double)m : 0.0, xr = jok ? (double)lref - (double)mr : 0.0;
+    const double e = jok ? exp(x) : 0.0, er = jok ? exp(xr) : 0.0;
+    const double z = tr_wave_sum_d(e), zr = tr_wave_sum_d(er);
+    return (float)tr_wave_sum_d(jok ? (e / z) * ((x - log(z)) - (xr - log(zr))) : 0.0);
+}
+
 // the sum of TRPO_PARTS f64 partials in index order (every caller the same bits)
 __device__ __forceinline__ double tr_parts_sum(const double* p) {
     double t = 0.0;
@@ -160,6 +182,38 @@ __global__ __launch_bounds__(256) void k_trpo_head(TrHeadArgs g) {
     if (row >= g.m) return;
     const int A = g.d.A, Aout = g.d.Aout;
     const bool jok = lane < A;
+    if (g.d.softmax) {
+        const int64_t trow = g.row0 + row;
+        const float l = jok ? g.d.O[(size_t)row * Aout + lane] : 0.f;
+        const TrSm sm = tr_sm(l, jok);
+        if (g.mode == 1) {
+            // u = M t / n_sub with M = diag(p) - p p^T: the Hessian of the mean kl at cur = ref
+            const float t = jok ? g.TO0[(size_t)row * Aout + lane] + g.TO1[(size_t)row * Aout + lane] : 0.f;
+            const float pt = tr_wave_sum(jok ? sm.p * t : 0.f);
+            if (jok) g.D3[(size_t)row * Aout + lane] = (sm.p * (t - pt)) * g.par->inv_nsub;
+            return;
+        }
+        const float af = g.a[trow];
+        const int ai = (af >= 0.f && af < (float)A) ? (int)af : -1;     // outside [0, A): tf.one_hot's zero row
+        const float nlp = 0.f - tr_wave_sum(lane == ai ? sm.logp : 0.f);
+        const float r = expf(g.nlp_old[trow] - nlp);
+        const float adv = g.adv[trow];
+        if (g.mode == 0) {
+            const float inv_n = g.par->inv_n;
+            const float gn = ai >= 0 ? (adv * r) * inv_n : 0.f;
+            const float ent = 0.f - tr_wave_sum(jok ? sm.p * sm.logp : 0.f);
+            const float dent = -(sm.p * (sm.logp + ent));
+            if (jok) g.D3[(size_t)row * Aout + lane] = gn * (sm.p - (lane == ai ? 1.f : 0.f)) - (g.alpha[0] * inv_n) * dent;
+            return;
+        }
+        const float kl = tr_sm_kl(l, jok ? g.mean_ref[(size_t)trow * A + lane] : 0.f, jok);
+        if (lane == 0) {
+            g.o_radv[trow] = r * adv;
+            g.o_rdiff[trow] = fabsf(r - 1.f);
+            g.o_kl[trow] = kl;
+        }
+        return;
+    }
     const TrCol c = tr_col(g.d, row, lane, jok);
     const int64_t tr = g.row0 + row;
     if (g.mode == 1) {

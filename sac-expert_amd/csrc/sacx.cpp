@@ -203,6 +203,9 @@ struct sacx_handle {
     std::tuple<int64_t, int32_t, int32_t> trpo_gkey{0, 0, 0};   // ... of (rows, trust_sub, cg_it)
     hipGraphExec_t trpo_fgraph = nullptr;              // one Fisher product p -> z ...
     std::pair<int64_t, int32_t> trpo_fkey{0, 0};       // ... of (rows, trust_sub)
+    // sacx_softmax_init: the actor net's outputs are SoftMaxActor's logits (discrete_actors.py:8-117); the
+    // trainables end before actor.logstd, which stays in the layout untouched
+    bool softmax = false;
     // layout
     std::vector<SegInfo> segs;
     std::map<std::string, size_t> seg_index;
@@ -1960,7 +1963,7 @@ std::vector<GemmProb> actor_dw_probs(sacx_handle* h, const ActorPass& c) {
     }
     pw.push_back(prob_dw(c.H[Da - 1] + (size_t)c.hrow0 * H1, H1, H1, c.M, c.D3, h->Aout, h->f(layer_name("actor", Da)), nullptr,
                          GRP_PI));
-    if (!h->cfg.per_state_std) {
+    if (!h->cfg.per_state_std && !h->softmax) {
         GemmProb p = prob_dw(c.E, 1, 0, c.M, c.E, h->A, h->f("actor.logstd"), nullptr, GRP_PI);
         p.ones_row = 0;   // single all-ones row: column sums of E
         pw.push_back(p);
@@ -1978,12 +1981,12 @@ std::vector<GemmProb> actor_dw_probs(sacx_handle* h, const ActorPass& c) {
 
 // The actor's trainables are one contiguous parameter range, actor.l0 .. actor.logstd (with per_state_std
 // the logstd variable is no trainable: its gradient stays 0 and Adam leaves it): its base (null before
-// sacx_bind) and float count
+// sacx_bind) and float count.  A softmax handle's range ends where actor.logstd begins (the net only).
 struct ParamRange { float* P; int64_t n; };
 ParamRange actor_range(const sacx_handle* h) {
     const SegInfo& sl = h->seg("actor.logstd");
-    return {h->arena ? h->f("actor.l0") : nullptr,
-            (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("actor.l0")) / 4)};
+    const uint64_t end = h->softmax ? sl.off : sl.off + (uint64_t)(sl.rows * sl.cols) * 4;
+    return {h->arena ? h->f("actor.l0") : nullptr, (int64_t)((end - h->off_of("actor.l0")) / 4)};
 }
 
 // the trainable GaussianActor's distribution over the output rows O [m, Aout]
@@ -1994,6 +1997,7 @@ PpoDist ppo_dist(sacx_handle* h, const float* O) {
     // logstd_init (continuous_actors.py:39-44), f32, as sacx_actor_act's
     const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
     d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    d.softmax = h->softmax ? 1 : 0;
     return d;
 }
 
@@ -4257,6 +4261,7 @@ static bool act_rows_ok(const sacx_handle* h, int64_t n) {
 
 int sacx_actor_act_host(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, float* act_out) {
     if (!h || !h->bound) return fail(h, "not bound");
+    if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (n < 0 || (n > 0 && (!obs || !act_out))) return fail(h, "bad arguments");
     const int S = h->S, A = h->A;
     const int64_t chunk = std::min<int64_t>(ACT_CAP, STAGE_CAP / (S + A));
@@ -4358,6 +4363,7 @@ int sacx_buffer_append_host_seeds(sacx_handle* h, const float* s, const float* a
 
 int sacx_actor_act_host_seeds(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, float* act_out) {
     if (!h || !h->bound) return fail(h, "not bound");
+    if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (flush_append(h)) return -1;
     if (n <= 0 || !obs || !act_out) return fail(h, "bad arguments");
     const int S = h->S, A = h->A, K = h->seeds;
@@ -4813,6 +4819,7 @@ int sacx_actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t determin
 static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, float* act_out,
                      uint32_t* done) {
     if (!h || !h->bound) return fail(h, "not bound");
+    if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (!deterministic && spec_cancel(h)) return -1;   // a draw from the stream: undo the speculative one
     if (n < 0 || (n > 0 && (!obs || !act_out))) return fail(h, "bad arguments");
     const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS;
@@ -5167,6 +5174,7 @@ int sacx_rollout(sacx_handle* h, int32_t model, const float* s_init, int64_t n, 
                  int32_t deterministic, float delta_clip, float reward_clip, float* s_out, float* a_out,
                  float* r_out, float* sp_out, uint8_t* d_out) {
     if (!h || !h->bound) return fail(h, "not bound");
+    if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (!h->cfg.use_expert) return fail(h, "rollout needs the world models (use_expert)");
     if (model < 0 || model >= h->nm) return fail(h, "model index out of range (num_models)");
     if (n < 0 || horizon < 0) return fail(h, "bad arguments");
@@ -5183,6 +5191,7 @@ int sacx_sim_collect(sacx_handle* h, int32_t model, int64_t n, int32_t horizon, 
                      float delta_clip, float reward_clip, float* s_out, float* a_out, float* r_out, float* sp_out,
                      uint8_t* d_out) {
     if (!h || !h->bound) return fail(h, "not bound");
+    if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (!h->cfg.use_expert) return fail(h, "sim_collect needs the world models (use_expert)");
     if (!h->models_only)
         return fail(h, "sim_collect: a use_expert = SACX_EXPERT_MODELS handle only (the ring holds the env data there)");
@@ -5491,7 +5500,7 @@ static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
         g.idx_ring = h->ptr<int32_t>("ppo.idx"); g.idx_ld = h->B;
         g.ctl = pctl; g.par = par;
         g.s_mean = W("norm.s_mean"); g.s_den = W("norm.s_den");
-        g.S = S; g.A = A; g.mb = mb; g.ldS = ldS;
+        g.S = S; g.A = h->softmax ? 1 : A; g.mb = mb; g.ldS = ldS;      // (softmax: the one action-index column)
         g.X = X; g.Arow = W("ppo.A"); g.advn = W("ppo.advn"); g.nlpo = W("ppo.nlpo"); g.acc = acc;
         L.grid = (mb + PPO_GATHER_ROWS - 1) / PPO_GATHER_ROWS;
         L.bytes = 4.0 * mb * (S + ldS + 2.0 * A + 4);
@@ -5592,7 +5601,7 @@ static int ppo_rows_pass(sacx_handle* h, const float* s, int64_t n, const PpoRow
         r.d = ppo_forward(h, s + done * S, m);
         r.m = m;
         auto mv = [&](auto*& p, int64_t w) { if (p) p += done * w; };
-        mv(r.a, A); mv(r.nlp_old, 1); mv(r.mean_ref, A); mv(r.ls_ref, A);
+        mv(r.a, h->softmax ? 1 : A); mv(r.nlp_old, 1); mv(r.mean_ref, A); mv(r.ls_ref, A);
         mv(r.nlp_out, 1); mv(r.mean_out, A); mv(r.ls_out, A); mv(r.ent_out, 1); mv(r.kl_out, 1); mv(r.rdiff_out, 1);
         launch_ppo_rows(r, h->stream);
     }
@@ -5611,6 +5620,7 @@ int sacx_ppo_neglogp(sacx_handle* h, const float* s, const float* a, int64_t n, 
 int sacx_ppo_dist(sacx_handle* h, const float* s, int64_t n, float* mean_out, float* logstd_out, float* ent_out) {
     if (ppo_check(h)) return -1;
     if (n < 0 || (n > 0 && !s)) return fail(h, "bad arguments");
+    if (h->softmax && logstd_out) return fail(h, "a softmax handle has no logstd: logstd_out must be NULL");
     PpoRowsArgs r{};
     r.mean_out = mean_out; r.ls_out = logstd_out; r.ent_out = ent_out;
     return ppo_rows_pass(h, s, n, r);
@@ -5619,7 +5629,8 @@ int sacx_ppo_dist(sacx_handle* h, const float* s, int64_t n, float* mean_out, fl
 int sacx_ppo_kl(sacx_handle* h, const float* s, const float* mean_ref, const float* logstd_ref, int64_t n,
                 float* kl_out) {
     if (ppo_check(h)) return -1;
-    if (n < 0 || (n > 0 && (!s || !mean_ref || !logstd_ref || !kl_out))) return fail(h, "bad arguments");
+    if (h->softmax && logstd_ref) return fail(h, "a softmax handle has no logstd: logstd_ref must be NULL");
+    if (n < 0 || (n > 0 && (!s || !mean_ref || (!logstd_ref && !h->softmax) || !kl_out))) return fail(h, "bad arguments");
     PpoRowsArgs r{};
     r.mean_ref = mean_ref; r.ls_ref = logstd_ref; r.kl_out = kl_out;
     return ppo_rows_pass(h, s, n, r);
@@ -5633,7 +5644,7 @@ int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* 
     const int S = h->S, A = h->A;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     HIPCHK(h, hipMemcpyAsync(W("ppo.s"), s, sizeof(float) * (size_t)n * S, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(W("ppo.a"), a, sizeof(float) * (size_t)n * A, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(W("ppo.a"), a, sizeof(float) * (size_t)n * (h->softmax ? 1 : A), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(W("ppo.adv"), adv, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
     launch_ppo_set(nullptr, PpoPar{}, h->ptr<PpoCtl>("ppo.ctl"), W("ppo.acc"), n, h->stream);
     {   // the gradient words of the actor's parameter range: the norm and Adam read all of it, the dW
@@ -5643,7 +5654,8 @@ int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* 
         HIPCHK(h, hipMemsetAsync(ar.P + 3 * h->p_stride, 0, sizeof(float) * (size_t)ar.n, h->stream));
     }
     PpoRowsArgs r{};                  // neglogp_old, kl_info_ref, the entropy rows (ppo.py:44-46)
-    r.a = W("ppo.a"); r.nlp_out = W("ppo.nlp_old"); r.mean_out = W("ppo.mean_ref"); r.ls_out = W("ppo.ls_ref");
+    r.a = W("ppo.a"); r.nlp_out = W("ppo.nlp_old"); r.mean_out = W("ppo.mean_ref");
+    r.ls_out = h->softmax ? nullptr : W("ppo.ls_ref");
     r.ent_out = W("ppo.tmp");
     if (ppo_rows_pass(h, W("ppo.s"), n, r)) return -1;
     PpoReduceArgs q{};
@@ -5686,7 +5698,7 @@ int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out) {
     const int64_t n = h->ppo_rows;
     PpoRowsArgs r{};                  // neglogp_cur over all rows -> |r - 1|; kl against the reference (ppo.py:91-95)
     r.a = W("ppo.a"); r.nlp_old = W("ppo.nlp_old"); r.rdiff_out = W("ppo.tmp");
-    r.mean_ref = W("ppo.mean_ref"); r.ls_ref = W("ppo.ls_ref"); r.kl_out = W("ppo.tmp") + h->cap;
+    r.mean_ref = W("ppo.mean_ref"); r.ls_ref = h->softmax ? nullptr : W("ppo.ls_ref"); r.kl_out = W("ppo.tmp") + h->cap;
     if (ppo_rows_pass(h, W("ppo.s"), n, r)) return -1;
     float* lg = W("ppo.log");
     PpoReduceArgs q{};
@@ -6125,6 +6137,27 @@ int sacx_trpo_init(sacx_handle* h) {
     return 0;
 }
 
+// ---------------------------------------------------------------- SoftMaxActor on the trainable handle
+// discrete_actors.py:8-117 with _nn = create_nn(s_dim, a_dim, ...): the actor net's A outputs are logits,
+// and sacx_ppo_* / sacx_trpo_* carry the categorical neglogp, entropy and kl (k_ppo_head, k_ppo_rows,
+// k_trpo_head in their softmax mode).  The layout stays the handle's own: actor.logstd keeps its words,
+// outside the trainable range.
+int sacx_softmax_init(sacx_handle* h) {
+    if (!h) return -1;
+    if (h->bound) return fail(h, "sacx_softmax_init must precede sacx_bind");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no SoftMaxActor");
+    if (h->softmax) return fail(h, "sacx_softmax_init was already called on this handle");
+    if (h->cfg.per_state_std) return fail(h, "a softmax handle has no std: per_state_std must be 0");
+    if (h->models_only)
+        return fail(h, "SACX_EXPERT_MODELS: the world models take continuous actions, the reference defines no encoding "
+                       "of a discrete one");
+    if (h->cfg.use_expert) return fail(h, "a softmax handle needs use_expert = SACX_EXPERT_OFF");
+    h->softmax = true;
+    if (h->trpo) h->trpo_nv = actor_range(h).n;     // the flat vectors hold the net only
+    return 0;
+}
+
 static int trpo_check(sacx_handle* h) {
     if (!h || !h->bound) return fail(h, "not bound");
     if (!h->ppo)
@@ -6222,7 +6255,7 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         // the gradient takes the advantages normalised once, the line search twice (trpo.py:244-250)
         a.adv = W("trpo.adv") + (mode == 2 ? (size_t)h->cap : 0);
         a.alpha = W("ppo.alpha"); a.par = par;
-        a.TO0 = G0; a.TO1 = G1; a.vls = dir ? dir_of("actor.logstd") : nullptr;
+        a.TO0 = G0; a.TO1 = G1; a.vls = (dir && !h->softmax) ? dir_of("actor.logstd") : nullptr;
         a.D3 = ap.D3; a.E = ap.E;
         a.o_radv = W("trpo.ev"); a.o_rdiff = W("trpo.ev") + h->cap; a.o_kl = W("trpo.ev") + 2 * (size_t)h->cap;
         L.grid = (m + 3) / 4;
@@ -6272,8 +6305,9 @@ static TrCgArgs trpo_cg_args(sacx_handle* h, int phase, int it) {
     a.done = h->ptr<int32_t>("trpo.done"); a.sc = h->ptr<double>("trpo.sc");
     a.par = h->ptr<TrpoPar>("trpo.par");
     a.W = h->f("actor.l0");
-    a.ls_off = h->cfg.per_state_std ? 0 : (int64_t)(h->f("actor.logstd") - h->f("actor.l0"));
-    a.ls_n = h->cfg.per_state_std ? 0 : h->A;
+    const bool ls = !h->cfg.per_state_std && !h->softmax;       // a state-independent logstd in the range
+    a.ls_off = ls ? (int64_t)(h->f("actor.logstd") - h->f("actor.l0")) : 0;
+    a.ls_n = ls ? h->A : 0;
     a.ls_floor = (float)std::log(1e-3);
     return a;
 }

@@ -815,7 +815,7 @@ struct PpoGatherArgs {
     const PpoCtl* ctl;
     const PpoPar* par;
     const float *s_mean, *s_den;
-    int32_t S, A, mb, ldS;
+    int32_t S, A, mb, ldS;      // A: the action table's columns (1 on a softmax handle: the action index)
     float* X;                   // [mb, ldS] normalised states (pad columns 0)
     float* Arow;                // [mb, A]
     float* advn;                // [mb] centred / scaled advantages
@@ -828,6 +828,9 @@ struct PpoDist {
     const float* O; int32_t A, Aout, per_state_std;
     const float* logstd;        // [A] (state-independent std)
     float logstd_init;          // log(std_mult) (- log(log 2) with per_state_std)
+    // sacx_softmax_init: O holds the A logits of SoftMaxActor (discrete_actors.py:47-100); the action
+    // rows are then one index per row (a[rows], stored as float) and the references logits [rows, A]
+    int32_t softmax;
 };
 
 // k_ppo_head: one wave per minibatch row -- ls, nlp_cur, r, the branch of the clipped surrogate,
@@ -838,7 +841,7 @@ struct PpoHeadArgs {
     const float *Arow, *advn, *nlpo;
     const float* alpha;         // ppo.alpha[0] (the value before this step's alpha update)
     const PpoPar* par;
-    float* D3;                  // [mb, Aout] d loss / d O
+    float* D3;                  // [mb, Aout] d loss / d O (softmax: d loss / d logits)
     float* E;                   // [mb, A] d loss / d logstd per row (state-independent std; its column sums)
     float* row_loss; float* row_ent;    // [mb]
 };
@@ -861,9 +864,9 @@ struct PpoFinalArgs {
 struct PpoRowsArgs {
     PpoDist d;
     int32_t m;
-    const float* a;             // [m, A] (nlp)
+    const float* a;             // [m, A] (nlp; softmax: [m])
     const float* nlp_old;       // [m] (rdiff)
-    const float *mean_ref, *ls_ref;   // [m, A] (kl)
+    const float *mean_ref, *ls_ref;   // [m, A] (kl; softmax: the reference logits, ls_ref null)
     float *nlp_out, *mean_out, *ls_out, *ent_out, *kl_out, *rdiff_out;
 };
 // k_ppo_reduce: one workgroup -- means over n rows of up to three columns; c[2], with count2, is

@@ -64,6 +64,9 @@ struct TrTanArgs {
 //   mode 1 (the Fisher product): the output tangent TO0 + TO1 -> (t_mean, t_ls) -> M / n_sub times it,
 //          back through the head: D3 [m, Aout] and E [m, A] as mode 0 leaves them
 //   mode 2 (the line search's evaluation): per row r adv, |r - 1|, kl against the reference
+// On a softmax handle (d.softmax) lane = logit: mode 0 writes d loss / d logits, mode 1
+// u = p (t - sum_j p_j t_j) / n_sub (M = diag(p) - p p^T at the reference point), mode 2 the categorical
+// kl (discrete_actors.py:68-96); a is one index per row, mean_ref the reference logits, E is not written
 struct TrHeadArgs {
     PpoDist d;
     int32_t mode, m;

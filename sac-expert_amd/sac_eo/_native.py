@@ -46,6 +46,7 @@ EXPORTS = [
     "sacx_vcritic_steps", "sacx_vcritic_end", "sacx_vcritic_plan_info",
     "sacx_sim_collect", "sacx_model_losses_eval", "sacx_rollout_launches",
     "sacx_trpo_init", "sacx_trpo_begin", "sacx_trpo_grad", "sacx_trpo_fvp", "sacx_trpo_step", "sacx_trpo_plan_info",
+    "sacx_softmax_init",
 ]
 
 
@@ -238,6 +239,7 @@ def lib():
         "sacx_vcritic_end": (ctypes.c_int, [vp, P(f64)]),
         "sacx_vcritic_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
         "sacx_trpo_init": (ctypes.c_int, [vp]),
+        "sacx_softmax_init": (ctypes.c_int, [vp]),
         "sacx_trpo_begin": (ctypes.c_int, [vp, vp, vp, vp, i64, P(TrpoParams)]),
         "sacx_trpo_grad": (ctypes.c_int, [vp, vp]),
         "sacx_trpo_fvp": (ctypes.c_int, [vp, vp, vp, i32]),

@@ -40,6 +40,9 @@ class MBRLOnPolicyAlg:
     """Base class for MBRL algorithms with on-policy updates (``mbrl_onpolicy_alg.py:11-33``)."""
 
     def __init__(self, idx, env, env_eval, actor, critics, models, alg_kwargs, mf_update_kwargs):
+        if getattr(actor, "softmax", False):
+            raise ValueError("alg_type mbrl does not run a SoftMaxActor: the world models take continuous actions, and "
+                             "the reference defines no encoding of a discrete one")
         self._setup(alg_kwargs)
         self.env, self.env_eval = env, env_eval
         self.actor, self.critics, self.models = actor, list(critics), list(models)

@@ -110,13 +110,15 @@ class PPO:
         eng = getattr(a, "_engine", None)
         if eng is not None and getattr(eng.cfg, "trainable_gaussian", False):
             self.engine = eng
+        self._softmax = bool(getattr(a, "softmax", False))     # a SoftMaxActor: one action index per row
         if self.engine is None:
             cfg = EngineConfig(
                 s_dim=a.s_dim, a_dim=a.a_dim, hidden=tuple(a.layers), activation=a.activation,
                 actor_activations=a.activations, batch=int(n_batch),
                 buffer_capacity=int(max(n, self._rollout_capacity or 0)), per_state_std=a.per_state_std,
                 actor_gaussian="train", actor_std_mult=float(a.std_mult), actor_output_norm=a.output_norm,
-                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096, vcritics=self._vcritics)
+                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096, vcritics=self._vcritics,
+                softmax=self._softmax)
             self.engine = Engine(cfg)
             w = a.get_weights()
             a._bind(self.engine, "actor", with_logstd=False)
@@ -159,10 +161,11 @@ class PPO:
             raise ValueError(f"PPO: {n} rollout rows give no minibatch with actor_nminibatch = {self.actor_nminibatch}")
         self._ensure_engine(n, n_batch)
         eng = self.engine
+        acols = () if self._softmax else (-1,)            # the action column: [n] indices, or [n, A]
         if dev:
-            eng.ppo_begin(s_all.reshape(n, -1), a_all.reshape(n, -1), adv_all.reshape(n))
+            eng.ppo_begin(s_all.reshape(n, -1), a_all.reshape(n, *acols), adv_all.reshape(n))
         else:
-            eng.ppo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, -1),
+            eng.ppo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, *acols),
                           np.asarray(adv_all, np.float32).reshape(n))
         with self._host_rng():                             # one np.random.shuffle per iteration (:55-62)
             parts = []

@@ -70,13 +70,15 @@ class TRPO:
                 raise RuntimeError("TRPO: the actor is bound to a trainable engine without the TRPO segments "
                                    "(EngineConfig(trpo=True))")
             self.engine = eng
+        self._softmax = bool(getattr(a, "softmax", False))     # a SoftMaxActor: one action index per row
         if self.engine is None:
             cfg = EngineConfig(
                 s_dim=a.s_dim, a_dim=a.a_dim, hidden=tuple(a.layers), activation=a.activation,
                 actor_activations=a.activations, batch=int(min(n, 1024)),
                 buffer_capacity=int(max(n, self._rollout_capacity or 0)), per_state_std=a.per_state_std,
                 actor_gaussian="train", actor_std_mult=float(a.std_mult), actor_output_norm=a.output_norm,
-                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096, vcritics=self._vcritics, trpo=True)
+                actor_layer_norm=a.layer_norm, graph_steps=1, stats_capacity=4096, vcritics=self._vcritics, trpo=True,
+                softmax=self._softmax)
             self.engine = Engine(cfg)
             w = a.get_weights()
             a._bind(self.engine, "actor", with_logstd=False)
@@ -107,10 +109,11 @@ class TRPO:
         self._ensure_engine(n)
         eng = self.engine
         par = self._params()
+        acols = () if self._softmax else (-1,)            # the action column: [n] indices, or [n, A]
         if dev:
-            eng.trpo_begin(s_all.reshape(n, -1), a_all.reshape(n, -1), adv_all.reshape(n), **par)
+            eng.trpo_begin(s_all.reshape(n, -1), a_all.reshape(n, *acols), adv_all.reshape(n), **par)
         else:
-            eng.trpo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, -1),
+            eng.trpo_begin(s_all.reshape(n, -1), np.asarray(a_all, np.float32).reshape(n, *acols),
                            np.asarray(adv_all, np.float32).reshape(n), **par)
         out = eng.trpo_step(**par)
         return {k: out[k] for k in self.KEYS}

@@ -103,8 +103,18 @@ class EngineConfig:
     # trpo_grad / trpo_fvp / trpo_step.  A host-only field, as vcritics: Engine makes the handle's init call
     # right after creating it; False leaves the handle and its layout as they are
     trpo: bool = False
+    # SoftMaxActor (discrete_actors.py:8-117) on the trainable handle: the actor net's a_dim outputs are
+    # logits, and neglogp / dist / kl, the PPO step and the TRPO update carry the categorical meaning.  A
+    # host-only field, as vcritics and trpo: Engine makes the handle's init call right after creating it;
+    # False leaves the handle and its results as they are
+    softmax: bool = False
 
     def __post_init__(self):
+        if self.softmax and not self.trainable_gaussian:
+            raise ValueError("softmax=True (the SoftMaxActor) needs actor_gaussian='train'")
+        if self.softmax and (self.per_state_std or self.world_models):
+            raise ValueError("softmax=True runs without per_state_std and without world_models (the world models "
+                             "take continuous actions)")
         if self.trpo and not self.trainable_gaussian:
             raise ValueError("trpo=True (the TRPO actor update) needs actor_gaussian='train'")
         if self.bc:
@@ -250,6 +260,11 @@ class Engine:
             self.lib.sacx_destroy(h)
             self.h = None
             raise N.SacxError(f"sacx_trpo_init: {msg}")
+        if bool(getattr(cfg, "softmax", False)) and self.lib.sacx_softmax_init(h) != 0:
+            msg = (self.lib.sacx_last_error(h) or b"").decode()
+            self.lib.sacx_destroy(h)
+            self.h = None
+            raise N.SacxError(f"sacx_softmax_init: {msg}")
         total = int(self.lib.sacx_arena_bytes(h))
         self.seeds = max(1, int(cfg.seeds))
         self.seed_stride = int(self.lib.sacx_seed_stride(h))
@@ -575,10 +590,26 @@ class Engine:
 
     # ------------------------------------------------------------------ PPO actor update
     # (EngineConfig(actor_gaussian="train"); every call fails with a message on any other engine)
+    @property
+    def _softmax(self) -> bool:
+        return bool(getattr(self.cfg, "softmax", False))
+
+    def _actions(self, a) -> "torch.Tensor":
+        """The action rows on the device: [n, A], or on a softmax engine one index per row, [n] as float
+        (NumPy indices are range-checked here; CUDA tensors go through as they are)."""
+        if not self._softmax:
+            return self._dev(a, (-1, self.cfg.a_dim))
+        if self._is_host(a):
+            ai = np.asarray(a)
+            if ai.size and (np.any(ai < 0) or np.any(ai >= self.cfg.a_dim) or np.any(ai != np.floor(ai))):
+                raise ValueError(f"softmax engine: action indices must be integers in [0, {self.cfg.a_dim})")
+        return self._dev(a, (-1,))
+
     def neglogp(self, s, a) -> "torch.Tensor":
-        """GaussianActor.neglogp (continuous_actors.py:132-138): s [n, S], a [n, A] -> [n] (CUDA)."""
-        S, A = self.cfg.s_dim, self.cfg.a_dim
-        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        """GaussianActor.neglogp (continuous_actors.py:132-138): s [n, S], a [n, A] -> [n] (CUDA).  On a softmax
+        engine SoftMaxActor.neglogp (discrete_actors.py:47-54) with a [n], one action index per row."""
+        S = self.cfg.s_dim
+        x, u = self._dev(s, (-1, S)), self._actions(a)
         n = int(x.shape[0])
         if int(u.shape[0]) != n:
             raise ValueError("s and a need the same number of rows")
@@ -590,25 +621,31 @@ class Engine:
 
     def dist(self, s):
         """GaussianActor._forward and entropy (continuous_actors.py:74-100, :140-143):
-        s [n, S] -> (mean [n, A], logstd [n, A], entropy [n]) CUDA tensors."""
+        s [n, S] -> (mean [n, A], logstd [n, A], entropy [n]) CUDA tensors.  On a softmax engine
+        (logits [n, A], None, entropy [n]): get_kl_info and entropy of discrete_actors.py:56-66, :98-100."""
         S, A = self.cfg.s_dim, self.cfg.a_dim
         x = self._dev(s, (-1, S))
         n = int(x.shape[0])
         kw = dict(dtype=torch.float32, device=self.device)
-        mean, ls, ent = torch.empty((n, A), **kw), torch.empty((n, A), **kw), torch.empty((n,), **kw)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        mean, ent = torch.empty((n, A), **kw), torch.empty((n,), **kw)
+        ls = None if self._softmax else torch.empty((n, A), **kw)      # softmax: (logits, None, entropy)
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         N.check(self.lib.sacx_ppo_dist(self.h, p(x), n, p(mean), p(ls), p(ent)), self.h, "ppo_dist")
         self._keep_ppo = (x,)
         return mean, ls, ent
 
     def kl(self, s, mean_ref, logstd_ref) -> "torch.Tensor":
-        """GaussianActor.kl(direction='forward') (continuous_actors.py:159-184) -> [n] (CUDA)."""
+        """GaussianActor.kl(direction='forward') (continuous_actors.py:159-184) -> [n] (CUDA).  On a softmax
+        engine kl(s, logits_ref, None): SoftMaxActor.kl (discrete_actors.py:68-96)."""
         S, A = self.cfg.s_dim, self.cfg.a_dim
         x = self._dev(s, (-1, S))
         n = int(x.shape[0])
-        mr, lr = self._dev(mean_ref, (n, A)), self._dev(logstd_ref, (n, A))
+        if self._softmax and logstd_ref is not None:
+            raise ValueError("softmax engine: kl(s, logits_ref, None)")
+        mr = self._dev(mean_ref, (n, A))
+        lr = None if self._softmax else self._dev(logstd_ref, (n, A))
         out = torch.empty((n,), dtype=torch.float32, device=self.device)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         N.check(self.lib.sacx_ppo_kl(self.h, p(x), p(mr), p(lr), n, p(out)), self.h, "ppo_kl")
         self._keep_ppo = (x, mr, lr)
         return out
@@ -616,9 +653,9 @@ class Engine:
     def ppo_begin(self, s, a, adv) -> int:
         """The head of PPO.update (ppo.py:43-46): the rollout (s [n, S], a [n, A], adv [n]) becomes
         the table the steps gather from; neglogp_old, kl_info_ref and the mean entropy are computed
-        with the weights as they stand.  Returns n."""
+        with the weights as they stand.  Returns n.  On a softmax engine a is [n], one index per row."""
         S, A = self.cfg.s_dim, self.cfg.a_dim
-        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        x, u = self._dev(s, (-1, S)), self._actions(a)
         n = int(x.shape[0])
         w = self._dev(adv, (-1,))
         if int(u.shape[0]) != n or int(w.shape[0]) != n:
@@ -697,6 +734,8 @@ class Engine:
             i += 1
         ls = seg["actor.logstd"]
         ol = (ls["offset"] - base) // 4
+        if self._softmax:                                   # the net only: the range ends where logstd begins
+            return out, ol
         if not self.cfg.per_state_std:
             out.append((ol, (1, ls["cols"])))
         return out, ol + ls["rows"] * ls["cols"]
@@ -737,7 +776,7 @@ class Engine:
         alpha_lr, adv_center, adv_scale.  Returns n."""
         self._trpo_need()
         S, A = self.cfg.s_dim, self.cfg.a_dim
-        x, u = self._dev(s, (-1, S)), self._dev(a, (-1, A))
+        x, u = self._dev(s, (-1, S)), self._actions(a)
         n = int(x.shape[0])
         w = self._dev(adv, (-1,))
         if int(u.shape[0]) != n or int(w.shape[0]) != n:
