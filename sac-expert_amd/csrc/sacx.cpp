@@ -24,6 +24,7 @@
 #include "vcritic.h"
 #include "trpo.h"
 #include "mt_jump.h"
+#include "sampler_sched.h"
 
 #include <rccl/rccl.h>
 
@@ -227,6 +228,7 @@ struct sacx_handle {
     int64_t slot_bytes = 0;   // distance between consecutive update-input slots
     int nbatch = 4;           // sampler batch (updates per k_rng launch)
     int nslot = 8;            // update-input slots the ring rotates over (a multiple of nbatch, >= 2 nbatch)
+    int grow = 0;             // largest batch of the grown schedule of long graphs (sampler_sched.h; 0: nbatch throughout)
     // bf16 weight shadows (SACX_WBF, default on): the matrices (segment "wbf.<name>") and whether
     // add_gemm wires them into the problems it builds (the update plans only)
     struct WbfMat { std::string name; int K, N; };
@@ -550,12 +552,13 @@ void build_layout(sacx_handle* h) {
     }
     // per-slot update inputs: the sampler + gather run ahead of the updates on a side stream,
     // so everything they write rotates over a ring of slots.  A cheap sampler (HC: 1,536 normals
-    // per update) gets 32 slots: a graph of up to 32 updates draws every input at its start,
+    // per update) gets 128 slots: a graph of up to 128 updates draws every input at its start,
     // with no sampler launch waiting on the update chain (a 20-update graph otherwise waits
     // ~0.1 ms at update 8 for a sampler batch the runtime releases only when the chain reaches
-    // it); an expensive one (Humanoid: 10 MB of slot rows per update) keeps 8, the footprint
-    // the caches hold
-    h->nslot = h->n_norm <= 16384 ? NSLOT : 8;
+    // it), and a longer one draws 64 updates per batch (sampler_sched.h); four or more packed
+    // seeds multiply the ring and keep 32; an expensive sampler (Humanoid: 10 MB of slot rows
+    // per update) keeps 8, the footprint the caches hold
+    h->nslot = h->n_norm <= 16384 ? (h->seeds >= 4 ? 32 : NSLOT) : 8;
     if (const char* e = std::getenv("SACX_NSLOT")) h->nslot = std::max(2, std::min(NSLOT, std::atoi(e)));
     const int ne1 = std::max(1, h->ne);
     // config C5: critic.adam's bf16 32x32 tiles read X^T (the critic rows, the critics' layer-0
@@ -3100,17 +3103,12 @@ struct KTimeMap {
     bool rows = false;      // also stamp the row kernels (k_actor_head, k_actor_bwd): dump only
 };
 
-// Sampler batches [s, e) of a G-update call: sizes ramp 1, 2, 4, ... up to nbatch, never crossing
-// a multiple of nbatch (see get_graph)
+// Sampler batches [s, e) of a G-update call (sampler_sched.h): sizes ramp 1, 2, 4, ... up to nbatch,
+// never crossing a multiple of nbatch; a graph of kSamplerGrowMinG updates or more on a handle
+// with the grown schedule (h->grow) ramps 1, 4, 16, ... up to h->grow instead (see chain_body)
 std::vector<std::pair<int, int>> sampler_batches(const sacx_handle* h, int G) {
-    std::vector<std::pair<int, int>> batches;
-    const int nbatch = h->nbatch;
-    for (int s0 = 0, ramp = 1; s0 < G; ramp = std::min(nbatch, 2 * ramp)) {
-        const int sz = std::min({ramp, nbatch - s0 % nbatch, G - s0});
-        batches.push_back({s0, s0 + sz});
-        s0 += sz;
-    }
-    return batches;
+    if (h->grow > h->nbatch && G >= kSamplerGrowMinG) return sampler_batches_grown(G, h->grow);
+    return sampler_batches_fixed(G, h->nbatch);
 }
 
 // what get_graph captures; the caller has created the 3 G + 1 events
@@ -3164,8 +3162,9 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
         HIPCHK(h, hipStreamWaitEvent(rs, evFork, 0));
         // Sampler batches [s, e): one k_rng launch draws updates s..e-1 in stream order and one
         // gather fills their slots s % nslot .. s % nslot + (e - s) - 1 -- consecutive slots (the
-        // kernels address slot + u), so a batch never crosses a multiple of nbatch (nslot is
-        // one).  Sizes ramp 1, 2, 4, ... up to nbatch so the first update of the graph waits
+        // kernels address slot + u), so a batch never crosses a multiple of the largest batch
+        // (nslot is one).  Sizes ramp 1, 2, 4, ... up to nbatch (long graphs of a cheap sampler:
+        // 1, 4, 16, 64, sampler_sched.h) so the first update of the graph waits
         // for one update's draws only.  Slot u%nslot is last read through update u's folded
         // alpha rows in update u+1's actor.head, so batch [s, e) is drawn after the actor.head
         // of update e-nslot, and must be done before update s.  When e <= nslot its slots are
@@ -3176,7 +3175,7 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
         for (int b = 0; b < (int)batches.size(); ++b) {
             const int s0 = batches[b].first, n = batches[b].second - s0;
             if ((b + 1 < (int)batches.size() && batches[b + 1].first != batches[b].second) || n < 1 ||
-                s0 % nslot + n > nslot)
+                s0 % nslot + n > nslot || (s0 > 0 && sampler_emit_after(batches[b], nslot) >= s0))
                 return fail(h, "internal: sampler batches");
         }
         auto prologue = [&](int b) {
@@ -3202,7 +3201,7 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
         std::vector<int> batch_of(G, -1), emit_after(batches.size(), -1);
         for (int b = 0; b < (int)batches.size(); ++b) {
             batch_of[batches[b].first] = b;
-            emit_after[b] = batches[b].second - nslot;          // <= 0: slots fresh at graph start
+            emit_after[b] = sampler_emit_after(batches[b], nslot);   // <= 0: slots fresh at graph start
         }
         for (int b = 0; b < (int)batches.size(); ++b)
             if (emit_after[b] <= 0) {
@@ -3351,6 +3350,8 @@ int get_seg_graph(sacx_handle* h, int s0, int n, bool has_prev, bool is_last, hi
     }, out);
 }
 
+constexpr int kSegMaxN = 32;
+
 // whether step(n) takes the single-stream segments (SACX_SEGMENTS, default on)
 // (2: every call, the mid-call sampler batches behind the end of the segment holding the update
 // that frees their slots)
@@ -3360,8 +3361,10 @@ bool use_segments(const sacx_handle* h, int64_t n, int32_t flags) {
     // n = 1 keeps its fork / join graph: 115 vs 134 us per warm call (r04_segments_by_n_v1.txt;
     // from n = 2 on the segments win, 202 vs 209 us, 1,316 vs 1,375 us at n = 20)
     const int nmin = std::getenv("SACX_SEG_NMIN") ? std::atoi(std::getenv("SACX_SEG_NMIN")) : 2;
+    // (short = at most kSegMaxN updates, whatever the ring: the 128-slot ring would hold longer calls,
+    // but those keep their fork / join graph, measured only up to 32 updates as segments)
     return env != 0 && flags == 0 && h->dp_ranks == 0 && !h->dp_local && n >= nmin &&
-           (n <= h->nslot || (env == 2 && n <= (int64_t)1 << 24));
+           (n <= std::min(h->nslot, kSegMaxN) || (env == 2 && n <= (int64_t)1 << 24));
 }
 
 // The segments of step(n): every segment graph instantiated (prepare), or also launched (run):
@@ -3373,7 +3376,8 @@ bool use_segments(const sacx_handle* h, int64_t n, int32_t flags) {
 // so fewer cross-stream waits and graph launches (20 updates: 3 segments instead of 6)
 std::vector<std::pair<int, int>> segment_batches(const sacx_handle* h, int n) {
     static const int grow = [] { const char* e = std::getenv("SACX_SEG_GROW"); return e ? std::atoi(e) : 4; }();
-    if (grow < 2 || h->rng_jump || h->rng_split || n > h->nslot) return sampler_batches(h, n);
+    if (grow < 2 || h->rng_jump || h->rng_split || n > std::min(h->nslot, kSegMaxN))
+        return sampler_batches_fixed(n, h->nbatch);
     std::vector<std::pair<int, int>> batches;
     for (int s0 = 0, sz = 1; s0 < n; sz *= grow) {
         const int k = std::min(sz, n - s0);
@@ -3748,10 +3752,10 @@ int sacx_create(const sacx_config* cfg, sacx_handle** out) {
         return bad("action output > 64 unsupported");
     }
     if (const char* e = std::getenv("SACX_WBF")) h->wbf_enabled = std::atoi(e);
-    build_layout(h);
     h->seeds = cfg->seeds > 1 ? cfg->seeds : 1;
-    h->seed_bytes = h->seeds > 1 ? (h->arena_bytes + 65535) & ~uint64_t(65535) : h->arena_bytes;
     h->plan_seeds = cfg->single_seed_plan ? 1 : h->seeds;
+    build_layout(h);                                        // (its slot ring follows the seed count)
+    h->seed_bytes = h->seeds > 1 ? (h->arena_bytes + 65535) & ~uint64_t(65535) : h->arena_bytes;
     *out = h;
     return 0;
 }
@@ -3876,11 +3880,22 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     // 16.15k / 16.17k, profiles/r06_ab_nbatch_v1.txt -- and slowed the profiled run: 10.2k updates/s
     // and 7.73 us per k_gemm / k_fwd2 launch under rocprofv3 against 16.1k and 6.92 at 8; SACX_NBATCH=16)
     h->nbatch = h->n_norm <= 16384 ? 8 : 4;
-    if (const char* e = std::getenv("SACX_NBATCH"))   // (k_rng alone takes batches up to half the ring)
+    // Long graphs of the cheap sampler (k_rng alone) grow their batches 1, 4, 16, 64 (sampler_sched.h):
+    // every batch start costs the chain two cross-queue graph edges, and a 256-update graph has 7
+    // batches instead of 35 (SACX_BATCH_GROW: the largest batch, 0 = batches of nbatch throughout;
+    // a forced SACX_NBATCH keeps the fixed schedule).  HC 2,000 updates 17.43k against 16.25k on 32
+    // slots with batches of 8; the 128-slot ring carries most of it (17.37k with batches of 8),
+    // profiles/sampler_grow_ab_v1.txt
+    int grow = h->n_norm <= 16384 ? 64 : 0;
+    if (const char* e = std::getenv("SACX_BATCH_GROW")) grow = std::max(0, std::min(NSLOT / 2, std::atoi(e)));
+    if (const char* e = std::getenv("SACX_NBATCH")) { // (k_rng alone takes batches up to half the ring)
         h->nbatch = std::max(1, std::min(h->rng_jump || h->rng_split ? NBATCH_MAX : NSLOT / 2, std::atoi(e)));
+        grow = 0;
+    }
     if (const char* e = std::getenv("SACX_MTJ_RAMP")) h->mtj_ramp = std::atoi(e);
     if (const char* e = std::getenv("SACX_MTJ_UNDER")) h->mtj_under = std::atoi(e);
     while (h->nslot % h->nbatch || h->nslot < 2 * h->nbatch) --h->nbatch;   // the ring holds whole batches
+    h->grow = grow > 0 && !h->rng_jump && !h->rng_split ? sampler_grow_max(h->nslot, grow) : 0;
     if (h->dp_ranks > 0) {
         if (h->cfg.use_expert) return fail(h, "data-parallel mode covers plain SAC (use_expert = 0)");
         const int64_t d = (int64_t)(h->off_of("t0.l0") - h->off_of("q0.l0"));

@@ -12,10 +12,12 @@ enum Act { ACT_RELU = 0, ACT_TANH = 1, ACT_ELU = 2, ACT_NONE = 3 };
 // update-input slots: the sampler + gather fill them a batch of NBATCH updates at a time,
 // ahead of the updates that consume them (and an update's alpha rows are read one update
 // later by the folded launches); the ring holds at least two batches (sacx_handle::nslot)
+// NBATCH_MAX: the batch the segmented / split samplers' work areas hold; k_rng alone draws up to
+// half the ring per launch (NSLOT: the largest ring, and pseq's length)
 #define NBATCH_MAX 8
 #define MAX_MODELS 8        // world models (--num_models, sacx.h SACX_MAX_MODELS)
-#define NSLOT 32
-#define CTL_WORDS 48
+#define NSLOT 128
+#define CTL_WORDS (16 + NSLOT)
 
 struct Ctl {
     int64_t t_sac;          // completed updates (Adam iterations of q / pi / alpha optimisers)
