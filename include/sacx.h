@@ -573,6 +573,39 @@ int sacx_trpo_plan_info(sacx_handle* h, int64_t rows, struct sacx_launch_info* o
  *     on the host from sacx_ppo_dist's logits (:22-42; off the hot path). */
 int sacx_softmax_init(sacx_handle* h);
 
+/* --- packed on-policy learners: K PPO and VCritic steps in one launch chain --------------------
+ * The reference's only parallelism is --runs K (sac_eo/train.py:148-152): K independent learners.
+ * For the on-policy loop a minibatch step (ppo.py:55-83; base_onpolicy_alg.py:219-283) is paced by
+ * its launch count and not by its arithmetic, so K learners' steps run in the same launches.
+ *
+ * sacx_learners_init: K in [2, SACX_MAX_LEARNERS] on a SACX_ACTOR_GAUSSIAN_TRAIN handle, with or without
+ * SACX_EXPERT_MODELS, sacx_vcritic_init and sacx_softmax_init, AFTER those init calls and before
+ * sacx_arena_bytes / sacx_layout / sacx_bind.  The handle then holds K learners as a packed SAC handle
+ * holds K seeds: sacx_seed_stride = the one-learner arena rounded up to 64 KiB, sacx_arena_bytes = K
+ * strides, the layout inside a learner's block byte for byte the one-learner handle's; sacx_config is
+ * not involved (cfg.seeds stays 1).  Fails with a message on another handle kind, on a bound handle,
+ * on a second call, on K out of range and on a handle that had sacx_trpo_init; sacx_trpo_init and
+ * sacx_vcritic_init fail after it.  TRPO's conjugate gradient and line search stay one learner per handle.
+ * After it every per-learner entry point (sacx_ppo_begin / _end / _neglogp / _dist / _kl,
+ * sacx_vcritic_begin / _end / _value / _loss, sacx_gae*, sacx_sim_collect, sacx_rollout, sacx_model_fit,
+ * sacx_model_losses_eval, sacx_actor_act*, the RNG state, sacx_resync) works on the learner chosen with
+ * sacx_seed_select, and sacx_ppo_steps / sacx_vcritic_steps fail with a message naming the calls below. */
+#define SACX_MAX_LEARNERS 64
+int sacx_learners_init(sacx_handle* h, int32_t K);
+/* train.py:148-152 over ppo.py:55-83 (the actor half of base_onpolicy_alg.py:219-283's update): n_steps
+ * minibatch steps of EVERY learner in the launches of one learner's step (sacx_ppo_steps' plan at grid z = K).  idx[K][n_steps][mb] (HOST): learner k's rows
+ * of ITS rollout table (each learner needs a sacx_ppo_begin; the tables may differ in length);
+ * params[K]: learner k's run-time inputs (its own actor_lr, as the adaptlr rule makes them differ).
+ * n_steps and mb are common.  Each learner reads its own index ring, "ppo.par", "ppo.alpha", control
+ * block and statistics rows, and ends bit for bit where sacx_ppo_steps on a one-learner handle holding
+ * its state ends.  Graphs of 64 / 8 / 1 steps in a cache of their own; SACX_STEP_EAGER launches directly. */
+int sacx_ppo_steps_packed(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const sacx_ppo_params* params,
+                          int32_t flags);
+/* train.py:148-152 over base_onpolicy_alg.py:219-283 (the critic half, beside ppo.py:55-83's actor
+ * steps): the same for sacx_vcritic_steps, at any critic count: idx[K][n_steps][mb] (HOST; learner k's indices below ITS shortest critic table), critic_lr[K]. */
+int sacx_vcritic_steps_packed(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const float* critic_lr,
+                              int32_t flags);
+
 int sacx_sync(sacx_handle* h);
 /* Brings the arena to the state the calls so far define, without waiting: runs an alpha branch
  * the drop-in loop's one-update steps deferred (its alpha Adam, stats row and counters; see

@@ -5878,8 +5878,14 @@ void launch_mloss(const MLossArgs& a, hipStream_t s) {
 
 // clip_by_global_norm of the model gradients (see GNormArgs): per-chunk sums of squares in a
 // fixed order, then the norm and scale in one wave
+// PK: packed learners (the PPO step of sacx_ppo_steps_packed), grid z = learner
+template <bool PK>
 __global__ __launch_bounds__(256) void k_gnorm_part(GNormArgs a) {
     __shared__ float red[4];
+    if constexpr (PK) {
+        const int64_t so = seed_off(a.sstride);
+        a.g = sr(a.g, so); a.part = sr(a.part, so);
+    }
     const int64_t chunk = (a.n + GNORM_PARTS - 1) / GNORM_PARTS;
     const int64_t b0 = (int64_t)blockIdx.x * chunk, b1 = min(a.n, b0 + chunk);
     float acc = 0.f;
@@ -6100,11 +6106,12 @@ void launch_ln(const LNArgs& a, hipStream_t s) {
 }
 
 void launch_gnorm(const GNormArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_gnorm_part, dim3(GNORM_PARTS), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_gnorm_part<false>, dim3(GNORM_PARTS), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_gnorm_final, dim3(1), dim3(64), 0, s, a);
 }
 void launch_gnorm_part(const GNormArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_gnorm_part, dim3(GNORM_PARTS), dim3(256), 0, s, a);
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_gnorm_part<true>, dim3(GNORM_PARTS, 1, seeds_z(a.nseeds)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_gnorm_part<false>, dim3(GNORM_PARTS), dim3(256), 0, s, a);
 }
 void launch_mfinal(const MFinalArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_mfinal, dim3(1), dim3(64), 0, s, a);
@@ -6217,8 +6224,31 @@ __device__ __forceinline__ float sm_kl(float l, float lref, bool jok) {
     return (float)wave_sum_d(jok ? (e / z) * ((x - log(z)) - (xr - log(zr))) : 0.0);
 }
 
+// Packed learners (sacx_ppo_steps_packed): grid z = learner; every arena pointer of the learner-0
+// arguments moves by blockIdx.z * sstride (reloc / seed_off above).  PK false is the one-learner
+// launch: no relocation is compiled in.
+__device__ __forceinline__ void reloc(PpoGatherArgs& g, int64_t so) {
+    g.s = sr(g.s, so); g.a = sr(g.a, so); g.adv = sr(g.adv, so); g.nlp_old = sr(g.nlp_old, so);
+    g.idx_ring = sr(g.idx_ring, so); g.ctl = sr(g.ctl, so); g.par = sr(g.par, so);
+    g.s_mean = sr(g.s_mean, so); g.s_den = sr(g.s_den, so);
+    g.X = sr(g.X, so); g.Arow = sr(g.Arow, so); g.advn = sr(g.advn, so); g.nlpo = sr(g.nlpo, so); g.acc = sr(g.acc, so);
+}
+__device__ __forceinline__ void reloc(PpoHeadArgs& g, int64_t so) {
+    g.d.O = sr(g.d.O, so); g.d.logstd = sr(g.d.logstd, so);
+    g.Arow = sr(g.Arow, so); g.advn = sr(g.advn, so); g.nlpo = sr(g.nlpo, so); g.alpha = sr(g.alpha, so);
+    g.par = sr(g.par, so); g.D3 = sr(g.D3, so); g.E = sr(g.E, so);
+    g.row_loss = sr(g.row_loss, so); g.row_ent = sr(g.row_ent, so);
+}
+__device__ __forceinline__ void reloc(PpoFinalArgs& g, int64_t so) {
+    g.row_loss = sr(g.row_loss, so); g.row_ent = sr(g.row_ent, so); g.gpart = sr(g.gpart, so);
+    g.par = sr(g.par, so); g.ctl = sr(g.ctl, so); g.alpha = sr(g.alpha, so); g.acc = sr(g.acc, so);
+    g.stats = sr(g.stats, so);
+}
+
+template <bool PK>
 __global__ __launch_bounds__(256) void k_ppo_gather(PpoGatherArgs g) {
     __shared__ float red[4];
+    if constexpr (PK) reloc(g, seed_off(g.sstride));
     const int mb = g.mb, S = g.S, A = g.A, ldS = g.ldS;
     const int64_t n = g.ctl->n_rows;
     if (n < 1) return;              // (no table: the host refuses the step before it gets here)
@@ -6262,7 +6292,9 @@ __global__ __launch_bounds__(256) void k_ppo_gather(PpoGatherArgs g) {
     }
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void k_ppo_head(PpoHeadArgs g) {
+    if constexpr (PK) reloc(g, seed_off(g.sstride));
     const int wave = wave_id(), lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + wave;
     if (row >= g.mb) return;
@@ -6321,8 +6353,10 @@ __global__ __launch_bounds__(256) void k_ppo_head(PpoHeadArgs g) {
     }
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void k_ppo_final(PpoFinalArgs g) {
     __shared__ float red[4];
+    if constexpr (PK) reloc(g, seed_off(g.sstride));
     float al = 0.f, ae = 0.f, ag = 0.f;
     for (int i = threadIdx.x; i < g.mb; i += 256) {
         al = al + g.row_loss[i];
@@ -6455,9 +6489,14 @@ void launch_ppo_set(PpoPar* dst, const PpoPar& v, PpoCtl* ctl, float* acc, int64
 // k_adam_apply's arithmetic with the learning rate and the optimiser's iteration count read from the
 // device (AdamApplyArgs::lr_dev / t_dev) and the clip scale always present: the PPO actor's Adam.  Its own
 // kernel, so that k_adam_apply and every launch of the other plans stay the code they were.
+template <bool PK>
 __global__ __launch_bounds__(256) void k_ppo_adam(AdamApplyArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
+    if constexpr (PK) {         // packed learners: grid z = learner
+        const int64_t so = seed_off(a.sstride);
+        a.P = sr(a.P, so); a.scale_dev = sr(a.scale_dev, so); a.lr_dev = sr(a.lr_dev, so); a.t_dev = sr(a.t_dev, so);
+    }
     const float tt = (float)(a.t_dev[0] + 1 - a.t_adv);
     const float lr_t = a.lr_dev[0] * sqrtf(1.f - powf(0.999f, tt)) / (1.f - powf(0.9f, tt));
     float* P = a.P + i;
@@ -6471,17 +6510,24 @@ __global__ __launch_bounds__(256) void k_ppo_adam(AdamApplyArgs a) {
     P[2 * a.p_stride] = vv1;
 }
 void launch_ppo_adam(const AdamApplyArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_ppo_adam, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((a.n + 255) / 256), 1, seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_ppo_adam<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_ppo_adam<false>, grid, dim3(256), 0, s, a);
 }
 
 void launch_ppo_gather(const PpoGatherArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_ppo_gather, dim3((a.mb + PPO_GATHER_ROWS - 1) / PPO_GATHER_ROWS), dim3(256), 0, s, a);
+    const dim3 grid((a.mb + PPO_GATHER_ROWS - 1) / PPO_GATHER_ROWS, 1, seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_ppo_gather<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_ppo_gather<false>, grid, dim3(256), 0, s, a);
 }
 void launch_ppo_head(const PpoHeadArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_ppo_head, dim3((a.mb + 3) / 4), dim3(256), 0, s, a);
+    const dim3 grid((a.mb + 3) / 4, 1, seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_ppo_head<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_ppo_head<false>, grid, dim3(256), 0, s, a);
 }
 void launch_ppo_final(const PpoFinalArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_ppo_final, dim3(1), dim3(256), 0, s, a);
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_ppo_final<true>, dim3(1, 1, seeds_z(a.nseeds)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_ppo_final<false>, dim3(1), dim3(256), 0, s, a);
 }
 void launch_ppo_rows(const PpoRowsArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_ppo_rows, dim3((a.m + 3) / 4), dim3(256), 0, s, a);

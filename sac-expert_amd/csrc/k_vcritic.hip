@@ -24,10 +24,36 @@ __device__ __forceinline__ float vc_block_sum(float v, float* red) {
     return t;
 }
 
+// Packed learners (sacx_vcritic_steps_packed): grid z is the learner, and each arena pointer of the
+// (learner-0) launch arguments moves by blockIdx.z * sstride -- k_sac.hip's seed_off / reloc idiom.  PK
+// false is the one-learner launch: no relocation is compiled in.
+__device__ __forceinline__ int64_t vc_seed_off(int64_t sstride) { return (int64_t)blockIdx.z * sstride; }
+template <class T>
+__device__ __forceinline__ T* vc_sr(T* p, int64_t so) {
+    return p ? reinterpret_cast<T*>(reinterpret_cast<unsigned long long>(p) + (unsigned long long)so) : p;
+}
+__device__ __forceinline__ void reloc(VcGatherArgs& g, int64_t so) {
+    g.s = vc_sr(g.s, so); g.rtg = vc_sr(g.rtg, so); g.idx_ring = vc_sr(g.idx_ring, so); g.ctl = vc_sr(g.ctl, so);
+    g.s_mean = vc_sr(g.s_mean, so); g.s_den = vc_sr(g.s_den, so); g.ret_den = vc_sr(g.ret_den, so);
+    g.X = vc_sr(g.X, so); g.T = vc_sr(g.T, so);
+}
+__device__ __forceinline__ void reloc(VcHeadArgs& g, int64_t so) {
+    g.O = vc_sr(g.O, so); g.T = vc_sr(g.T, so); g.G = vc_sr(g.G, so); g.sq = vc_sr(g.sq, so);
+}
+__device__ __forceinline__ void reloc(VcFinalArgs& g, int64_t so) {
+    g.sq = vc_sr(g.sq, so); g.ctl = vc_sr(g.ctl, so); g.stats = vc_sr(g.stats, so);
+}
+__device__ __forceinline__ void reloc(VcAdamArgs& a, int64_t so) {
+    a.P = vc_sr(a.P, so); a.lr_dev = vc_sr(a.lr_dev, so); a.t_dev = vc_sr(a.t_dev, so);
+}
+inline unsigned vc_seeds_z(int n) { return n > 1 ? (unsigned)n : 1u; }
+
 }  // namespace
 
 // ==================================================================== the critic step's rows
+template <bool PK>
 __global__ __launch_bounds__(256) void k_vc_gather(VcGatherArgs g) {
+    if constexpr (PK) reloc(g, vc_seed_off(g.sstride));
     const int mb = g.mb, S = g.S, ldS = g.ldS, rows = g.nc * g.mb;
     const int32_t* idx = g.idx_ring + (size_t)(g.ctl->seq % VC_IDX_CAP) * g.idx_ld;
     const float rden = g.ret_den[0];
@@ -48,7 +74,9 @@ __global__ __launch_bounds__(256) void k_vc_gather(VcGatherArgs g) {
     }
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void k_vc_head(VcHeadArgs g) {
+    if constexpr (PK) reloc(g, vc_seed_off(g.sstride));
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= g.rows) return;
     // critics.py:42-49: 0.5 mean((rtg_n - v_n)^2); d / d v_n = -(rtg_n - v_n) / mb
@@ -57,7 +85,9 @@ __global__ __launch_bounds__(256) void k_vc_head(VcHeadArgs g) {
     g.sq[j] = diff * diff;
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void k_vc_final(VcFinalArgs g) {
+    if constexpr (PK) reloc(g, vc_seed_off(g.sstride));
     __shared__ float red[4];
     float loss[MAX_MODELS];
     float sum = 0.f;                // v_loss_all = 0.0, += each critic's loss (base_onpolicy_alg.py:273-280)
@@ -83,7 +113,9 @@ __global__ __launch_bounds__(256) void k_vc_final(VcFinalArgs g) {
     ctl->t = ctl->t + 1;            // (the Adam launch behind this one takes the advanced count: t_adv)
 }
 
+template <bool PK>
 __global__ __launch_bounds__(256) void k_vc_adam(VcAdamArgs a) {
+    if constexpr (PK) reloc(a, vc_seed_off(a.sstride));
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const float tt = (float)(a.t_dev[0] + 1 - a.t_adv);
@@ -242,16 +274,23 @@ __global__ __launch_bounds__(256) void k_gae_apply(GaeArgs g) {
 
 // ==================================================================== launchers
 void launch_vc_gather(const VcGatherArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_vc_gather, dim3((a.nc * a.mb + VC_GATHER_ROWS - 1) / VC_GATHER_ROWS), dim3(256), 0, s, a);
+    const dim3 grid((a.nc * a.mb + VC_GATHER_ROWS - 1) / VC_GATHER_ROWS, 1, vc_seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_vc_gather<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_vc_gather<false>, grid, dim3(256), 0, s, a);
 }
 void launch_vc_head(const VcHeadArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_vc_head, dim3((a.rows + 255) / 256), dim3(256), 0, s, a);
+    const dim3 grid((a.rows + 255) / 256, 1, vc_seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_vc_head<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_vc_head<false>, grid, dim3(256), 0, s, a);
 }
 void launch_vc_final(const VcFinalArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_vc_final, dim3(1), dim3(256), 0, s, a);
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_vc_final<true>, dim3(1, 1, vc_seeds_z(a.nseeds)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_vc_final<false>, dim3(1), dim3(256), 0, s, a);
 }
 void launch_vc_adam(const VcAdamArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_vc_adam, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((a.n + 255) / 256), 1, vc_seeds_z(a.nseeds));
+    if (a.nseeds > 1) hipLaunchKernelGGL(k_vc_adam<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_vc_adam<false>, grid, dim3(256), 0, s, a);
 }
 void launch_vc_rows(const VcRowsArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_vc_rows, dim3((a.m + 255) / 256), dim3(256), 0, s, a);

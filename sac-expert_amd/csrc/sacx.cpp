@@ -183,15 +183,27 @@ struct sacx_handle {
     bool ln = false;          // --actor_layer_norm: Dense -> LayerNorm -> tanh on the actor's layer 0
     // actor_gaussian == SACX_ACTOR_GAUSSIAN_TRAIN: the PPO actor step (sacx_ppo_*, build_ppo_plan)
     bool ppo = false;
-    int64_t ppo_rows = 0;     // rows of the rollout table (sacx_ppo_begin; 0: none yet)
-    int64_t ppo_seq_host = 0; // minibatch steps issued (mirrors PpoCtl::seq: the index ring position)
+    // host mirrors of a learner's on-policy counters: one entry per learner (sacx_learners_init), the
+    // per-learner entry points use the selected learner's (op())
+    struct OnPolicyHost {
+        int64_t ppo_rows = 0; // rows of the rollout table (sacx_ppo_begin; 0: none yet)
+        int64_t ppo_seq = 0;  // minibatch steps issued (mirrors PpoCtl::seq: the index ring position)
+        int64_t vc_rows[MAX_MODELS] = {0, 0, 0, 0, 0, 0, 0, 0};   // rows of each critic's table (mirrors VcCtl::n_rows)
+        int64_t vc_seq = 0;   // critic steps issued (mirrors VcCtl::seq: the index ring position)
+    };
+    std::vector<OnPolicyHost> onp = std::vector<OnPolicyHost>(1);
+    OnPolicyHost& op() { return onp[(size_t)sel]; }
+    // sacx_learners_init: K > 1 learners of the on-policy loop in K arena blocks (seeds = K); 0: none.
+    // sacx_ppo_steps_packed / sacx_vcritic_steps_packed run learner 0's plan at grid z = K: plans and
+    // graphs of their own (the one-learner plans hold the selected learner's pointers)
+    int learners = 0;
+    std::map<int, std::vector<Launch>> ppo_pk_plans, vc_pk_plans;
+    std::map<std::pair<int, int>, hipGraphExec_t> ppo_pk_graphs, vc_pk_graphs;
     std::map<int, std::vector<Launch>> ppo_plans;                  // minibatch rows -> one step's launches
     std::map<std::pair<int, int>, hipGraphExec_t> ppo_graphs;      // (minibatch rows, steps) -> graph
     // sacx_vcritic_init: the VCritics beside the trainable actor (sacx_vcritic_*, sacx_gae*, build_vc_plan)
     int vc = 0;               // critics (0: none; the layout is then the handle's own)
     int64_t vc_pstride = 0;   // floats between the critics' parameters, Adam moments and gradients
-    int64_t vc_rows[MAX_MODELS] = {0, 0, 0, 0, 0, 0, 0, 0};   // rows of each critic's table (mirrors VcCtl::n_rows)
-    int64_t vc_seq_host = 0;  // critic steps issued (mirrors VcCtl::seq: the index ring position)
     std::map<int, std::vector<Launch>> vc_plans;
     std::map<std::pair<int, int>, hipGraphExec_t> vc_graphs;
     // sacx_trpo_init: the TRPO actor update (sacx_trpo_*)
@@ -1009,7 +1021,7 @@ bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& nam
     Launch& L1 = plan[plan.size() - 1];
     const GemmArgs &a0 = L0.gemm, &a1 = L1.gemm;
     if (L0.kind != Launch::GEMM || L1.kind != Launch::GEMM || a0.mode != GM_FWD || a1.mode != GM_FWD) return false;
-    if (a0.t32 || a1.t32 || a0.dwl || a1.dwl || a0.bf16 || a0.nseeds > 1 || h->seeds > 1) return false;
+    if (a0.t32 || a1.t32 || a0.dwl || a1.dwl || a0.bf16 || a0.nseeds > 1 || (h->seeds > 1 && h->learners == 0)) return false;
     // layer 0 may carry the actor head (rowk 3: target tile prologues from the head's partial dots,
     // which keep the prologue free of barriers, and head rows as extra workgroups)
     const bool head = a0.rowk == 3;
@@ -1109,6 +1121,11 @@ void pack_seeds(Launch& L, int64_t stride, int n) {
     L.rng.nseeds = L.gather.nseeds = L.gemm.nseeds = L.head.nseeds = L.fin.nseeds = L.qh.nseeds = L.ab.nseeds = n;
     L.ln.sstride = stride;
     L.ln.nseeds = n;
+    // the on-policy steps (sacx_ppo_steps_packed / sacx_vcritic_steps_packed)
+    L.pg.sstride = L.ph.sstride = L.pf.sstride = L.gn.sstride = L.ap.sstride = stride;
+    L.pg.nseeds = L.ph.nseeds = L.pf.nseeds = L.gn.nseeds = L.ap.nseeds = n;
+    L.vg.sstride = L.vh.sstride = L.vf.sstride = L.va.sstride = stride;
+    L.vg.nseeds = L.vh.nseeds = L.vf.nseeds = L.va.nseeds = n;
 }
 
 // Data-parallel mode: the dW launch `L` stores its local gradients (+3 p_stride) instead of
@@ -3048,24 +3065,30 @@ int capture_plan(sacx_handle* h, const char* what, const std::vector<Launch>& pl
 // it advances with every step handed to the stream, so a failure midway leaves the two in step.  The
 // ring is filled a chunk of at most cap steps at a time; a chunk replays as graphs of 64, 8 and 1
 // back-to-back steps, cached in `graphs` by (mb, steps), or runs as plain launches (SACX_STEP_EAGER).
-int run_ring_steps(sacx_handle* h, const std::vector<Launch>& plan, int32_t* ring, int ld, int64_t cap, int64_t* seq_host,
-                   std::map<std::pair<int, int>, hipGraphExec_t>& graphs, const char* what, const int32_t* idx,
-                   int64_t n_steps, int mb, int32_t flags) {
+// Packed learners (seq_hosts holds more than one counter): `ring` is learner 0's, learner k's sits
+// k * seed_bytes behind it and takes idx[k][n_steps][mb] at its own counter; `plan` then runs them all.
+int run_ring_steps(sacx_handle* h, const std::vector<Launch>& plan, int32_t* ring, int ld, int64_t cap,
+                   const std::vector<int64_t*>& seq_hosts, std::map<std::pair<int, int>, hipGraphExec_t>& graphs,
+                   const char* what, const int32_t* idx, int64_t n_steps, int mb, int32_t flags) {
     for (int64_t done = 0; done < n_steps;) {
         const int64_t chunk = std::min<int64_t>(n_steps - done, cap);
         HIPCHK(h, hipStreamSynchronize(h->stream));   // ring rows of earlier chunks are consumed
-        // the chunk's rows are contiguous modulo the ring: at most two copies
-        const int64_t s0 = *seq_host % cap;
-        const int64_t first = std::min<int64_t>(chunk, cap - s0);
-        HIPCHK(h, hipMemcpy2D(ring + s0 * ld, sizeof(int32_t) * ld, idx + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
-                              (size_t)first, hipMemcpyHostToDevice));
-        if (chunk > first)
-            HIPCHK(h, hipMemcpy2D(ring, sizeof(int32_t) * ld, idx + (done + first) * mb, sizeof(int32_t) * mb,
-                                  sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
+        for (size_t k = 0; k < seq_hosts.size(); ++k) {
+            int32_t* rk = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ring) + k * h->seed_bytes);
+            const int32_t* ik = idx + (int64_t)k * n_steps * mb;
+            // the chunk's rows are contiguous modulo the ring: at most two copies
+            const int64_t s0 = *seq_hosts[k] % cap;
+            const int64_t first = std::min<int64_t>(chunk, cap - s0);
+            HIPCHK(h, hipMemcpy2D(rk + s0 * ld, sizeof(int32_t) * ld, ik + done * mb, sizeof(int32_t) * mb, sizeof(int32_t) * mb,
+                                  (size_t)first, hipMemcpyHostToDevice));
+            if (chunk > first)
+                HIPCHK(h, hipMemcpy2D(rk, sizeof(int32_t) * ld, ik + (done + first) * mb, sizeof(int32_t) * mb,
+                                      sizeof(int32_t) * mb, (size_t)(chunk - first), hipMemcpyHostToDevice));
+        }
         if (flags & SACX_STEP_EAGER) {
             for (int64_t j = 0; j < chunk; ++j)
                 for (const Launch& L : plan) enqueue(L, h, h->stream);
-            *seq_host += chunk;
+            for (int64_t* q : seq_hosts) *q += chunk;
             HIPCHK(h, hipGetLastError());
         } else {
             for (int64_t j = 0; j < chunk;) {
@@ -3077,7 +3100,7 @@ int run_ring_steps(sacx_handle* h, const std::vector<Launch>& plan, int32_t* rin
                     it = graphs.emplace(std::make_pair(mb, n), ex).first;
                 }
                 HIPCHK(h, hipGraphLaunch(it->second, h->stream));
-                *seq_host += n;
+                for (int64_t* q : seq_hosts) *q += n;
                 j += n;
             }
         }
@@ -3773,6 +3796,8 @@ void sacx_destroy(sacx_handle* h) {
     for (auto& kv : h->roll_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->ppo_graphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : h->vc_graphs) (void)hipGraphExecDestroy(kv.second);
+    for (auto& kv : h->ppo_pk_graphs) (void)hipGraphExecDestroy(kv.second);
+    for (auto& kv : h->vc_pk_graphs) (void)hipGraphExecDestroy(kv.second);
     if (h->trpo_graph) (void)hipGraphExecDestroy(h->trpo_graph);
     if (h->trpo_fgraph) (void)hipGraphExecDestroy(h->trpo_fgraph);
     for (auto e : h->events) (void)hipEventDestroy(e);
@@ -3855,7 +3880,8 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     // launches take 32x32 tiles too (tools/t32_dw.sh: Humanoid 4 seeds +3.5 %, 8 seeds +5 %,
     // bf16 4 seeds +8 %, HC 32 seeds +1.9 %; HC 8 / 16 seeds and one Humanoid seed even or worse)
     auto t32_of = [](int64_t rows) { return rows >= 4096 ? 1 : rows >= 1024 ? 2 : 0; };
-    h->tile32 = t32_of((int64_t)h->seeds * h->B);
+    // (packed on-policy learners keep the one-learner handle's tiles: each learner's results are its own run's)
+    h->tile32 = t32_of((int64_t)(h->learners > 1 ? 1 : h->seeds) * h->B);
     h->tile32_plan = t32_of((int64_t)h->plan_seeds * h->B);
     if (h->bc) h->tile32 = h->tile32_plan = 0;   // the BC update has the expert rows only, whatever the batch
     if (const char* e = std::getenv("SACX_T32")) h->tile32 = h->tile32_plan = std::atoi(e);
@@ -3970,14 +3996,14 @@ int sacx_resync(sacx_handle* h) {
     if (h->ppo) {                            // the step sequence (index ring position) and the table's rows
         PpoCtl pc{};
         HIPCHK(h, hipMemcpy(&pc, h->ptr<PpoCtl>("ppo.ctl"), sizeof(PpoCtl), hipMemcpyDeviceToHost));
-        h->ppo_seq_host = pc.seq;
-        h->ppo_rows = pc.n_rows;
+        h->op().ppo_seq = pc.seq;
+        h->op().ppo_rows = pc.n_rows;
     }
     if (h->vc > 0) {
         VcCtl vc{};
         HIPCHK(h, hipMemcpy(&vc, h->ptr<VcCtl>("vc.ctl"), sizeof(VcCtl), hipMemcpyDeviceToHost));
-        h->vc_seq_host = vc.seq;
-        for (int k = 0; k < MAX_MODELS; ++k) h->vc_rows[k] = vc.n_rows[k];
+        h->op().vc_seq = vc.seq;
+        for (int k = 0; k < MAX_MODELS; ++k) h->op().vc_rows[k] = vc.n_rows[k];
     }
     return 0;
 }
@@ -5494,9 +5520,7 @@ int sacx_time_graph(sacx_handle* h, int64_t n_replays, const char* skip_kernel, 
 //   actor.gnorm    the gradient range's sum of squares by chunks
 //   ppo.final      means, the clip scale, alpha's step, the statistics row, the counters
 //   actor.adam     Keras Adam over the actor's parameter range at the device-read rate
-static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
-    auto it = h->ppo_plans.find(mb);
-    if (it != h->ppo_plans.end()) return it->second;
+static std::vector<Launch> make_ppo_plan(sacx_handle* h, int mb) {
     std::vector<Launch> plan;
     const int cur = h->probs_cursor;
     const int S = h->S, A = h->A, H1 = h->H1, Aout = h->Aout, ldS = h->ldS;
@@ -5584,7 +5608,31 @@ static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
         plan.push_back(U);
     }
     h->probs_cursor = cur;
-    return h->ppo_plans.emplace(mb, std::move(plan)).first->second;
+    return plan;
+}
+static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
+    auto it = h->ppo_plans.find(mb);
+    if (it != h->ppo_plans.end()) return it->second;
+    return h->ppo_plans.emplace(mb, make_ppo_plan(h, mb)).first->second;
+}
+
+// The plan of the packed steps (sacx_learners_init): `make`'s launch list on learner 0's arena block,
+// whichever learner is selected, every launch at grid z = K (pack_seeds)
+static const std::vector<Launch>& packed_plan(sacx_handle* h, std::map<int, std::vector<Launch>>& cache, int mb,
+                                              std::vector<Launch> (*make)(sacx_handle*, int)) {
+    auto it = cache.find(mb);
+    if (it != cache.end()) return it->second;
+    char* const sel_arena = h->arena;
+    h->arena = h->arena0;
+    std::vector<Launch> plan = make(h, mb);
+    h->arena = sel_arena;
+    for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
+    return cache.emplace(mb, std::move(plan)).first->second;
+}
+static int packed_check(sacx_handle* h, const char* one) {
+    if (h->learners < 2)
+        return fail(h, std::string("the handle holds one learner (sacx_learners_init was not called): use ") + one);
+    return 0;
 }
 
 static int ppo_check(sacx_handle* h) {
@@ -5677,40 +5725,48 @@ int sacx_ppo_begin(sacx_handle* h, const float* s, const float* a, const float* 
     q.c[0] = W("ppo.tmp"); q.out[0] = W("ppo.log"); q.n = n; q.half0 = 1.f;
     launch_ppo_reduce(q, h->stream);
     HIPCHK(h, hipGetLastError());
-    h->ppo_rows = n;
+    h->op().ppo_rows = n;
     return 0;
+}
+
+static PpoPar ppo_par_of(const sacx_ppo_params& q) {
+    PpoPar par{};
+    par.clip_lo = (float)(1.0 - (double)q.eps_ppo);
+    par.clip_hi = (float)(1.0 + (double)q.eps_ppo);
+    par.max_grad_norm = q.max_grad_norm;
+    par.ent_targ = q.ent_targ; par.alpha_lr = q.alpha_lr; par.actor_lr = q.actor_lr;
+    par.ent_reg = q.ent_reg != 0; par.adv_center = q.adv_center != 0; par.adv_scale = q.adv_scale != 0;
+    return par;
 }
 
 int sacx_ppo_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const sacx_ppo_params* params,
                    int32_t flags) {
     if (ppo_check(h)) return -1;
+    if (h->learners > 1)
+        return fail(h, "the handle holds " + std::to_string(h->learners) + " learners: use sacx_ppo_steps_packed (the "
+                       "one-learner step's graphs hold one learner's pointers)");
     if (n_steps <= 0) return 0;
     if (!idx || !params) return fail(h, "null index array or parameters");
-    if (h->ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
+    if (h->op().ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
     if (mb < 1 || mb > h->B)
         return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
     for (int64_t i = 0; i < n_steps * (int64_t)mb; ++i)
-        if (idx[i] < 0 || idx[i] >= h->ppo_rows) return fail(h, "minibatch index outside the rollout table");
+        if (idx[i] < 0 || idx[i] >= h->op().ppo_rows) return fail(h, "minibatch index outside the rollout table");
     if (!(params->eps_ppo >= 0.f) || !(params->actor_lr >= 0.f) || !(params->alpha_lr >= 0.f))
         return fail(h, "eps_ppo, actor_lr and alpha_lr must be non-negative");
     const std::vector<Launch>& plan = build_ppo_plan(h, mb);
-    PpoPar par{};
-    par.clip_lo = (float)(1.0 - (double)params->eps_ppo);
-    par.clip_hi = (float)(1.0 + (double)params->eps_ppo);
-    par.max_grad_norm = params->max_grad_norm;
-    par.ent_targ = params->ent_targ; par.alpha_lr = params->alpha_lr; par.actor_lr = params->actor_lr;
-    par.ent_reg = params->ent_reg != 0; par.adv_center = params->adv_center != 0; par.adv_scale = params->adv_scale != 0;
+    const PpoPar par = ppo_par_of(*params);
     launch_ppo_set(h->ptr<PpoPar>("ppo.par"), par, h->ptr<PpoCtl>("ppo.ctl"), h->f("ppo.acc"), -1, h->stream);
-    return run_ring_steps(h, plan, h->ptr<int32_t>("ppo.idx"), h->B, PPO_IDX_CAP, &h->ppo_seq_host, h->ppo_graphs, "PPO step",
-                          idx, n_steps, mb, flags);
+    return run_ring_steps(h, plan, h->ptr<int32_t>("ppo.idx"), h->B, PPO_IDX_CAP, {&h->op().ppo_seq}, h->ppo_graphs,
+                          "PPO step", idx, n_steps, mb, flags);
 }
 
 int sacx_ppo_end(sacx_handle* h, float eps_ppo, double* out) {
     if (ppo_check(h)) return -1;
     if (!out) return fail(h, "null output");
-    if (h->ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
+    if (h->op().ppo_rows < 1) return fail(h, "no rollout table: call sacx_ppo_begin first");
     auto W = [&](const std::string& nm) { return h->f(nm); };
-    const int64_t n = h->ppo_rows;
+    const int64_t n = h->op().ppo_rows;
     PpoRowsArgs r{};                  // neglogp_cur over all rows -> |r - 1|; kl against the reference (ppo.py:91-95)
     r.a = W("ppo.a"); r.nlp_old = W("ppo.nlp_old"); r.rdiff_out = W("ppo.tmp");
     r.mean_ref = W("ppo.mean_ref"); r.ls_ref = h->softmax ? nullptr : W("ppo.ls_ref"); r.kl_out = W("ppo.tmp") + h->cap;
@@ -5757,6 +5813,7 @@ int sacx_vcritic_init(sacx_handle* h, int32_t n_critics) {
     if (!h->ppo)
         return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no VCritics");
     if (h->vc > 0) return fail(h, "sacx_vcritic_init was already called on this handle");
+    if (h->learners > 0) return fail(h, "sacx_vcritic_init must precede sacx_learners_init");
     if (n_critics < 1 || n_critics > SACX_MAX_MODELS)
         return fail(h, "n_critics " + std::to_string(n_critics) + " outside [1, SACX_MAX_MODELS = " +
                            std::to_string(SACX_MAX_MODELS) + "]");
@@ -5834,9 +5891,7 @@ static int vc_check_critic(sacx_handle* h, int32_t critic) {
 //                launch count grows with the critics (two layers: 1 launch up to 2 critics, 2 up to 5, 3 up to 8)
 //   vc.final     each critic's loss, their sum, the statistics row, the counters
 //   v.adam       one Keras Adam over the critics' parameter range at the device-read rate
-static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
-    auto it = h->vc_plans.find(mb);
-    if (it != h->vc_plans.end()) return it->second;
+static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
     std::vector<Launch> plan;
     const int cur = h->probs_cursor;
     const int S = h->S, ldS = h->ldS, nc = h->vc;
@@ -5931,7 +5986,12 @@ static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
         plan.push_back(U);
     }
     h->probs_cursor = cur;
-    return h->vc_plans.emplace(mb, std::move(plan)).first->second;
+    return plan;
+}
+static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
+    auto it = h->vc_plans.find(mb);
+    if (it != h->vc_plans.end()) return it->second;
+    return h->vc_plans.emplace(mb, make_vc_plan(h, mb)).first->second;
 }
 
 // critic `critic` on m <= ACT_CAP caller rows s: normalise, hidden layers, the output layer -> act.Q [m]
@@ -6044,18 +6104,21 @@ int sacx_vcritic_begin(sacx_handle* h, int32_t critic, const float* s, const flo
     // the weights' words only (not the padding between segments)
     HIPCHK(h, hipMemsetAsync(h->f("vc.grad"), 0, sizeof(float) * (size_t)h->vc_pstride, h->stream));
     HIPCHK(h, hipGetLastError());
-    h->vc_rows[critic] = n;
+    h->op().vc_rows[critic] = n;
     return 0;
 }
 
 int sacx_vcritic_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, float critic_lr, int32_t flags) {
     if (vc_check(h)) return -1;
+    if (h->learners > 1)
+        return fail(h, "the handle holds " + std::to_string(h->learners) + " learners: use sacx_vcritic_steps_packed (the "
+                       "one-learner step's graphs hold one learner's pointers)");
     if (n_steps <= 0) return 0;
     if (!idx) return fail(h, "null index array");
-    int64_t n_min = h->vc_rows[0];
+    int64_t n_min = h->op().vc_rows[0];
     for (int k = 0; k < h->vc; ++k) {
-        if (h->vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
-        n_min = std::min(n_min, h->vc_rows[k]);
+        if (h->op().vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
+        n_min = std::min(n_min, h->op().vc_rows[k]);
     }
     if (mb < 1 || mb > h->B)
         return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
@@ -6066,18 +6129,18 @@ int sacx_vcritic_steps(sacx_handle* h, const int32_t* idx, int64_t n_steps, int3
     VcPar par{};
     par.critic_lr = critic_lr;
     launch_vc_set(h->ptr<VcPar>("vc.par"), par, h->ptr<VcCtl>("vc.ctl"), -1, 0, h->stream);
-    return run_ring_steps(h, plan, h->ptr<int32_t>("vc.idx"), h->B, VC_IDX_CAP, &h->vc_seq_host, h->vc_graphs, "critic step", idx,
-                          n_steps, mb, flags);
+    return run_ring_steps(h, plan, h->ptr<int32_t>("vc.idx"), h->B, VC_IDX_CAP, {&h->op().vc_seq}, h->vc_graphs,
+                          "critic step", idx, n_steps, mb, flags);
 }
 
 int sacx_vcritic_end(sacx_handle* h, double* out) {
     if (vc_check(h)) return -1;
     if (!out) return fail(h, "null output");
     for (int k = 0; k < h->vc; ++k)
-        if (h->vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
+        if (h->op().vc_rows[k] < 1) return fail(h, "critic " + std::to_string(k) + " has no table: call sacx_vcritic_begin first");
     float* ls = h->f("vc.loss");
     for (int k = 0; k < h->vc; ++k)
-        if (vc_loss_pass(h, k, h->f("vc.s") + (size_t)k * h->cap * h->S, h->f("vc.rtg") + (size_t)k * h->cap, h->vc_rows[k], ls + k))
+        if (vc_loss_pass(h, k, h->f("vc.s") + (size_t)k * h->cap * h->S, h->f("vc.rtg") + (size_t)k * h->cap, h->op().vc_rows[k], ls + k))
             return -1;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float lh[MAX_MODELS];
@@ -6107,6 +6170,9 @@ int sacx_trpo_init(sacx_handle* h) {
     if (!h->ppo)
         return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no TRPO update");
     if (h->trpo) return fail(h, "sacx_trpo_init was already called on this handle");
+    if (h->learners > 0)
+        return fail(h, "a handle with sacx_learners_init runs no TRPO update: its conjugate gradient and line search are one "
+                       "learner per handle");
     static_assert(sizeof(TrpoPar) == 64, "trpo.par is 16 words");
     const int F = SACX_F32, A = h->A, Aout = h->Aout;
     const NetDims& na = h->nd[0];
@@ -6171,6 +6237,102 @@ int sacx_softmax_init(sacx_handle* h) {
     h->softmax = true;
     if (h->trpo) h->trpo_nv = actor_range(h).n;     // the flat vectors hold the net only
     return 0;
+}
+
+// ---------------------------------------------------------------- packed on-policy learners
+// The reference's --runs K (train.py:148-152) for the on-policy loop: K independent learners, each the
+// one-learner handle's layout byte for byte, in K arena blocks seed_bytes apart.  Their PPO minibatch
+// steps (ppo.py:55-83) and critic steps (base_onpolicy_alg.py:219-283) run in the same launches, grid
+// z = learner; everything else addresses the learner chosen with sacx_seed_select.
+int sacx_learners_init(sacx_handle* h, int32_t K) {
+    if (!h) return -1;
+    if (h->bound) return fail(h, "sacx_learners_init must precede sacx_bind");
+    if (!h->ppo)
+        return fail(h, "not a trainable GaussianActor handle (actor_gaussian = SACX_ACTOR_GAUSSIAN_TRAIN): no packed learners");
+    if (h->learners > 0) return fail(h, "sacx_learners_init was already called on this handle");
+    if (h->trpo)
+        return fail(h, "a handle with sacx_trpo_init holds one learner: TRPO's conjugate gradient and line search are not packed");
+    if (K < 2 || K > SACX_MAX_LEARNERS)
+        return fail(h, "learners " + std::to_string(K) + " outside [2, SACX_MAX_LEARNERS = " + std::to_string(SACX_MAX_LEARNERS) + "]");
+    h->learners = h->seeds = K;
+    h->plan_seeds = 1;                      // (every shape decision is the one-learner handle's)
+    h->seed_bytes = (h->arena_bytes + 65535) & ~uint64_t(65535);
+    h->onp.assign((size_t)K, sacx_handle::OnPolicyHost{});
+    return 0;
+}
+
+// A segment of learner k.  The step parameters go to each learner's block with one k_ppo_set / k_vc_set
+// launch per learner: they differ between learners (adaptlr, ppo.py:109-117) and ride as kernel
+// arguments, in stream order in front of the steps, as the one-learner call's do
+static void* learner_seg(const sacx_handle* h, const std::string& seg, int k) {
+    return h->arena0 + (uint64_t)k * h->seed_bytes + h->off_of(seg);
+}
+
+int sacx_ppo_steps_packed(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const sacx_ppo_params* params,
+                          int32_t flags) {
+    if (ppo_check(h)) return -1;
+    if (packed_check(h, "sacx_ppo_steps")) return -1;
+    if (n_steps <= 0) return 0;
+    if (!idx || !params) return fail(h, "null index array or parameters");
+    if (mb < 1 || mb > h->B)
+        return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
+    const int K = h->learners;
+    for (int k = 0; k < K; ++k) {
+        const int64_t rows = h->onp[k].ppo_rows;
+        if (rows < 1) return fail(h, "learner " + std::to_string(k) + " has no rollout table: call sacx_ppo_begin on it first");
+        const int32_t* ik = idx + (int64_t)k * n_steps * mb;
+        for (int64_t i = 0; i < n_steps * (int64_t)mb; ++i)
+            if (ik[i] < 0 || ik[i] >= rows)
+                return fail(h, "learner " + std::to_string(k) + ": minibatch index outside its rollout table");
+        if (!(params[k].eps_ppo >= 0.f) || !(params[k].actor_lr >= 0.f) || !(params[k].alpha_lr >= 0.f))
+            return fail(h, "learner " + std::to_string(k) + ": eps_ppo, actor_lr and alpha_lr must be non-negative");
+    }
+    const std::vector<Launch>& plan = packed_plan(h, h->ppo_pk_plans, mb, make_ppo_plan);
+    std::vector<int64_t*> seqs;
+    for (int k = 0; k < K; ++k) {
+        launch_ppo_set(static_cast<PpoPar*>(learner_seg(h, "ppo.par", k)), ppo_par_of(params[k]),
+                       static_cast<PpoCtl*>(learner_seg(h, "ppo.ctl", k)), static_cast<float*>(learner_seg(h, "ppo.acc", k)), -1,
+                       h->stream);
+        seqs.push_back(&h->onp[k].ppo_seq);
+    }
+    return run_ring_steps(h, plan, static_cast<int32_t*>(learner_seg(h, "ppo.idx", 0)), h->B, PPO_IDX_CAP, seqs,
+                          h->ppo_pk_graphs, "packed PPO step", idx, n_steps, mb, flags);
+}
+
+int sacx_vcritic_steps_packed(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t mb, const float* critic_lr,
+                              int32_t flags) {
+    if (vc_check(h)) return -1;
+    if (packed_check(h, "sacx_vcritic_steps")) return -1;
+    if (n_steps <= 0) return 0;
+    if (!idx || !critic_lr) return fail(h, "null index array or rates");
+    if (mb < 1 || mb > h->B)
+        return fail(h, "minibatch rows " + std::to_string(mb) + " outside [1, batch = " + std::to_string(h->B) + "]");
+    const int K = h->learners;
+    for (int k = 0; k < K; ++k) {
+        int64_t n_min = h->onp[k].vc_rows[0];
+        for (int c = 0; c < h->vc; ++c) {
+            if (h->onp[k].vc_rows[c] < 1)
+                return fail(h, "learner " + std::to_string(k) + ": critic " + std::to_string(c) +
+                                   " has no table: call sacx_vcritic_begin on it first");
+            n_min = std::min(n_min, h->onp[k].vc_rows[c]);
+        }
+        const int32_t* ik = idx + (int64_t)k * n_steps * mb;
+        for (int64_t i = 0; i < n_steps * (int64_t)mb; ++i)
+            if (ik[i] < 0 || ik[i] >= n_min)
+                return fail(h, "learner " + std::to_string(k) + ": minibatch index outside its shortest critic table");
+        if (!(critic_lr[k] >= 0.f)) return fail(h, "learner " + std::to_string(k) + ": critic_lr must be non-negative");
+    }
+    const std::vector<Launch>& plan = packed_plan(h, h->vc_pk_plans, mb, make_vc_plan);
+    std::vector<int64_t*> seqs;
+    for (int k = 0; k < K; ++k) {
+        VcPar par{};
+        par.critic_lr = critic_lr[k];
+        launch_vc_set(static_cast<VcPar*>(learner_seg(h, "vc.par", k)), par, static_cast<VcCtl*>(learner_seg(h, "vc.ctl", k)), -1, 0,
+                      h->stream);
+        seqs.push_back(&h->onp[k].vc_seq);
+    }
+    return run_ring_steps(h, plan, static_cast<int32_t*>(learner_seg(h, "vc.idx", 0)), h->B, VC_IDX_CAP, seqs, h->vc_pk_graphs,
+                          "packed critic step", idx, n_steps, mb, flags);
 }
 
 static int trpo_check(sacx_handle* h) {

@@ -667,6 +667,9 @@ struct AdamApplyArgs {
     // stays the code it was for every other plan
     const float* lr_dev;
     const int64_t* t_dev;
+    // packed learners (k_ppo_adam only): grid z = learner, every pointer above moves by z * sstride
+    int64_t sstride;
+    int32_t nseeds;
 };
 
 // In-process data-parallel reduce (sacx_dp_local_step): buf[r][i] = sum over r' of buf[r'][i], in
@@ -706,6 +709,9 @@ struct GNormArgs {
     float* part;                // [GNORM_PARTS]
     float* scale_out;           // [1]
     float clip;
+    // packed learners (k_gnorm_part of the PPO step): grid z = learner, g / part move by z * sstride
+    int64_t sstride;
+    int32_t nseeds;
 };
 
 // ---------------------------------------------------------------- model rollout (F2)
@@ -823,6 +829,11 @@ struct PpoGatherArgs {
     float* advn;                // [mb] centred / scaled advantages
     float* nlpo;                // [mb]
     float* acc;                 // ppo.acc
+    // packed learners (sacx_ppo_steps_packed): the K learners' arena blocks sit sstride bytes apart, grid
+    // z = learner, every pointer above moves by blockIdx.z * sstride (each learner its own table, index
+    // ring, control block and parameters)
+    int64_t sstride;
+    int32_t nseeds;
 };
 
 // the distribution of continuous_actors.py:74-100 from the actor's output rows O [rows, Aout]
@@ -846,6 +857,8 @@ struct PpoHeadArgs {
     float* D3;                  // [mb, Aout] d loss / d O (softmax: d loss / d logits)
     float* E;                   // [mb, A] d loss / d logstd per row (state-independent std; its column sums)
     float* row_loss; float* row_ent;    // [mb]
+    int64_t sstride;            // packed learners, as PpoGatherArgs
+    int32_t nseeds;
 };
 
 // k_ppo_final: one workgroup -- loss and entropy means, the global norm and the clip scale
@@ -859,6 +872,8 @@ struct PpoFinalArgs {
     float* alpha;               // [3] alpha, m, v
     float* acc;
     float* stats; int32_t stats_cap;
+    int64_t sstride;            // packed learners, as PpoGatherArgs
+    int32_t nseeds;
 };
 
 // k_ppo_rows: the whole-rollout passes over a chunk of rows (neglogp / (mean, ls) / entropy / kl /

@@ -42,6 +42,10 @@ struct VcGatherArgs {
     int32_t S, ldS, mb, nc;
     float* X;                       // [nc * mb, ldS]
     float* T;                       // [nc * mb]
+    // packed learners (sacx_vcritic_steps_packed): the K learners' arena blocks sit sstride bytes apart,
+    // grid z = learner, every pointer above moves by blockIdx.z * sstride
+    int64_t sstride;
+    int32_t nseeds;
 };
 
 // k_vc_head: per row g = (v - rtg_n) / mb (d loss / d output) and the row's squared difference
@@ -50,6 +54,8 @@ struct VcHeadArgs {
     int32_t rows, mb;
     float* G;                       // [rows]
     float* sq;                      // [rows]
+    int64_t sstride;                // packed learners, as VcGatherArgs
+    int32_t nseeds;
 };
 
 // k_vc_final: one workgroup -- each critic's 0.5 * mean of its mb squared differences (a fixed order),
@@ -59,6 +65,8 @@ struct VcFinalArgs {
     int32_t mb, nc;
     VcCtl* ctl;
     float* stats; int32_t stats_cap;
+    int64_t sstride;                // packed learners, as VcGatherArgs
+    int32_t nseeds;
 };
 
 // k_vc_adam: Keras Adam over the critics' parameter range (m, v, gradient at +1, +2, +3 p_stride), the
@@ -67,6 +75,8 @@ struct VcAdamArgs {
     float* P; int64_t n; int64_t p_stride;
     const float* lr_dev;
     const int64_t* t_dev; int32_t t_adv;    // the count used is t_dev[0] + 1 - t_adv
+    int64_t sstride;                // packed learners, as VcGatherArgs
+    int32_t nseeds;
 };
 
 // k_vc_rows: a chunk of the whole-table passes -- out[i] = Q[i] (x ret_den with value), and / or

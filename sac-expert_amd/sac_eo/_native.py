@@ -15,6 +15,7 @@ SACX_ABI_VERSION = 8
 MAX_DEPTH = 4                   # SACX_MAX_DEPTH: hidden layers per net
 MAX_WIDTH = 1024                # SACX_MAX_WIDTH: widest hidden layer
 MAX_MODELS = 8                  # SACX_MAX_MODELS: --num_models
+MAX_LEARNERS = 64               # SACX_MAX_LEARNERS: packed on-policy learners (sacx_learners_init)
 STAGE_FLOATS = 65536            # SACX_STAGE_FLOATS (include/sacx.h)
 ACT = {"relu": 0, "tanh": 1, "elu": 2}
 DTYPES = {0: "f32", 1: "i32", 2: "i64", 3: "u32", 4: "f64"}
@@ -47,6 +48,7 @@ EXPORTS = [
     "sacx_sim_collect", "sacx_model_losses_eval", "sacx_rollout_launches",
     "sacx_trpo_init", "sacx_trpo_begin", "sacx_trpo_grad", "sacx_trpo_fvp", "sacx_trpo_step", "sacx_trpo_plan_info",
     "sacx_softmax_init",
+    "sacx_learners_init", "sacx_ppo_steps_packed", "sacx_vcritic_steps_packed",
 ]
 
 
@@ -240,6 +242,9 @@ def lib():
         "sacx_vcritic_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
         "sacx_trpo_init": (ctypes.c_int, [vp]),
         "sacx_softmax_init": (ctypes.c_int, [vp]),
+        "sacx_learners_init": (ctypes.c_int, [vp, i32]),
+        "sacx_ppo_steps_packed": (ctypes.c_int, [vp, vp, i64, i32, P(PpoParams), i32]),
+        "sacx_vcritic_steps_packed": (ctypes.c_int, [vp, vp, i64, i32, P(f32), i32]),
         "sacx_trpo_begin": (ctypes.c_int, [vp, vp, vp, vp, i64, P(TrpoParams)]),
         "sacx_trpo_grad": (ctypes.c_int, [vp, vp]),
         "sacx_trpo_fvp": (ctypes.c_int, [vp, vp, vp, i32]),

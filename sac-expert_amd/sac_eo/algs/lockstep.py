@@ -11,7 +11,11 @@ stream), ``sacx_sac_step`` (the packed update graph, grid z = seed) and
 
 Lock-step needs the K loops to ask for the same update schedule: SAC_exp updates once per env
 step whatever the episode boundaries; SAC's G updates every real_step_mod steps of an episode
-need episodes of equal length (no early termination).  A divergence raises."""
+need episodes of equal length (no early termination).  A divergence raises.
+
+``run_lockstep_onpolicy`` is the same for the model-based on-policy loop (``--alg_type mbrl --mf_algo ppo
+--pack_runs``): K learners of one ``EngineConfig(learners=K)`` engine, their critic and PPO minibatch steps in one
+launch chain per update (``sac_eo.algs.model_free.packed.update_packed``)."""
 import os
 import time
 
@@ -81,3 +85,46 @@ def run_lockstep(algs, engine, total_timesteps, params_list):
             return names
         if finished:
             raise RuntimeError("packed runs diverged: some learners finished before the others")
+
+
+def run_lockstep_onpolicy(algs, engine, total_timesteps, params_list):
+    """The on-policy loop (``alg_type mbrl``, PPO) of K learners of one ``EngineConfig(learners=K)`` engine in
+    lock-step: each learner's ``_train_loop`` yields the critic update and the actor update of every policy
+    update and does everything else on its own learner (env data, model fit, sim_collect, gae, the entropy / kl
+    passes, logs, checkpoints).  A round of K identical requests is answered with
+    ``sac_eo.algs.model_free.packed.update_packed``: every prepare, ONE packed steps call, every finish -- each
+    learner's log is its serial run's.  Returns the checkpoint names."""
+    from .model_free.packed import update_packed
+    if len(algs) != engine.seeds:
+        raise ValueError("one learner per learner of the packed engine")
+    loops = [a._train_loop(total_timesteps, p) for a, p in zip(algs, params_list)]
+    names = [None] * len(loops)
+    reqs = [None] * len(loops)
+
+    def advance(send):
+        finished = 0
+        for i, lp in enumerate(loops):
+            try:
+                reqs[i] = next(lp) if send is None else lp.send(send[i])
+            except StopIteration as stop:
+                names[i] = stop.value
+                finished += 1
+        if finished and finished != len(loops):
+            raise RuntimeError("packed runs diverged: some learners finished before the others "
+                               "(use --serial_runs or drop --pack_runs)")
+        return finished == len(loops)
+
+    done = advance(None)
+    while not done:
+        kind = reqs[0][0]
+        if any(r[0] != kind for r in reqs):
+            raise RuntimeError("packed runs diverged: the learners ask for different updates "
+                               "(use --serial_runs or drop --pack_runs)")
+        if kind == "critic_update":
+            logs = update_packed([a.critic_update for a in algs], [(r[1], r[2]) for r in reqs])
+        elif kind == "actor_update":
+            logs = update_packed([a.mf_algo for a in algs], [r[1] for r in reqs])
+        else:
+            raise ValueError(kind)
+        done = advance(logs)
+    return names

@@ -14,11 +14,18 @@ the PPO-trained GaussianActor, the VCritics and the world models; the replay rin
   model (index draw, ring rows, rollout: one device call), ``Engine.gae`` per model, the critic update
   and the PPO update on ``torch.cat`` of the parts.  The rollout rows never leave the device.
 
+Packed runs (``--pack_runs``): ``alg_kwargs['_pack'] = (shared engine or None, learner, K)`` makes the learner
+one of K on one ``EngineConfig(learners=K)`` engine (through its ``SeedView``), and ``_train_loop`` -- the loop
+as a generator, as ``SACBase._train_loop`` -- hands the critic update and the actor update of
+``_update_actor_critic`` to the lock-step driver (``sac_eo.algs.lockstep.run_lockstep_onpolicy``), which
+answers a round of K requests with one packed steps call.  ``train`` answers them itself, one learner.
+
 TRPO (``alg_kwargs['mf_algo'] == 'trpo'``) runs when the class is constructed directly: it builds
 ``sac_eo.algs.model_free.trpo.TRPO`` and an engine with ``trpo=True``, and the loop logs whatever keys
 ``update`` returns.  ``init_alg`` (the front door of ``python -m sac_eo.train``) still refuses it.
 """
 import contextlib
+import dataclasses
 import time
 
 import numpy as np
@@ -43,6 +50,7 @@ class MBRLOnPolicyAlg:
         if getattr(actor, "softmax", False):
             raise ValueError("alg_type mbrl does not run a SoftMaxActor: the world models take continuous actions, and "
                              "the reference defines no encoding of a discrete one")
+        self._pack = alg_kwargs.pop("_pack", None)
         self._setup(alg_kwargs)
         self.env, self.env_eval = env, env_eval
         self.actor, self.critics, self.models = actor, list(critics), list(models)
@@ -161,7 +169,16 @@ class MBRLOnPolicyAlg:
         if cfg.separate_reward_nn:
             cfg.reward_hidden = tuple(m0.reward_layers)
             cfg.reward_activations = tuple(m0.reward_activations)
-        eng = Engine(cfg)
+        if self._pack is None:
+            eng = Engine(cfg)
+        else:                                          # one learner of a packed engine (sac_eo.algs.lockstep)
+            shared, learner, n = self._pack
+            pcfg = dataclasses.replace(cfg, learners=int(n))
+            if shared is None:
+                shared = Engine(pcfg)
+            elif shared.cfg != pcfg:
+                raise ValueError("packed runs need one configuration (shapes and hyper-parameters)")
+            eng = shared.seed_view(learner)
         a._bind(eng, "actor")
         for i, c in enumerate(self.critics):
             c._bind(eng, f"v{i}")
@@ -232,6 +249,23 @@ class MBRLOnPolicyAlg:
     def _update(self):
         self._update_models()
         self._update_actor_critic()
+
+    def _answer(self, req):
+        """One learner's own answer to a request of the loop: the update on its engine."""
+        if req[0] == "critic_update":
+            return self.critic_update.update(req[1], req[2])
+        if req[0] == "actor_update":
+            return self.mf_algo.update(req[1])
+        raise ValueError(req[0])
+
+    def _drive(self, gen):
+        """Runs a generator of the loop to its end, answering every request on this learner."""
+        try:
+            req = next(gen)
+            while True:
+                req = gen.send(self._answer(req))
+        except StopIteration as stop:
+            return stop.value
 
     def _fit(self, batches, rows, base):
         """The device steps of a list of [B, model_batch] index arrays into the training rows."""
@@ -326,6 +360,11 @@ class MBRLOnPolicyAlg:
 
     def _update_actor_critic(self):
         """mbrl_onpolicy_alg.py:124-174."""
+        return self._drive(self._update_actor_critic_gen())
+
+    def _update_actor_critic_gen(self):
+        """mbrl_onpolicy_alg.py:124-174 as a generator: yields ("critic_update", rollout_data_all, B) and
+        ("actor_update", rollout_data_agg) and takes the update's log back; everything else runs here."""
         t_ac = time.time()
         env_states = self.env_data.get_states()
         ent = np.mean(self.actor.entropy(env_states))
@@ -342,9 +381,9 @@ class MBRLOnPolicyAlg:
             rollout_data_agg = tuple(aggregate_rows(x) for x in rollout_data_all)
             steps_update = int(rollout_data_agg[0].shape[0])
             t1 = time.time()
-            log_critics = self.critic_update.update(rollout_data_all, self.B)
+            log_critics = yield ("critic_update", rollout_data_all, self.B)
             t2 = time.time()
-            log_actor = self.mf_algo.update(rollout_data_agg)
+            log_actor = yield ("actor_update", rollout_data_agg)
             t3 = time.time()
             self.logger.log_train({"steps_update": steps_update, "time_actor": t3 - t2, "time_critic": t2 - t1,
                                    "time_sim_data": t1 - t0})
@@ -357,6 +396,10 @@ class MBRLOnPolicyAlg:
     # ------------------------------------------------------------------ loop
     def train(self, total_timesteps, params):
         """base_onpolicy_alg.py:285-349."""
+        return self._drive(self._train_loop(total_timesteps, params))
+
+    def _train_loop(self, total_timesteps, params):
+        """base_onpolicy_alg.py:285-349 as a generator (the requests of _update_actor_critic_gen)."""
         self._set_rms()
         self._collect_expert_data()
         pts = lambda freq: np.concatenate((np.arange(0, total_timesteps, freq)[1:], [total_timesteps]))
@@ -369,7 +412,8 @@ class MBRLOnPolicyAlg:
             self._evaluate(num_timesteps)
         while num_timesteps < total_timesteps:
             num_timesteps += self._collect_env_data(num_timesteps)
-            self._update()
+            self._update_models()
+            yield from self._update_actor_critic_gen()
             if evaluate and num_timesteps >= eval_points[ev]:
                 self._evaluate(num_timesteps)
                 ev = min(ev + 1, len(eval_points) - 1)

@@ -97,7 +97,15 @@ class VCriticUpdate:
 
     # ------------------------------------------------------------------ update
     def update(self, rollout_data_all, B):
-        """Updates critics (``base_onpolicy_alg.py:219-266``)."""
+        """Updates critics (``base_onpolicy_alg.py:219-266``): prepare, the minibatch steps, finish."""
+        ctx = self.update_prepare(rollout_data_all, B)
+        self.update_steps(ctx)
+        return self.update_finish(ctx)
+
+    def update_prepare(self, rollout_data_all, B):
+        """``base_onpolicy_alg.py:219-242``: every critic's table (``vcritic_begin``) and the minibatch shuffles
+        drawn from this learner's stream, in the reference's order.  -> the steps' inputs: ``idx[n_steps, mb]``
+        (None without steps), ``lr``."""
         s_all_list, _, _, rtg_all_list, _, _ = rollout_data_all
         if len(self.critics) != B:
             s_all_list = [aggregate_rows(s_all_list)]           # (torch.cat for rows on the device)
@@ -123,7 +131,15 @@ class VCriticUpdate:
                 idx = np.arange(n_samples)
                 np.random.shuffle(idx)
                 parts.append(minibatches(n_samples, self.critic_nminibatch, idx))
-        if parts:
-            eng.vcritic_steps(np.concatenate(parts, 0), critic_lr=self.critic_lr)
-        out = eng.vcritic_end()
+        return dict(idx=np.concatenate(parts, 0) if parts else None, lr=self.critic_lr)
+
+    def update_steps(self, ctx):
+        """``base_onpolicy_alg.py:244-251``: every minibatch step of the update, on this learner's engine
+        (``sac_eo.algs.model_free.packed.update_packed`` runs K learners' steps in one call instead)."""
+        if ctx["idx"] is not None:
+            self.engine.vcritic_steps(ctx["idx"], critic_lr=ctx["lr"])
+
+    def update_finish(self, ctx):
+        """``base_onpolicy_alg.py:253-264``: every critic's loss over its whole table."""
+        out = self.engine.vcritic_end()
         return [{'critic_loss': out['critic_loss'][k]} for k in range(len(self.critics))]

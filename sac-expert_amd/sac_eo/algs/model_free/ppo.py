@@ -147,9 +147,21 @@ class PPO:
 
     # ------------------------------------------------------------------ update
     def update(self, rollout_data, expert_reg=None):
-        """Updates actor (``ppo.py:41-119``)."""
+        """Updates actor (``ppo.py:41-119``): prepare, the minibatch steps, finish."""
         if expert_reg is not None:
             raise NotImplementedError("PPO.update: the expert_reg branch (ppo.py:148-223) is not built")
+        ctx = self.update_prepare(rollout_data)
+        self.update_steps(ctx)
+        return self.update_finish(ctx)
+
+    def step_params(self):
+        """The run-time inputs of the minibatch steps that every learner of a packed call shares."""
+        return dict(eps_ppo=self.eps, max_grad_norm=self.max_grad_norm, ent_targ=self.ent_targ, ent_reg=self.ent_reg,
+                    alpha_lr=self.alpha_lr, adv_center=self.adv_center, adv_scale=self.adv_scale)
+
+    def update_prepare(self, rollout_data):
+        """``ppo.py:43-62``: the rollout becomes the table (``ppo_begin``) and the minibatch shuffles are drawn
+        from this learner's stream, in the reference's order.  -> the steps' inputs: ``idx[n_steps, mb]``, ``lr``."""
         s_all, a_all, adv_all, _, _, _ = rollout_data
         # CUDA tensors (Engine.sim_collect / Engine.gae rows) go to ppo_begin as they are: no host copy
         dev = _on_device(s_all)
@@ -173,11 +185,17 @@ class PPO:
                 idx = np.arange(n)
                 np.random.shuffle(idx)
                 parts.append(minibatches(n, self.actor_nminibatch, idx))
-        lr = self.actor_lr
-        eng.ppo_steps(np.concatenate(parts, 0), eps_ppo=self.eps, actor_lr=lr, max_grad_norm=self.max_grad_norm,
-                      ent_targ=self.ent_targ, ent_reg=self.ent_reg, alpha_lr=self.alpha_lr,
-                      adv_center=self.adv_center, adv_scale=self.adv_scale)
-        out = eng.ppo_end(self.eps)
+        return dict(idx=np.concatenate(parts, 0), lr=self.actor_lr)
+
+    def update_steps(self, ctx):
+        """``ppo.py:63-83``: every minibatch step of the update, on this learner's engine
+        (``sac_eo.algs.model_free.packed.update_packed`` runs K learners' steps in one call instead)."""
+        self.engine.ppo_steps(ctx["idx"], actor_lr=ctx["lr"], **self.step_params())
+
+    def update_finish(self, ctx):
+        """``ppo.py:86-119``: the whole-rollout passes (``ppo_end``), the log, the adaptlr rule."""
+        lr = ctx["lr"]
+        out = self.engine.ppo_end(self.eps)
         tv = out['tv']
         log_actor = {
             'ent': out['ent'],

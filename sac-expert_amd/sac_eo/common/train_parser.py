@@ -5,7 +5,9 @@ Same flag names, types, defaults and kwargs groups as the reference parser
 ``param`` dicts carry over.  Flags the reference accepts but never reads
 ("Dead flags") are accepted and ignored here too.  One addition
 in the setup group: ``--gpus`` (learners are placed one per GPU) and ``--serial_runs`` (run the
-``--runs`` of one process one after another instead of as lock-step packed seeds).
+``--runs`` of one process one after another instead of as lock-step packed seeds) and ``--pack_runs`` (off by
+default: the ``--runs`` of ``--alg_type mbrl --mf_algo ppo`` train as the packed learners of one engine in
+lock-step, their PPO and critic minibatch steps in one launch chain).
 """
 import argparse
 
@@ -123,6 +125,9 @@ def create_train_parser() -> argparse.ArgumentParser:
             p.add_argument("--" + typ.split(":", 1)[1], dest=name, default=default, action="store_false")
         else:
             p.add_argument("--" + name, type=typ, default=default, **kw)
+    # --pack_runs: present in the namespace only when given (read with getattr(args, "pack_runs", False)), so a
+    # command without it parses to exactly what it parsed to before
+    p.add_argument("--pack_runs", action="store_true", default=argparse.SUPPRESS)
     return p
 
 

@@ -108,8 +108,24 @@ class EngineConfig:
     # host-only field, as vcritics and trpo: Engine makes the handle's init call right after creating it;
     # False leaves the handle and its results as they are
     softmax: bool = False
+    # K on-policy learners (the reference's --runs K, train.py:148-152) packed into one handle: each learner
+    # the one-learner engine's layout in its own arena block, their PPO and critic minibatch steps in the
+    # same launches (Engine.ppo_steps_packed / vcritic_steps_packed), everything else on the learner chosen
+    # with select_seed.  A host-only field, as vcritics: Engine calls sacx_learners_init after the other init
+    # calls; 0 makes no call and leaves everything as it is.  Needs actor_gaussian="train", no trpo, seeds = 1
+    learners: int = 0
 
     def __post_init__(self):
+        if int(self.learners) != 0:
+            if not 2 <= int(self.learners) <= N.MAX_LEARNERS:
+                raise ValueError(f"learners must be 0 (one learner) or in [2, {N.MAX_LEARNERS}]")
+            if not self.trainable_gaussian:
+                raise ValueError("learners=K (packed on-policy learners) needs actor_gaussian='train'")
+            if self.trpo:
+                raise ValueError("learners=K does not run with trpo=True: TRPO's conjugate gradient and line search "
+                                 "stay one learner per engine")
+            if int(self.seeds) != 1:
+                raise ValueError("learners=K needs seeds left at 1 (seeds packs SAC learners; learners packs on-policy ones)")
         if self.softmax and not self.trainable_gaussian:
             raise ValueError("softmax=True (the SoftMaxActor) needs actor_gaussian='train'")
         if self.softmax and (self.per_state_std or self.world_models):
@@ -265,8 +281,14 @@ class Engine:
             self.lib.sacx_destroy(h)
             self.h = None
             raise N.SacxError(f"sacx_softmax_init: {msg}")
+        learners = int(getattr(cfg, "learners", 0))
+        if learners > 0 and self.lib.sacx_learners_init(h, learners) != 0:
+            msg = (self.lib.sacx_last_error(h) or b"").decode()
+            self.lib.sacx_destroy(h)
+            self.h = None
+            raise N.SacxError(f"sacx_learners_init: {msg}")
         total = int(self.lib.sacx_arena_bytes(h))
-        self.seeds = max(1, int(cfg.seeds))
+        self.seeds = learners if learners > 0 else max(1, int(cfg.seeds))
         self.seed_stride = int(self.lib.sacx_seed_stride(h))
         self._raw = torch.zeros(total + 256, dtype=torch.uint8, device=self.device)
         off = (-self._raw.data_ptr()) % 256
@@ -680,6 +702,25 @@ class Engine:
         N.check(self.lib.sacx_ppo_steps(self.h, idx.ctypes.data, int(idx.shape[0]), int(idx.shape[1]), ctypes.byref(par),
                                         N.STEP_EAGER if eager else 0), self.h, "ppo_steps")
 
+    def ppo_steps_packed(self, idx: np.ndarray, *, eps_ppo: float, actor_lr, max_grad_norm=None, ent_targ: float = 0.0,
+                         ent_reg: bool = False, alpha_lr: float = 0.0, adv_center: bool = True, adv_scale: bool = True,
+                         eager: bool = False):
+        """ppo_steps for EVERY learner of an EngineConfig(learners=K) engine in the launches of one learner's
+        steps (sacx_ppo_steps_packed): ``idx[K, n_steps, mb]``, learner k's rows of its own table;
+        ``actor_lr`` a scalar or one rate per learner (the adaptlr rule makes them differ)."""
+        K = self.seeds
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.ndim != 3 or idx.shape[0] != K:
+            raise ValueError(f"idx must be [learners = {K}, n_steps, mb]")
+        lrs = np.broadcast_to(np.asarray(actor_lr, dtype=np.float64), (K,))
+        par = (N.PpoParams * K)()
+        for k in range(K):
+            par[k] = N.PpoParams(eps_ppo=float(eps_ppo), max_grad_norm=float(max_grad_norm or 0.0), ent_targ=float(ent_targ),
+                                 alpha_lr=float(alpha_lr), actor_lr=float(lrs[k]), ent_reg=int(bool(ent_reg)),
+                                 adv_center=int(bool(adv_center)), adv_scale=int(bool(adv_scale)))
+        N.check(self.lib.sacx_ppo_steps_packed(self.h, idx.ctypes.data, int(idx.shape[1]), int(idx.shape[2]), par,
+                                               N.STEP_EAGER if eager else 0), self.h, "ppo_steps_packed")
+
     def ppo_end(self, eps_ppo: float) -> dict:
         """The tail of PPO.update (ppo.py:86-106) over the table's rows: ent, tv, kl, outside_clip,
         the two grad norms averaged over the steps since ppo_begin, alpha, the step count."""
@@ -928,6 +969,17 @@ class Engine:
             raise ValueError("idx must be [n_steps, mb]")
         N.check(self.lib.sacx_vcritic_steps(self.h, idx.ctypes.data, int(idx.shape[0]), int(idx.shape[1]), float(critic_lr),
                                             N.STEP_EAGER if eager else 0), self.h, "vcritic_steps")
+
+    def vcritic_steps_packed(self, idx: np.ndarray, *, critic_lr, eager: bool = False):
+        """vcritic_steps for EVERY learner of an EngineConfig(learners=K) engine in the launches of one learner's
+        steps (sacx_vcritic_steps_packed): ``idx[K, n_steps, mb]``; ``critic_lr`` a scalar or one per learner."""
+        K = self.seeds
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.ndim != 3 or idx.shape[0] != K:
+            raise ValueError(f"idx must be [learners = {K}, n_steps, mb]")
+        lrs = (ctypes.c_float * K)(*[float(x) for x in np.broadcast_to(np.asarray(critic_lr, dtype=np.float64), (K,))])
+        N.check(self.lib.sacx_vcritic_steps_packed(self.h, idx.ctypes.data, int(idx.shape[1]), int(idx.shape[2]), lrs,
+                                                   N.STEP_EAGER if eager else 0), self.h, "vcritic_steps_packed")
 
     def vcritic_end(self) -> dict:
         """The tail of _update_critics (base_onpolicy_alg.py:253-264): every critic's get_loss over its
@@ -1283,7 +1335,8 @@ class SeedView:
     seed first and ``v`` is the seed's views.  ``step`` / ``prepare`` advance every seed of
     the handle, so they belong to the lock-step driver (sac_eo.algs.lockstep), not to a view."""
 
-    _SHARED = ("step", "prepare", "close", "time_graph", "time_kernels", "profile", "plan_info")
+    _SHARED = ("step", "prepare", "close", "time_graph", "time_kernels", "profile", "plan_info", "ppo_steps_packed",
+               "vcritic_steps_packed")
 
     def __init__(self, engine: Engine, k: int):
         self._eng, self._k = engine, int(k)

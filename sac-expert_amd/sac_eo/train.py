@@ -6,7 +6,8 @@ Runs are spread over processes: under ``torch.distributed.run`` rank r trains ru
 ONE device handle in lock-step (sac_eo.algs.lockstep: one launch chain per timestep for all
 of them, each run's log identical to its serial run's), or -- with ``--serial_runs``, or where
 lock-step cannot hold (SAC with early-terminating episodes, ``--env_batch_type traj``,
-``--actor_layer_norm``) -- one after another.  No data moves between learners (SURVEY §8e:
+``--actor_layer_norm``) -- one after another.  ``--alg_type mbrl --mf_algo ppo --pack_runs`` trains the
+runs of one process as the packed learners of one engine (``EngineConfig(learners=K)``), in lock-step.  No data moves between learners (SURVEY §8e:
 replicas).  As in the reference (``:159-191``), the runs' checkpoint logs are gathered into one
 pickled list ``<env_type>_<env>_<alg_type>_<mf_algo>[_<save_file>]_<date>`` and removed."""
 import copy
@@ -87,15 +88,25 @@ def lockstep_ok(args, env_kwargs, k: int) -> bool:
     return True
 
 
-def train_packed(inputs_list):
-    """The runs of ``inputs_list`` as seeds of one packed handle, in lock-step."""
-    from .algs.lockstep import run_lockstep
+def train_packed(inputs_list, onpolicy=False):
+    """The runs of ``inputs_list`` as seeds of one packed handle, in lock-step (onpolicy: as the learners of
+    one ``EngineConfig(learners=K)`` engine, ``--pack_runs``)."""
+    from .algs.lockstep import run_lockstep, run_lockstep_onpolicy
     algs, shared = [], None
     for i, d in enumerate(inputs_list):
         alg = build_alg(d, pack=(shared, i, len(inputs_list)))
         shared = shared if shared is not None else alg.engine._eng
         algs.append(alg)
-    return run_lockstep(algs, shared, inputs_list[0]["alg_kwargs"]["total_timesteps"], inputs_list)
+    run = run_lockstep_onpolicy if onpolicy else run_lockstep
+    return run(algs, shared, inputs_list[0]["alg_kwargs"]["total_timesteps"], inputs_list)
+
+
+def pack_runs_ok(args, k: int) -> bool:
+    """Whether k runs of a process train as the packed learners of one engine (``--pack_runs``): the model-based
+    on-policy loop with PPO.  (TRPO's conjugate gradient and line search stay one learner per engine.)"""
+    from ._native import MAX_LEARNERS
+    return bool(getattr(args, "pack_runs", False)) and not args.serial_runs and args.alg_type == "mbrl" \
+        and args.mf_algo == "ppo" and 2 <= k <= MAX_LEARNERS
 
 
 def _train_runs(runs, run_inputs, args, local_rank=None):
@@ -106,6 +117,8 @@ def _train_runs(runs, run_inputs, args, local_rank=None):
         torch.cuda.set_device(local_rank)
     if len(runs) > 1 and lockstep_ok(args, run_inputs[0]["env_kwargs"], len(runs)):
         return dict(zip(runs, train_packed(run_inputs)))
+    if pack_runs_ok(args, len(runs)):
+        return dict(zip(runs, train_packed(run_inputs, onpolicy=True)))
     return {r: train(d) for r, d in zip(runs, run_inputs)}
 
 
@@ -138,7 +151,8 @@ def main(argv=None):
         inputs_dict["actor_kwargs"]["actor_squash"] = True
     if args.alg_type == "mbrl":
         # the model-based on-policy loop trains the plain GaussianActor (actor_squash stays False); its runs
-        # train one after another (lockstep_ok), each on its own engine
+        # train one after another (lockstep_ok), each on its own engine -- or, with --pack_runs, as the packed
+        # learners of one engine (pack_runs_ok)
         if args.actor_squash:
             raise ValueError("--alg_type mbrl trains the plain GaussianActor: --actor_squash is not supported")
         if inputs_dict["actor_kwargs"].get("actor_output_norm"):
