@@ -19,8 +19,10 @@
 // fmaf).  GEMM accumulation is the exact-f32 MFMA (k-ordered fmaf chain).
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include <math.h>
 #include "sacx_internal.h"
 
@@ -838,7 +840,7 @@ __device__ __forceinline__ int xcd_tile(int b, int T) {
     return x * q + (x < r ? x : r) + j;
 }
 
-// actor.head folded into the target tiles of q.fwd0 (GM_FWD, rowk = 3, problem headp): the
+// actor.head folded into the target tiles of q.fwd0 (GR_ACTOR_HEAD, problem headp): the
 // tile's 16 target rows get evaluate() (continuous_actors.py:327-379) from the actor's
 // layer-2 output -- mu / logstd rows = Ha2[m0.., :] W3 (a 16 x Aout MFMA tile, K = H1 split
 // over the 4 waves) -- and the A tile [state columns of A | normalised actions] is staged in
@@ -975,7 +977,7 @@ __device__ __forceinline__ void head_prologue(const HeadArgs& hd, const GemmProb
     if constexpr (SYNC) __syncthreads();
 }
 
-// actor.head.bwd folded into actor.bwd1 (rowk 4): the policy-row work of k_actor_bwd for the
+// actor.head.bwd folded into actor.bwd1 (GR_HEAD_BWD): the policy-row work of k_actor_bwd for the
 // tile's 16 rows (SAC_expert.py:262-296 through continuous_actors.py:327-379).
 // Thread (row, col) owns action col of row m0 + row: the action gradient is the sum of the
 // critics' partial dots (written by the pi.q.bwd1 tiles) scaled by the rows' output gradients,
@@ -1476,7 +1478,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         finalize_update(f, f.nred);
         return;
     }
-    if constexpr (ROWK == 3) {
+    if constexpr (gemm_rows_head(MODE, ROWK)) {
         // actor.head rows beside the tiles: dispatched first, so their serial row work
         // overlaps the tiles instead of trailing the launch
         if (tile < row_blocks) {
@@ -1486,9 +1488,9 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         tile -= row_blocks;
     }
     if (tile >= total_tiles) {
-        if constexpr (ROWK > 0 && ROWK < 3) {   // horizontally fused Q-head rows
-            qhead_block<ROWK - 1, NQ>(ga.qh, tile - total_tiles, so, ROWK == 1 ? &ga.fin : nullptr);
-        } else if constexpr (ROWK == 0 || ROWK == 7) {
+        if constexpr (gemm_rows_qhead(MODE, ROWK)) {   // horizontally fused Q-head rows
+            qhead_block<gemm_qhead_mode(ROWK), NQ>(ga.qh, tile - total_tiles, so, ROWK == GR_QHEAD ? &ga.fin : nullptr);
+        } else if constexpr (gemm_rows_mfinal(ROWK)) {
             if (ga.has_mfinal == 2) {          // the BC update's finalisation (model.bwd2 of the folded BC plan)
                 FinalArgs f = ga.fin;
                 reloc(f, so);
@@ -1507,7 +1509,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
     GemmProb g = ga.probs[p];   // by value: every field loads once, up front (speculatable)
     // the selected problem's fields of this mode, again in one batch (one asm statement: the
     // loads cannot be split by waits between separate pins)
-    if constexpr (MODE == GM_FWD && ROWK == 3) {
+    if constexpr (MODE == GM_FWD && ROWK == GR_ACTOR_HEAD) {
         // q.fwd0 with the actor head folded in (plain SAC: never an mse problem): the head
         // prologue's operands ride in the same batch
         const HeadArgs& hd = ga.head;
@@ -1517,7 +1519,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
                      "s"(hd.a_mean), "s"(hd.a_den), "s"(hd.ldh), "s"(hd.H1), "s"(hd.A), "s"(hd.Aout),
                      "s"(hd.per_state_std), "s"(hd.lim), "s"(s0.r0), "s"(s0.noise), "s"(s0.nlp_out), "s"(g.vec),
                      "s"(hd.part), "s"(hd.tq));
-    } else if constexpr (MODE == GM_FWD && ROWK == 5) {
+    } else if constexpr (MODE == GM_FWD && ROWK == GR_HEAD_PART) {
         asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.lda), "s"(g.ldb), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.tiles_n),
                      "s"(g.tile_begin), "s"(g.act), "s"(g.bias), "s"(g.vec), "s"(g.C), "s"(g.ldc),
                      "s"(g.pw), "s"(g.ppart), "s"(g.pw_ld), "s"(g.pw_cs), "s"(g.pw_n));
@@ -1525,11 +1527,11 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.lda), "s"(g.ldb), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.tiles_n),
                      "s"(g.tile_begin), "s"(g.act), "s"(g.bias), "s"(g.mse), "s"(g.se_raw), "s"(g.spe_raw),
                      "s"(g.dmean), "s"(g.dden), "s"(g.headp), "s"(g.vec));
-    } else if constexpr (MODE == GM_DX && ROWK == 2) {
+    } else if constexpr (MODE == GM_DX && ROWK == GR_PIQHEAD) {
         asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.lda), "s"(g.ldb), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.tiles_n),
                      "s"(g.tile_begin), "s"(g.act), "s"(g.wgen), "s"(g.gen_act), "s"(g.H), "s"(g.ldh), "s"(g.vec),
                      "s"(g.pw), "s"(g.ppart), "s"(g.pw_ld), "s"(g.pw_cs), "s"(g.pw_n), "s"(g.C));
-    } else if constexpr (MODE == GM_DX && ROWK == 7) {
+    } else if constexpr (MODE == GM_DX && ROWK == GR_GEN_BWD2) {
         asm volatile("" ::"s"(g.A), "s"(g.B), "s"(g.lda), "s"(g.ldb), "s"(g.M), "s"(g.N), "s"(g.K), "s"(g.tiles_n),
                      "s"(g.tile_begin), "s"(g.act), "s"(g.wgen), "s"(g.gen_act), "s"(g.H), "s"(g.ldh), "s"(g.vec),
                      "s"(g.gd), "s"(g.gst), "s"(g.gd_ld), "s"(g.g_o), "s"(g.gst_ld));
@@ -1546,9 +1548,9 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
     reloc(g, so);
     GEMM_PH(1);
     if constexpr (T32) {
-        static_assert(!(MODE == GM_FWD && ROWK == 3), "T32: plain FWD / DX / DW tiles");
-        gemm_tile32<MODE, VEC, BF, (MODE == GM_DX && ROWK == 2) || (MODE == GM_FWD && ROWK == 5),
-                    MODE == GM_FWD && ROWK == 8>(ga, g, tile - g.tile_begin, so, red);
+        static_assert(!(MODE == GM_FWD && ROWK == GR_ACTOR_HEAD), "T32: plain FWD / DX / DW tiles");
+        gemm_tile32<MODE, VEC, BF, gemm_rows_part(MODE, ROWK), MODE == GM_FWD && ROWK == GR_MSE_HEAD>(
+            ga, g, tile - g.tile_begin, so, red);
         return;
     }
     const int lt = tile - g.tile_begin;
@@ -1569,7 +1571,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
     float e4 = 0.f;
     if constexpr (MODE == GM_FWD) {
         e0 = g.bias[nnc];
-        if constexpr (ROWK == 8) {   // launches with world-model head rows (mse problems) only
+        if constexpr (ROWK == GR_MSE_HEAD) {   // launches with world-model head rows (mse problems) only
             // world-model head rows (mse): zero-sized resources when not an mse problem
             e1 = bload(rs(g.se_raw), boff(g.mse != 0, mmc * ((g.mse & MSE_FIT) ? g.ldp : g.N) + nnc));
             // (MSE_GAUSS: the model's logstd of this column; none for the reward column)
@@ -1589,10 +1591,10 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         e3 = bload(make_rsrc(g.T, g.T != nullptr ? 0x7fffffffu : 0u), (uint32_t)pidx * 4u);
     }
     EpiScalars es{};
-    if constexpr (MODE == GM_DW || (MODE == GM_FWD && ROWK == 8))
+    if constexpr (MODE == GM_DW || (MODE == GM_FWD && ROWK == GR_MSE_HEAD))
         es = epi_scalars(sr(ga.ctl, so), g.group);
     // partial-dot weights of this thread's output column (zero-sized resource: no partials)
-    constexpr bool PART = (MODE == GM_DX && ROWK == 2) || (MODE == GM_FWD && ROWK == 5);
+    constexpr bool PART = gemm_rows_part(MODE, ROWK);
     float pwv[8];
     if constexpr (PART) {
         const __amdgpu_buffer_rsrc_t rpw = rs(g.pw);
@@ -1615,7 +1617,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
     floatx4 acc1 = {0.f, 0.f, 0.f, 0.f};
     __shared__ float As[16][68];
     bool a_lds = false;
-    if constexpr (MODE == GM_FWD && ROWK == 3) {
+    if constexpr (MODE == GM_FWD && ROWK == GR_ACTOR_HEAD) {
         if (g.headp) {
             // K <= 64: at most one 16-wide k slab per wave.  Its B operand is requested before
             // the prologue, so the tile pays one memory round trip, not two.
@@ -1640,8 +1642,8 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
             a_lds = true;
         }
     }
-    __shared__ float d3s[ROWK == 4 ? 16 : 1][17];
-    if constexpr (MODE == GM_DX && ROWK == 4) {
+    __shared__ float d3s[ROWK == GR_HEAD_BWD ? 16 : 1][17];
+    if constexpr (MODE == GM_DX && ROWK == GR_HEAD_BWD) {
         // actor.bwd1 with actor.head.bwd folded in (host: one problem, K = H1 <= 256 and a multiple
         // of 16 -- at most one group of 4 whole k slabs per wave -- and Aout <= 8).  The slab operands (Ha2, W1^T and
         // the W3a rows of the generation MFMA) are requested before the prologue, so the tile
@@ -1704,14 +1706,14 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         }
         a_lds = true;
     }
-    // rowk 6 (model.fwd0 of the fit): this lane's A row is replay record phys(idx[m]) and its
+    // GR_GATHER (model.fwd0 of the fit): this lane's A row is replay record phys(idx[m]) and its
     // tile row's (t >> 4) the one whose target columns the tile stores; every address is valid
     // (clamped row, in-record columns) and out-of-range values are masked after the arithmetic
     const float* grow = nullptr;
     float traw0 = 0.f, traw1 = 0.f, tmu = 0.f, tden = 1.f;
     int tcol = 0;
     bool tstore = false;
-    if constexpr (MODE == GM_FWD && ROWK == 6) {
+    if constexpr (MODE == GM_FWD && ROWK == GR_GATHER) {
         const MGatherArgs& mg = ga.mg;
         const int64_t seq = mg.ctl->mfit_seq, start = mg.ctl->start;
         const int32_t* ir = mg.idx_ring + (seq % mg.idx_cap) * (int64_t)(mg.nm * mg.mb) + (int64_t)p * mg.mb;
@@ -1757,7 +1759,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         if (tn == 0 && mok && k0 < g.lda)        // X for model.adam's layer-0 dW (zero pad columns)
             *reinterpret_cast<float4*>(const_cast<float*>(g.A) + (size_t)m * g.lda + k0) = float4{a[0], a[1], a[2], a[3]};
     };
-    if constexpr (MODE == GM_DX && ROWK == 7) {
+    if constexpr (MODE == GM_DX && ROWK == GR_GEN_BWD2) {
         // model.bwd1 with model.bwd2 folded in (host: g_o <= 32, every problem a generated one).
         // D3 operand of the generation, per output slab t and pair member j: lane (r, grp) holds
         // D3[m0 + r][16 t + 4 grp + j] (zero past g_o / M), as model.bwd2's A operand
@@ -1860,7 +1862,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
             // iterations past it1 read a clamped (valid) slab and are zeroed
             const int k0 = (it + u) * 16 + grp * 4;
             const int k0e = (it + u < it1) ? k0 : (1 << 30);
-            if constexpr (MODE == GM_FWD && ROWK == 6) gather_a(k0e, a[u], vt);
+            if constexpr (MODE == GM_FWD && ROWK == GR_GATHER) gather_a(k0e, a[u], vt);
             else load_a<AKC, V && AKC, MODE == GM_DX>(ra, g, m, mok, k0e, a[u], rw);
             load_b<BKC, V && BKC, MODE == GM_DW>(rb, g, n, nok, k0e, b[u]);
         }
@@ -1887,7 +1889,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
         main_loop(std::false_type{});
     }
     GEMM_PH(2);
-    if constexpr (MODE == GM_FWD && ROWK == 6) {
+    if constexpr (MODE == GM_FWD && ROWK == GR_GATHER) {
         const MGatherArgs& mg = ga.mg;
         if (tstore) {
             float y = tcol < mg.S ? ((traw0 - traw1) - tmu) / tden : (traw0 - tmu) / tden;
@@ -1907,7 +1909,7 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
     float v = red[0][R][L] + red[1][R][L];
     v = v + red[2][R][L];
     v = v + red[3][R][L];
-    if constexpr (MODE == GM_FWD && ROWK == 8) {
+    if constexpr (MODE == GM_FWD && ROWK == GR_MSE_HEAD) {
         if (g.mse) {          // uniform: the expert MSE / fit-loss epilogue (all 256 threads take part)
             const bool fit = (g.mse & MSE_FIT) != 0;
             float pred = v + e0;
@@ -2043,20 +2045,20 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
 #ifndef SACX_T32_BF_WGS
 #define SACX_T32_BF_WGS 4
 #endif
-// fp32 32x32 dX tiles with the Q-head rows (rowk 1) spill 17-18 VGPRs at 6 per CU; 5 per CU
+// fp32 32x32 dX tiles with the Q-head rows (GR_QHEAD) spill 17-18 VGPRs at 6 per CU; 5 per CU
 // (no spill) measured neutral (Humanoid +0.2 %, HC 8 seeds -0.7 %, tools/ab_qh.sh), so 6 stays
 #ifndef SACX_T32_QH_WGS
 #define SACX_T32_QH_WGS SACX_T32_WGS
 #endif
-// bf16 forward tiles without world-model head rows (rowk != 8: no mse epilogue operands held over the
+// bf16 forward tiles without world-model head rows (not GR_MSE_HEAD: no mse epilogue operands held over the
 // main loop) fit 5 per CU: a 1,024-tile Humanoid q.fwd launch then runs in one round even with the
 // side stream's sampler holding a CU
 #ifndef SACX_T32_BF_FWD_WGS
 #define SACX_T32_BF_FWD_WGS 5
 #endif
 #define SACX_T32_OCC                                                                                         \
-    (T32 ? (MODE != GM_DW ? (BF ? (MODE == GM_FWD && ROWK != 8 ? SACX_T32_BF_FWD_WGS : SACX_T32_BF_WGS)          \
-                                : (MODE == GM_DX && ROWK == 1 ? SACX_T32_QH_WGS : SACX_T32_WGS))              \
+    (T32 ? (MODE != GM_DW ? (BF ? (MODE == GM_FWD && ROWK != GR_MSE_HEAD ? SACX_T32_BF_FWD_WGS : SACX_T32_BF_WGS) \
+                                : (MODE == GM_DX && ROWK == GR_QHEAD ? SACX_T32_QH_WGS : SACX_T32_WGS))       \
                           : SACX_T32_DW_WGS)                                                                 \
          : 1)
 template <int MODE, int VEC, int ROWK = 0, int NQ = 4, bool BF = false, bool PK = false, bool T32 = false>
@@ -2084,7 +2086,7 @@ __global__ __launch_bounds__(256, SACX_T32_OCC) void k_gemm(uint32_t h0, uint32_
 template <int VEC, int NQ, bool BF, bool PK = false>
 __global__ __launch_bounds__(256, 5) void k_gemm_head(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3, GemmArgs ga) {
     const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    gemm_core<GM_FWD, VEC, 3, NQ, BF, PK>(KHdr{{h0, h1, h2, h3}}, ga);
+    gemm_core<GM_FWD, VEC, GR_ACTOR_HEAD, NQ, BF, PK>(KHdr{{h0, h1, h2, h3}}, ga);
     if (ga.ktime != nullptr) {
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -2451,113 +2453,72 @@ static bool khdr_enabled() {            // (read at every launch enqueue: graph 
     return !(e && std::atoi(e) == 0);
 }
 
+// A run-time bool (or small int) as a compile-time constant: f(std::true_type{}) / f(std::false_type{})
+// (with_int: f(std::integral_constant<int, i>{}), i clamped to [0, N)).  with_bool_if<ON>: only where the
+// kernel has both forms -- elsewhere the false one alone is instantiated.
+template <class F>
+static void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <bool ON, class F>
+static void with_bool_if(bool b, F&& f) {
+    if constexpr (ON) with_bool(b, f);
+    else f(std::false_type{});
+}
+template <int N, class F>
+static void with_int(int i, F&& f) {
+    if constexpr (N == 1) f(std::integral_constant<int, 0>{});
+    else if (i >= N - 1) f(std::integral_constant<int, N - 1>{});
+    else with_int<N - 1>(i, f);
+}
+
+[[noreturn]] static void gemm_variant_die(const GemmArgs& a) {
+    fprintf(stderr, "sacx: no kernel for GEMM mode %d with rows %d (t32 %d, seeds %d, dwl %d)\n", a.mode, a.rowk, a.t32,
+            a.nseeds, a.dwl);
+    abort();
+}
+
+// One (mode, rows, packing, tile) variant of k_gemm / k_gemm_head -- those of gemm_variant_ok, no others --
+// with the launch's bf16 and float4 forms (dW + Adam reads no operand along k: VEC = 0) and, where a row
+// kernel rides along, its wide form (NQ = 8: rows past 256 columns)
+template <int MODE, int ROWS, bool PK, bool T32>
+static void launch_gemm_v(const GemmArgs& a, hipStream_t s) {
+    if constexpr (gemm_variant_ok(MODE, ROWS, T32, PK, 0)) {
+        const KHdr kh = khdr_of(a, khdr_enabled());
+        const dim3 grid(gemm_workgroups(a), 1, seeds_z(a.nseeds)), block(256);
+        constexpr bool QROWS = gemm_rows_qhead(MODE, ROWS), HROWS = gemm_rows_head(MODE, ROWS);
+        with_bool(a.bf16, [&](auto bf) {
+            with_bool_if<MODE != GM_DW>(a.vec, [&](auto vec) {
+                with_bool_if<QROWS || HROWS>((QROWS ? a.qh.H1 : a.head.H1) > 256, [&](auto wide) {
+                    constexpr bool BF = decltype(bf)::value;
+                    constexpr int V = decltype(vec)::value, NQ = decltype(wide)::value ? 8 : 4;
+                    if constexpr (MODE == GM_FWD && HROWS)
+                        hipLaunchKernelGGL((k_gemm_head<V, NQ, BF, PK>), grid, block, 0, s, KH_ARGS);
+                    else
+                        hipLaunchKernelGGL((k_gemm<MODE, V, ROWS, NQ, BF, PK, T32>), grid, block, 0, s, KH_ARGS);
+                });
+            });
+        });
+    } else {
+        gemm_variant_die(a);
+    }
+}
+
+// a.rowk among ROWS... (every GemmRows value: launch_gemm_v drops what gemm_variant_ok does not hold)
+template <int MODE, bool PK, bool T32, int... ROWS>
+static void launch_gemm_rows(const GemmArgs& a, hipStream_t s, std::integer_sequence<int, ROWS...>) {
+    if (!((a.rowk == ROWS ? (launch_gemm_v<MODE, ROWS, PK, T32>(a, s), true) : false) || ...)) gemm_variant_die(a);
+}
+
 template <bool PK, bool T32>
 static void launch_gemm_t(const GemmArgs& a, hipStream_t s) {
-    const KHdr kh = khdr_of(a, khdr_enabled());
-    const unsigned z = seeds_z(a.nseeds);
-    const dim3 grid(a.total_tiles + (a.has_final ? 1 : 0) + (a.has_mfinal ? 1 : 0), 1, z), block(256);
+    const std::make_integer_sequence<int, GR_COUNT> rows;
     switch (a.mode) {
-    case GM_FWD:
-        if (a.rowk == 3) {                 // q.fwd0 with the actor head folded in
-            const dim3 gh(a.total_tiles + (a.has_final ? 1 : 0) + a.row_blocks, 1, z);
-            const bool h8 = a.head.H1 > 256;
-#define SACX_FH(V, Q)                                                                               \
-    do {                                                                                           \
-        if (a.bf16) hipLaunchKernelGGL((k_gemm_head<V, Q, true, PK>), gh, block, 0, s, KH_ARGS);              \
-        else hipLaunchKernelGGL((k_gemm_head<V, Q, false, PK>), gh, block, 0, s, KH_ARGS);                   \
-    } while (0)
-            if (a.vec) { if (h8) SACX_FH(1, 8); else SACX_FH(1, 4); }
-            else { if (h8) SACX_FH(0, 8); else SACX_FH(0, 4); }
-#undef SACX_FH
-        } else if (a.rowk == 5) {          // actor.fwd1 (+alpha) writing the head partials
-            if (a.bf16) {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 5, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 5, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-            } else {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 5, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 5, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-            }
-        } else if (a.rowk == 6) {          // model.fwd0 of the fit, gathering its rows (one seed, 16x16)
-            if constexpr (!PK && !T32) {
-                if (a.bf16) {
-                    if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 6, 4, true, false, false>), grid, block, 0, s, KH_ARGS);
-                    else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 6, 4, true, false, false>), grid, block, 0, s, KH_ARGS);
-                } else {
-                    if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 6, 4, false, false, false>), grid, block, 0, s, KH_ARGS);
-                    else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 6, 4, false, false, false>), grid, block, 0, s, KH_ARGS);
-                }
-            }
-        } else if (a.rowk == 8) {          // with world-model head rows (mse problems)
-            if (a.bf16) {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 8, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 8, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-            } else {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 8, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 8, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-            }
-        } else if (a.bf16) {
-            if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 0, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-            else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 0, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-        } else {
-            if (a.vec) hipLaunchKernelGGL((k_gemm<GM_FWD, 1, 0, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-            else hipLaunchKernelGGL((k_gemm<GM_FWD, 0, 0, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-        }
-        break;
-    case GM_DX: {
-        const dim3 gx(a.total_tiles + (a.rowk && a.rowk < 3 ? a.row_blocks : 0) + (a.has_mfinal ? 1 : 0), 1, z);
-        const bool q8 = a.rowk && a.qh.H1 > 256;
-#define SACX_DX(V, R, Q)                                                                            \
-    do {                                                                                           \
-        if (a.bf16) hipLaunchKernelGGL((k_gemm<GM_DX, V, R, Q, true, PK, T32>), gx, block, 0, s, KH_ARGS);          \
-        else hipLaunchKernelGGL((k_gemm<GM_DX, V, R, Q, false, PK, T32>), gx, block, 0, s, KH_ARGS);                      \
-    } while (0)
-        if (a.rowk == 7) {                 // model.bwd1 with model.bwd2 folded in (one seed, 16x16)
-            if constexpr (!PK && !T32) {
-                if (a.bf16) {
-                    if (a.vec) hipLaunchKernelGGL((k_gemm<GM_DX, 1, 7, 4, true, false, false>), gx, block, 0, s, KH_ARGS);
-                    else hipLaunchKernelGGL((k_gemm<GM_DX, 0, 7, 4, true, false, false>), gx, block, 0, s, KH_ARGS);
-                } else {
-                    if (a.vec) hipLaunchKernelGGL((k_gemm<GM_DX, 1, 7, 4, false, false, false>), gx, block, 0, s, KH_ARGS);
-                    else hipLaunchKernelGGL((k_gemm<GM_DX, 0, 7, 4, false, false, false>), gx, block, 0, s, KH_ARGS);
-                }
-            }
-        } else if (a.rowk == 4) {                 // actor.bwd1 with actor.head.bwd folded in (16x16 only)
-            if (a.bf16) {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_DX, 1, 4, 4, true, PK, false>), gx, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_DX, 0, 4, 4, true, PK, false>), gx, block, 0, s, KH_ARGS);
-            } else {
-                if (a.vec) hipLaunchKernelGGL((k_gemm<GM_DX, 1, 4, 4, false, PK, false>), gx, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_DX, 0, 4, 4, false, PK, false>), gx, block, 0, s, KH_ARGS);
-            }
-        } else if (a.rowk == 1) {
-            if (a.vec) { if (q8) SACX_DX(1, 1, 8); else SACX_DX(1, 1, 4); }
-            else { if (q8) SACX_DX(0, 1, 8); else SACX_DX(0, 1, 4); }
-        } else if (a.rowk == 2) {
-            if (a.vec) { if (q8) SACX_DX(1, 2, 8); else SACX_DX(1, 2, 4); }
-            else { if (q8) SACX_DX(0, 2, 8); else SACX_DX(0, 2, 4); }
-        } else {
-            if (a.vec) SACX_DX(1, 0, 4);
-            else SACX_DX(0, 0, 4);
-        }
-#undef SACX_DX
-        break;
-    }
-    default:
-        if (a.rowk == 3) {                 // dW + Adam with the policy rows of actor.head beside it
-            const dim3 gh(a.total_tiles + a.row_blocks, 1, z);
-            const bool h8 = a.head.H1 > 256;
-            if (a.bf16) {
-                if (h8) hipLaunchKernelGGL((k_gemm<GM_DW, 0, 3, 8, true, PK, T32>), gh, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_DW, 0, 3, 4, true, PK, T32>), gh, block, 0, s, KH_ARGS);
-            } else {
-                if (h8) hipLaunchKernelGGL((k_gemm<GM_DW, 0, 3, 8, false, PK, T32>), gh, block, 0, s, KH_ARGS);
-                else hipLaunchKernelGGL((k_gemm<GM_DW, 0, 3, 4, false, PK, T32>), gh, block, 0, s, KH_ARGS);
-            }
-        } else if (a.bf16) {
-            hipLaunchKernelGGL((k_gemm<GM_DW, 0, 0, 4, true, PK, T32>), grid, block, 0, s, KH_ARGS);
-        } else {
-            hipLaunchKernelGGL((k_gemm<GM_DW, 0, 0, 4, false, PK, T32>), grid, block, 0, s, KH_ARGS);
-        }
+    case GM_FWD: return launch_gemm_rows<GM_FWD, PK, T32>(a, s, rows);
+    case GM_DX: return launch_gemm_rows<GM_DX, PK, T32>(a, s, rows);
+    case GM_DW: return launch_gemm_rows<GM_DW, PK, T32>(a, s, rows);
+    default: gemm_variant_die(a);
     }
 }
 
@@ -2573,16 +2534,16 @@ static void launch_gemm_t(const GemmArgs& a, hipStream_t s) {
 // order k_gemm's LDS reduction adds its waves', then bias and activation -- and column group 0's
 // workgroups store layer 0 for the backward.  Then layer 1: K = H0 split over the four waves as in
 // k_gemm (one group of <= 4 slabs each), A read from LDS, the partials reduced through LDS in wave
-// order, bias, activation, and (actor.fwd1, rowk 5) the head's per-tile partial dots.  Every output
+// order, bias, activation, and (actor.fwd1, GR_HEAD_PART) the head's per-tile partial dots.  Every output
 // is bit-identical to the two k_gemm launches; the launch boundary between them and layer 1's cold
 // operand round trip are gone.
-// HEAD (the target / critic pair of plain SAC, rowk 3): the first row_blocks workgroups are actor-head
+// HEAD (the target / critic pair of plain SAC, GR_PAIR_HEAD): the first row_blocks workgroups are actor-head
 // rows (4 waves each: the previous update's alpha rows, whose last block then finalises that update's
 // alpha, k_alpha_final's work, when has_final), and the target nets' tiles (headp) compute their 16
 // rows' evaluate() actions in a prologue (head_prologue, actor.fwd1's partial dots) into the LDS A tile
 // H0X: the largest layer-0 width of the variant (256, or 512: the world-model fit's model.fwd0/1 pair).
-// GATHER (rowk 6, the fit): layer 0's A rows are replay records gathered by the step's minibatch indices
-// and normalised on load (k_gemm rowk 6's arithmetic); wave 0 of column group 0 stores them to X and the
+// GATHER (GR_GATHER, the fit): layer 0's A rows are replay records gathered by the step's minibatch indices
+// and normalised on load (k_gemm GR_GATHER's arithmetic); wave 0 of column group 0 stores them to X and the
 // group's threads store the rows' targets T (get_loss :286-296) -- model.gather+fwd0+fwd1 in one launch
 #ifndef SACX_DW_DIAG_XBF
 #define SACX_DW_DIAG_XBF 0
@@ -2669,7 +2630,7 @@ __global__ __launch_bounds__(NW * 64, HEAD ? 2 * NW / 4 : 1) void k_fwd2(GemmArg
     float xa[2][4];
     const float* trec = nullptr;             // GATHER: the record of this thread's target row
     if constexpr (GATHER) {
-        // k_gemm rowk 6: row m of problem p is record start + idx_ring[seq][p][m] of the replay ring
+        // k_gemm GR_GATHER: row m of problem p is record start + idx_ring[seq][p][m] of the replay ring
         const MGatherArgs& mg = ga.mg;
         const int64_t seq = mg.ctl->mfit_seq, start = mg.ctl->start;
         const int32_t* ir = mg.idx_ring + (seq % mg.idx_cap) * (int64_t)(mg.nm * mg.mb) + (int64_t)p * mg.mb;
@@ -2739,13 +2700,13 @@ __global__ __launch_bounds__(NW * 64, HEAD ? 2 * NW / 4 : 1) void k_fwd2(GemmArg
     const int row = te >> 4, col = te & 15;
     float b1[CTW];
     constexpr int NPW = HEAD ? 1 : 8;         // (the head pair never writes the head's partial dots)
-    float pwv[CTW][NPW];                      // head partial-dot weights of this thread's columns (rowk 5)
+    float pwv[CTW][NPW];                      // head partial-dot weights of this thread's columns (GR_HEAD_PART)
 #pragma unroll
     for (int j2 = 0; j2 < CTW; ++j2) {
         const int nn = 64 * cg + 16 * (CTW * eh + j2) + col;
         b1[j2] = bload(rs(g1.bias), boff(nn < N1, nn));
         if constexpr (!HEAD) {
-            const __amdgpu_buffer_rsrc_t rpw = rs(ga.rowk == 5 ? g1.pw : nullptr);
+            const __amdgpu_buffer_rsrc_t rpw = rs(ga.rowk == GR_HEAD_PART ? g1.pw : nullptr);
 #pragma unroll
             for (int j = 0; j < NPW; ++j)
                 pwv[j2][j] = bload(rpw, boff(j < g1.pw_n && nn < N1, j * g1.pw_ld + min(nn, N1 - 1) * g1.pw_cs));
@@ -2755,7 +2716,7 @@ __global__ __launch_bounds__(NW * 64, HEAD ? 2 * NW / 4 : 1) void k_fwd2(GemmArg
     if constexpr (GATHER) {
         // the targets T[row][c] (get_loss :286-296): c < S the normalised delta sp - s, c == S the
         // reward, clipped by --delta_clip_loss / --reward_clip_loss; column group 0, 16 columns per
-        // 256 threads (k_gemm rowk 6's arithmetic)
+        // 256 threads (k_gemm GR_GATHER's arithmetic)
         const MGatherArgs& mg = ga.mg;
         const int S = mg.S, A = mg.A, tcol = 16 * eh + col, mmr = m0 + row;
         if (cg == 0 && mmr < g0.M && tcol <= S) {
@@ -2861,8 +2822,8 @@ __global__ __launch_bounds__(NW * 64, HEAD ? 2 * NW / 4 : 1) void k_fwd2(GemmArg
         v = v + red2[2][ct][R][L];
         v = v + red2[3][ct][R][L];
         const float x = nn < N1 ? act_f(v + b1[j2], g1.act) : 0.f;
-        if (!HEAD && ga.rowk == 5 && g1.ppart != nullptr) {
-            // the actor head's partial dots (k_gemm rowk 5), per 16-column tile
+        if (!HEAD && ga.rowk == GR_HEAD_PART && g1.ppart != nullptr) {
+            // the actor head's partial dots (k_gemm GR_HEAD_PART), per 16-column tile
             if (mm < g1.M) {
                 float mine = 0.f;
 #pragma unroll
@@ -2890,7 +2851,8 @@ __global__ __launch_bounds__(NW * 64, HEAD ? 2 * NW / 4 : 1) void k_fwd2(GemmArg
 }
 
 void launch_gemm(const GemmArgs& a, hipStream_t s) {
-    if (a.mode == GM_FWD2) {       // two forward layers in one launch (host: one seed, fp32, 16x16)
+    if (!gemm_variant_ok(a.mode, a.rowk, a.t32 != 0, a.nseeds > 1, a.dwl)) gemm_variant_die(a);
+    if (a.mode == GM_FWD2) {       // two forward layers in one launch (one seed, fp32, 16x16)
         // the kernel's layout: pair p's problems at 2p / 2p + 1, grid (tiles of the largest pair,
         // pairs, + a plane of head rows first for HEAD)
         GemmArgs b = a;
@@ -2902,52 +2864,47 @@ void launch_gemm(const GemmArgs& a, hipStream_t s) {
             most = std::max(most, ((a.probs[np + i].M + 15) / 16) * a.probs[np + i].tiles_n);
         }
         const dim3 block(SACX_FWD2_NW * 64), grid2(most, np);
-        if (a.rowk == 3) {          // the target / critic pair with the actor-head rows
+        // (each variant's float4 form first, and FIN from 2 down: the two FIN = 2 kernels' instruction schedule
+        // follows the order in which the variants are instantiated)
+        if (a.rowk == GR_PAIR_HEAD) {              // the target / critic pair with the actor-head rows
             const dim3 grid(std::max(most, a.row_blocks), np + 1), hblock(SACX_FWD2_HEAD_NW * 64);
-#define SACX_F2H(V, F) hipLaunchKernelGGL((k_fwd2<V, SACX_FWD2_HEAD_NW, true, F>), grid, hblock, 0, s, b)
-            if (a.has_final == 2) { if (a.vec) SACX_F2H(1, 2); else SACX_F2H(0, 2); }
-            else if (a.has_final) { if (a.vec) SACX_F2H(1, 1); else SACX_F2H(0, 1); }
-            else { if (a.vec) SACX_F2H(1, 0); else SACX_F2H(0, 0); }
-#undef SACX_F2H
-        } else if (a.rowk == 6) {   // the world-model fit's gather + two layers (16 waves, H0 <= 512)
-            if (a.vec) hipLaunchKernelGGL((k_fwd2<1, 16, false, 0, 512, true>), grid2, dim3(1024), 0, s, b);
-            else hipLaunchKernelGGL((k_fwd2<0, 16, false, 0, 512, true>), grid2, dim3(1024), 0, s, b);
-        } else if (a.rowk == 9) {   // the fit's two layers on pre-gathered rows (16 waves, H0 <= 512)
-            if (a.vec) hipLaunchKernelGGL((k_fwd2<1, 16, false, 0, 512, false>), grid2, dim3(1024), 0, s, b);
-            else hipLaunchKernelGGL((k_fwd2<0, 16, false, 0, 512, false>), grid2, dim3(1024), 0, s, b);
-        } else {
-            if (a.vec) hipLaunchKernelGGL((k_fwd2<1, SACX_FWD2_NW, false>), grid2, block, 0, s, b);
-            else hipLaunchKernelGGL((k_fwd2<0, SACX_FWD2_NW, false>), grid2, block, 0, s, b);
+            with_int<3>(a.has_final == 2 ? 2 : a.has_final ? 1 : 0, [&](auto fin) {
+                with_bool(a.vec, [&](auto vec) {
+                    constexpr int V = decltype(vec)::value, FIN = decltype(fin)::value;
+                    hipLaunchKernelGGL((k_fwd2<V, SACX_FWD2_HEAD_NW, true, FIN>), grid, hblock, 0, s, b);
+                });
+            });
+        } else if (a.rowk == GR_GATHER) {                 // the world-model fit's gather + two layers (16 waves, H0 <= 512)
+            with_bool(a.vec, [&](auto vec) {
+                hipLaunchKernelGGL((k_fwd2<decltype(vec)::value, 16, false, 0, 512, true>), grid2, dim3(1024), 0, s, b);
+            });
+        } else if (a.rowk == GR_PREGATHERED) {     // the fit's two layers on pre-gathered rows (16 waves, H0 <= 512)
+            with_bool(a.vec, [&](auto vec) {
+                hipLaunchKernelGGL((k_fwd2<decltype(vec)::value, 16, false, 0, 512, false>), grid2, dim3(1024), 0, s, b);
+            });
+        } else {                                   // GR_NONE, GR_HEAD_PART (a run-time test in the epilogue)
+            with_bool(a.vec, [&](auto vec) {
+                hipLaunchKernelGGL((k_fwd2<decltype(vec)::value, SACX_FWD2_NW, false>), grid2, block, 0, s, b);
+            });
         }
         return;
     }
     if (a.dwl) {   // dW + Adam with LDS-staged rows: plain problems only (no fused rows, no alpha.final)
         const dim3 grid(a.total_tiles, 1, seeds_z(a.nseeds)), block(256);
         const KHdr kh = khdr_of(a, khdr_enabled());
-#define SACX_DWLL(NH)                                                                                  \
-    do {                                                                                              \
-        if (a.nseeds > 1) {                                                                           \
-            if (a.bf16) hipLaunchKernelGGL((k_dwl<true, true, NH>), grid, block, 0, s, KH_ARGS);            \
-            else hipLaunchKernelGGL((k_dwl<false, true, NH>), grid, block, 0, s, KH_ARGS);                  \
-        } else {                                                                                      \
-            if (a.bf16) hipLaunchKernelGGL((k_dwl<true, false, NH>), grid, block, 0, s, KH_ARGS);           \
-            else hipLaunchKernelGGL((k_dwl<false, false, NH>), grid, block, 0, s, KH_ARGS);                 \
-        }                                                                                             \
-    } while (0)
-        if (a.dwl == 2) SACX_DWLL(1);      // 32x16 tiles
-        else SACX_DWLL(2);                 // 32x32 tiles
-#undef SACX_DWLL
+        with_bool(a.bf16, [&](auto bf) {
+            with_bool(a.nseeds > 1, [&](auto pk) {
+                with_bool(a.dwl == 2, [&](auto half) {     // 32x16 tiles, else 32x32
+                    constexpr int NH = decltype(half)::value ? 1 : 2;
+                    hipLaunchKernelGGL((k_dwl<decltype(bf)::value, decltype(pk)::value, NH>), grid, block, 0, s, KH_ARGS);
+                });
+            });
+        });
         return;
     }
-    // 32x32 tiles: plain FWD / DX / DW launches only (the host never sets t32 elsewhere)
-    const bool t32 = a.t32 && !(a.mode == GM_FWD && a.rowk == 3);
-    if (a.nseeds > 1) {
-        if (t32) launch_gemm_t<true, true>(a, s);
-        else launch_gemm_t<true, false>(a, s);
-    } else {
-        if (t32) launch_gemm_t<false, true>(a, s);
-        else launch_gemm_t<false, false>(a, s);
-    }
+    with_bool(a.nseeds > 1, [&](auto pk) {
+        with_bool(a.t32 != 0, [&](auto t32) { launch_gemm_t<decltype(pk)::value, decltype(t32)::value>(a, s); });
+    });
 }
 
 // ==================================================================== k_rng
@@ -5291,37 +5248,25 @@ __global__ __launch_bounds__(256) void k_actor_bwd_wide(ActorBwdArgs b) {
 
 void launch_actor_bwd(const ActorBwdArgs& a, hipStream_t s) {
     const int rows = a.B + a.ne;
-    const dim3 grid((rows + 3) / 4, 1, seeds_z(a.nseeds));
+    const dim3 grid((rows + 3) / 4, 1, seeds_z(a.nseeds)), block(256);
     const int hd = std::max(a.H0, a.use_expert ? a.Hm0 : 0);
-    if (a.H1 > 64 * MAXQ || hd > 64 * MAXQ) {   // either axis wide: slabs on each, independently
-#define SACX_ABW(Q, D)                                                                                    \
-    do {                                                                                                  \
-        if (a.nseeds > 1) hipLaunchKernelGGL((k_actor_bwd_wide<Q, D, true>), grid, dim3(256), 0, s, a);   \
-        else hipLaunchKernelGGL((k_actor_bwd_wide<Q, D, false>), grid, dim3(256), 0, s, a);               \
-    } while (0)
-        if (a.H1 > 64 * MAXQ && hd > 64 * MAXQ) SACX_ABW(2, 2);
-        else if (a.H1 > 64 * MAXQ) SACX_ABW(2, 1);
-        else SACX_ABW(1, 2);
-#undef SACX_ABW
-        return;
-    }
-    const bool q8 = a.H1 > 256, d8 = hd > 256;
-#define SACX_AB(Q, D, ...)                                                                                  \
-    do {                                                                                                    \
-        if (a.nseeds > 1) hipLaunchKernelGGL((k_actor_bwd<Q, D, true, ##__VA_ARGS__>), grid, dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((k_actor_bwd<Q, D, false, ##__VA_ARGS__>), grid, dim3(256), 0, s, a);            \
-    } while (0)
-    if (q8) {
-        if (d8) SACX_AB(8, 8);
-        else SACX_AB(8, 4);
-    } else if (a.Aout > 8 && a.Aout <= 24) {   // W3a staged in LDS (see actor_bwd_body)
-        if (d8) SACX_AB(4, 8, 24);
-        else SACX_AB(4, 4, 24);
-    } else {
-        if (d8) SACX_AB(4, 8);
-        else SACX_AB(4, 4);
-    }
-#undef SACX_AB
+    const bool hw = a.H1 > 64 * MAXQ, dw = hd > 64 * MAXQ;
+    with_bool(a.nseeds > 1, [&](auto pk) {
+        constexpr bool PK = decltype(pk)::value;
+        if (hw || dw) {   // either axis wide: slabs on each, independently
+            if (hw && dw) hipLaunchKernelGGL((k_actor_bwd_wide<2, 2, PK>), grid, block, 0, s, a);
+            else if (hw) hipLaunchKernelGGL((k_actor_bwd_wide<2, 1, PK>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_actor_bwd_wide<1, 2, PK>), grid, block, 0, s, a);
+            return;
+        }
+        with_bool(hd > 256, [&](auto d8) {
+            constexpr int D = decltype(d8)::value ? 8 : 4;
+            if (a.H1 > 256) hipLaunchKernelGGL((k_actor_bwd<8, D, PK>), grid, block, 0, s, a);
+            else if (a.Aout > 8 && a.Aout <= 24)   // W3a staged in LDS (see actor_bwd_body)
+                hipLaunchKernelGGL((k_actor_bwd<4, D, PK, 24>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_actor_bwd<4, D, PK>), grid, block, 0, s, a);
+        });
+    });
 }
 
 // ==================================================================== k_append

@@ -989,10 +989,10 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
             p.vec = (a4 ? 1 : 0) | (b4 ? 2 : 0);
         }
     }
-    // forward launches with world-model head rows (mse epilogues) take their own variant (rowk 8),
+    // forward launches with world-model head rows (mse epilogues) take their own variant,
     // so the others do not hold the mse operands in registers
     for (auto& p : ps)
-        if (mode == GM_FWD && p.mse) L.gemm.rowk = 8;
+        if (mode == GM_FWD && p.mse) L.gemm.rowk = GR_MSE_HEAD;
     if (record_probs) h->probs.insert(h->probs.end(), ps.begin(), ps.end());
     L.gemm.dwl = dwl ? (h->dwl_nh == 1 ? 2 : 1) : 0;    // 2: 32x16 tiles, 1: 32x32
     L.gemm.mode = mode;
@@ -1009,26 +1009,38 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
     plan.push_back(L);
 }
 
-// Appends the problems of GEMM launch `b` to launch `a` (same mode; tile ranges follow a's).
+// Gives the GEMM launch `L` of a plan its variant.  A mode or tile shape that has no kernel for it is a
+// bug of the builder (seeds are packed later, by pack_seeds: launch_gemm checks the whole combination)
+void set_rows(Launch& L, GemmRows rows) {
+    if (L.kind != Launch::GEMM || !gemm_variant_ok(L.gemm.mode, rows, L.gemm.t32 != 0, false, L.gemm.dwl)) {
+        fprintf(stderr, "sacx: no GEMM kernel for %s with rows %d (mode %d, t32 %d, dwl %d)\n", L.name.c_str(), (int)rows,
+                L.gemm.mode, L.gemm.t32, L.gemm.dwl);
+        abort();
+    }
+    L.gemm.rowk = rows;
+}
+
 // Replaces the plan's last two launches -- the layers 0 and 1 of the same nets, as add_gemm built
 // them -- by one k_fwd2 launch (GM_FWD2) when the pair qualifies: fp32, one seed, 16x16 tiles, plain
-// forward problems (layer 1 optionally with the actor head's partial dots, rowk 5), at most 4 nets,
-// K0 <= 32, H0 a multiple of 64 up to 256, layer 1 reading exactly layer 0's output.  Returns
+// forward problems (layer 1 optionally with the actor head's partial dots, GR_HEAD_PART), at most 4 nets,
+// K0 <= 32, H0 a multiple of 64 up to 256, layer 1 reading exactly layer 0's output.  wide0: a plain
+// layer 0 is the world-model fit's, on pre-gathered rows (GR_PREGATHERED: up to 512 wide).  Returns
 // whether it fused.
-bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& name) {
+bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& name, bool wide0 = false) {
     if (plan.size() < 2 || h->wide) return false;     // (k_fwd2 holds layer 0's rows in LDS: <= 512 wide)
     Launch& L0 = plan[plan.size() - 2];
     Launch& L1 = plan[plan.size() - 1];
     const GemmArgs &a0 = L0.gemm, &a1 = L1.gemm;
     if (L0.kind != Launch::GEMM || L1.kind != Launch::GEMM || a0.mode != GM_FWD || a1.mode != GM_FWD) return false;
     if (a0.t32 || a1.t32 || a0.dwl || a1.dwl || a0.bf16 || a0.nseeds > 1 || (h->seeds > 1 && h->learners == 0)) return false;
-    // layer 0 may carry the actor head (rowk 3: target tile prologues from the head's partial dots,
+    // layer 0 may carry the actor head (target tile prologues from the head's partial dots,
     // which keep the prologue free of barriers, and head rows as extra workgroups)
-    const bool head = a0.rowk == 3;
-    // or layer 0 gathers its rows from the replay ring (rowk 6: the world-model fit's model.fwd0), or
-    // reads them pre-gathered (rowk 9): the fit's layer 0, up to 512 wide
-    const bool gather = a0.rowk == 6 || a0.rowk == 9;
-    if ((a0.rowk != 0 && !head && !gather) || (a1.rowk != 0 && a1.rowk != 5) || ((head || gather) && a1.rowk != 0) ||
+    const bool head = a0.rowk == GR_ACTOR_HEAD;
+    // or layer 0 gathers its rows from the replay ring (the world-model fit's model.fwd0), or
+    // reads them pre-gathered: the fit's layer 0, up to 512 wide
+    const bool gather = a0.rowk == GR_GATHER || (wide0 && a0.rowk == GR_NONE);
+    if ((a0.rowk != GR_NONE && !head && !gather) || (a1.rowk != GR_NONE && a1.rowk != GR_HEAD_PART) ||
+        ((head || gather) && a1.rowk != GR_NONE) ||
         a0.has_final || a1.has_final || a0.nprob != a1.nprob || a0.nprob > 4)
         return false;
     if (head && (a0.head.part == nullptr || a0.head.H1 > 256 || a0.head.A > 16)) return false;
@@ -1058,8 +1070,12 @@ bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& nam
     g.mode = GM_FWD2;
     g.vec = vec ? 1 : 0;
     g.total_tiles = tiles;
-    g.rowk = head ? 3 : gather ? a0.rowk : a1.rowk;
-    if (a0.rowk == 6) g.mg = a0.mg;
+    g.rowk = head ? GR_PAIR_HEAD : a0.rowk == GR_GATHER ? GR_GATHER : gather ? GR_PREGATHERED : a1.rowk;
+    if (!gemm_variant_ok(GM_FWD2, g.rowk, false, false, 0)) {
+        fprintf(stderr, "sacx: no k_fwd2 kernel for %s with rows %d\n", name.c_str(), g.rowk);
+        abort();
+    }
+    if (a0.rowk == GR_GATHER) g.mg = a0.mg;
     if (head) {
         g.head = a0.head;
         g.hfin = a0.hfin;
@@ -1079,6 +1095,7 @@ bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& nam
     return true;
 }
 
+// Appends the problems of GEMM launch `b` to launch `a` (same mode; tile ranges follow a's).
 bool merge_gemm(GemmArgs& a, const GemmArgs& b) {
     if (a.mode == GM_FWD2 || b.mode == GM_FWD2) {
         // two k_fwd2 launches: layer-0 problems, then layer-1 problems, each launch's in order
@@ -1094,7 +1111,7 @@ bool merge_gemm(GemmArgs& a, const GemmArgs& b) {
         for (int i = 0; i < na + nb; ++i) { a.probs[i] = l0[i]; a.probs[na + nb + i] = l1[i]; }
         a.nprob = 2 * (na + nb);
         a.total_tiles += b.total_tiles;
-        if (b.rowk == 5) a.rowk = 5;           // head partials: per problem (ppart null or not)
+        if (b.rowk == GR_HEAD_PART) a.rowk = GR_HEAD_PART;   // head partials: per problem (ppart null or not)
         return true;
     }
     if (a.mode != b.mode || a.t32 != b.t32 || a.dwl != b.dwl || a.nprob + b.nprob > GEMM_MAXP) return false;
@@ -1106,9 +1123,9 @@ bool merge_gemm(GemmArgs& a, const GemmArgs& b) {
     a.nprob += b.nprob;
     a.total_tiles += b.total_tiles;
     a.vec = a.vec || b.vec;
-    if (b.rowk == 8) {             // world-model head rows: the forward variant with mse operands
-        if (a.rowk != 0 && a.rowk != 8) return false;
-        a.rowk = 8;
+    if (b.rowk == GR_MSE_HEAD) {   // world-model head rows: the forward variant with mse operands
+        if (a.rowk != GR_NONE && a.rowk != GR_MSE_HEAD) return false;
+        a.rowk = GR_MSE_HEAD;
     }
     return true;
 }
@@ -1318,7 +1335,7 @@ void xbf_wire(sacx_handle* h, std::vector<Launch>& plan, int slot) {
             uint16_t* img = h->ptr<uint16_t>("xbf.ws.Hq1") + (size_t)(d / ((int64_t)B * Hc0)) * Hc0 * ld;
             for (size_t q = 0; q < i && p.abf == nullptr; ++q) {
                 Launch& F = plan[q];
-                if (F.kind != Launch::GEMM || F.gemm.mode != GM_FWD || !F.gemm.t32 || !F.gemm.bf16 || F.gemm.rowk != 0) continue;
+                if (F.kind != Launch::GEMM || F.gemm.mode != GM_FWD || !F.gemm.t32 || !F.gemm.bf16 || F.gemm.rowk != GR_NONE) continue;
                 for (int c = 0; c < F.gemm.nprob; ++c) {
                     GemmProb& f = F.gemm.probs[c];
                     if (f.C == p.A && f.M == B && f.N == Hc0 && f.ldc == Hc0 && f.mse == 0 && f.ppart == nullptr) {
@@ -1389,7 +1406,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         L.bytes = 4.0 * (r1 - r0) * H0 * 3;
         plan.push_back(L);
     };
-    // actor.fwd1 writes the head's Ha2 . W3 as per-column-tile partials (rowk 5), so the head
+    // actor.fwd1 writes the head's Ha2 . W3 as per-column-tile partials (GR_HEAD_PART), so the head
     // rows and the target-tile prologues sum 16 values per output instead of re-reading Ha2
     // rows.  SACX_HEAD_PART=0 keeps the row dots (A/B measurement).
     const char* hpe = std::getenv("SACX_HEAD_PART");
@@ -1406,7 +1423,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         }
         return p;
     };
-    auto mark_part = [&]() { if (head_part) plan.back().gemm.rowk = 5; };
+    auto mark_part = [&]() { if (head_part) set_rows(plan.back(), GR_HEAD_PART); };
     if (h->ln) {
         add_gemm(h, plan, "actor.fwd0", {prob_fwd(Xa, ldS, h->Ra, S, W("actor.l0"), H0, Ha1, ACT_NONE)}, record_probs);
         ln_fwd("actor.ln", 0, h->Ra);
@@ -1506,7 +1523,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         }
         add_gemm(h, plan, "q.fwd0+actor.head", p0, record_probs);
         Launch& L = plan.back();
-        L.gemm.rowk = 3;
+        set_rows(L, GR_ACTOR_HEAD);
         L.gemm.head = head_fused;
         L.gemm.head_block0 = eo ? (2 * B) / 4 : ((h->Ra + 3) & ~3) / 4;
         L.gemm.row_blocks = eo ? (h->Ra + 3) / 4 - (2 * B) / 4 : 0;   // + the alpha rows (merged_body)
@@ -1566,7 +1583,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         }
         add_gemm(h, plan, "q.head+critic.bwd1", pb, record_probs);
         Launch& L = plan.back();
-        L.gemm.rowk = 1;
+        set_rows(L, GR_QHEAD);
         L.gemm.row_blocks = (B + 3) / 4;
         L.gemm.qh = q;
         L.grid += L.gemm.row_blocks;
@@ -1593,7 +1610,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             a.cache_row0 = B;
             a.cache_row1 = h->Ra;
             L.name += "+actor.head";
-            L.gemm.rowk = 3;
+            set_rows(L, GR_POLICY_HEAD);
             L.gemm.head = a;
             L.gemm.head_block0 = B / 4;
             L.gemm.row_blocks = (2 * B + 3) / 4 - B / 4;
@@ -1696,7 +1713,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         add_gemm(h, plan, "pi.q.head+pi.q.bwd1", pb, record_probs);
         {
             Launch& L = plan.back();
-            L.gemm.rowk = 2;
+            set_rows(L, GR_PIQHEAD);
             L.gemm.row_blocks = (B + 3) / 4;
             L.gemm.qh = q;
             L.grid += L.gemm.row_blocks;
@@ -1723,7 +1740,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
                 }
             }
             add_gemm(h, plan, "model.bwd1", pd, record_probs);
-            if (fold_hbw) plan.back().gemm.rowk = 2;   // DX with the partial epilogue (no q-head rows)
+            if (fold_hbw) set_rows(plan.back(), GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
         }
     }
     // ---- actor backward
@@ -1738,7 +1755,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         p.hbw = 1;
         add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
         Launch& L = plan.back();
-        L.gemm.rowk = 4;
+        set_rows(L, GR_HEAD_BWD);
         HeadBwdArgs& b = L.gemm.hbw;
         b.B = B; b.A = A; b.Aout = Aout; b.per_state_std = h->cfg.per_state_std; b.tq = tq;
         b.lim = h->cfg.act_limit; b.part = W("ws.apart"); b.gpol = W("ws.gp"); b.a_den = W("norm.a_den");
@@ -2344,12 +2361,12 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     const int tqh = (H1 + 15) / 16;
     const bool head_part = fold && Aout <= 8 && H1 <= 256 && H1 % 64 == 0 && h->tile32_plan == 0;
     actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", record_probs);
-    if (head_part) {                         // the head's Ha2 . W3 as per-column-tile partials of the last layer (rowk 5)
+    if (head_part) {                         // the head's Ha2 . W3 as per-column-tile partials of the last layer (GR_HEAD_PART)
         GemmArgs& g = plan.back().gemm;      // (two layers: the norm's launch is behind layer 0's)
         GemmProb& p = g.probs[0];
         p.pw = W(L_("actor", Da)); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;
         p.ppart = W("ws.hpart");
-        g.rowk = 5;
+        set_rows(plan.back(), GR_HEAD_PART);
     }
     if (fold && !h->ln && h->fwd2) fuse_fwd2(h, plan, "actor.fwd01");
     {   // ---- actor head: sample(s_e) into the models' input rows (their normaliser for the action columns)
@@ -2380,13 +2397,8 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
         add_gemm(h, plan, "model.fwd" + std::to_string(i), ps, record_probs);
     }
-    if (fold && h->fwd2 && S + A <= 32) {    // the pair as one k_fwd2 launch (rowk 9: layer 0 up to 512 wide)
-        Launch& F0 = plan[plan.size() - 2];
-        if (F0.gemm.rowk == 0 && !F0.gemm.t32) {
-            F0.gemm.rowk = 9;
-            if (!fuse_fwd2(h, plan, "model.fwd01")) plan[plan.size() - 2].gemm.rowk = 0;
-        }
-    }
+    // the pair as one k_fwd2 launch (GR_PREGATHERED: layer 0 up to 512 wide)
+    if (fold && h->fwd2 && S + A <= 32) fuse_fwd2(h, plan, "model.fwd01", true);
     const int mtn = (S + 15) / 16;
     // ---- the models' head + the MSE (BC.py:340-352), weight 1
     add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT | MSE_BC, se_raw, spe_raw), record_probs);
@@ -2414,8 +2426,8 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         }
         add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
         Launch& L = plan.back();
-        if (i == 1 && fold_hbw) L.gemm.rowk = 2;       // DX with the partial epilogue (no q-head rows)
-        if (fold && i == Dm && L.gemm.rowk == 0) {     // + the finalisation: one more workgroup
+        if (i == 1 && fold_hbw) set_rows(L, GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
+        if (fold && i == Dm && L.gemm.rowk == GR_NONE) {   // + the finalisation: one more workgroup
             L.name += "+bc.final";
             L.gemm.has_mfinal = 2;
             L.gemm.fin = fin;
@@ -2430,7 +2442,7 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         p.hbw = 1;
         add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
         Launch& L = plan.back();
-        L.gemm.rowk = 4;
+        set_rows(L, GR_HEAD_BWD);
         HeadBwdArgs& b = L.gemm.hbw;
         b.B = 0; b.A = A; b.Aout = Aout; b.per_state_std = h->cfg.per_state_std; b.tq = 0;
         b.lim = h->cfg.act_limit; b.part = nullptr; b.gpol = nullptr; b.a_den = W("norm.a_den");
@@ -2504,7 +2516,7 @@ void build_model_plan(sacx_handle* h) {
     const int nt = (Om + 15) / 16;    // fit-loss partials per row (16-column tiles of model.fwd2)
     const int ldO = (int)r4(O);       // D3 row stride
     const int ntm = (mb + 15) / 16;   // GaussianModel: logstd-gradient partials per column (row tiles)
-    // model.bwd2 generated on model.bwd1's operand loads (rowk 7) for narrow heads (S + 1 <= 32)
+    // model.bwd2 generated on model.bwd1's operand loads (GR_GEN_BWD2) for narrow heads (S + 1 <= 32)
     const bool bfold = fuse && h->mfuse >= 3 && O <= 32 && h->mtile != 2 && h->unaligned_b && !h->gm && !h->srn &&
                        Dm == 2 && !h->wide;
     auto W = [&](const std::string& n) { return h->f(n); };
@@ -2522,7 +2534,7 @@ void build_model_plan(sacx_handle* h) {
     // The minibatch rows: pre-gathered (SACX_MPRE, default) -- one k_mgather per block of <= MFIT_PRE steps
     // writes step j's normalised rows / targets into staging slot j before the block's steps, whose
     // launches read slot j (enqueue_fit_step moves their slot-0 pointers); or gathered per step, on
-    // model.fwd0's operand loads (rowk 6: 16x16 tiles, whose rows are whole records; the reward nets'
+    // model.fwd0's operand loads (GR_GATHER: 16x16 tiles, whose rows are whole records; the reward nets'
     // layer 0 reads the gathered X, so --separate_reward_nn keeps the gather launch) or by its own launch
     const bool pre = h->mpre != 0;
     float* Xin = pre ? W("mfit.Xs") : Xf;     // what the steps read: slot 0 of the staging, or X / T
@@ -2542,7 +2554,7 @@ void build_model_plan(sacx_handle* h) {
         h->mpres[h->sel] = L;
     }
     const bool gfold = !pre && fuse && h->mfuse >= 2 && h->mtile != 2 && h->stride % 4 == 0 && ldQ % 4 == 0 && !h->srn &&
-                       !h->wide;              // (rowk 6 / 9 and k_fwd2: layer 0 up to 512 wide)
+                       !h->wide;              // (GR_GATHER / GR_PREGATHERED and k_fwd2: layer 0 up to 512 wide)
     if (!gfold && !pre) {
         Launch L{};
         L.kind = Launch::MGATHER;
@@ -2661,8 +2673,7 @@ void build_model_plan(sacx_handle* h) {
             add_gemm(h, plan, name, f[0], false);    // (<= SACX_MAX_MODELS problems: one launch)
             if (gfold) {
                 Launch& F = plan.back();
-                if (F.gemm.t32 || F.gemm.dwl) { fprintf(stderr, "sacx: model.fwd0 gather needs 16x16 tiles\n"); abort(); }
-                F.gemm.rowk = 6;
+                set_rows(F, GR_GATHER);         // (16x16 tiles: a row is a whole record)
                 F.gemm.mg = mg;
                 F.name = "model.gather+fwd0";
                 F.bytes += 4.0 * nm * mb * (2.0 * S + A + 1 + O);
@@ -2679,14 +2690,8 @@ void build_model_plan(sacx_handle* h) {
         h->tile32 = t32_fit;
         // the gathered layer 0 and layer 1 as ONE k_fwd2 launch (SACX_MFWD2, default; K0 = S + A <= 32)
         if (i == 1 && gfold && h->mfwd2) fuse_fwd2(h, plan, "model.gather+fwd01");
-        // or, pre-gathered, layer 0 (rowk 9: H0 <= 512, plain A) and layer 1 the same way
-        if (i == 1 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32 && !h->wide) {
-            Launch& F0 = plan[plan.size() - 2];
-            if (F0.kind == Launch::GEMM && F0.gemm.rowk == 0 && !F0.gemm.t32) {
-                F0.gemm.rowk = 9;
-                if (!fuse_fwd2(h, plan, "model.fwd01")) plan[plan.size() - 2].gemm.rowk = 0;
-            }
-        }
+        // or, pre-gathered, layer 0 (GR_PREGATHERED: H0 <= 512, plain A) and layer 1 the same way
+        if (i == 1 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32 && !h->wide) fuse_fwd2(h, plan, "model.fwd01", true);
         if (i == Lf && fuse) plan.back().name = "model.fwd" + std::to_string(i) + "+loss";
     }
     if (!fuse) {
@@ -2720,9 +2725,8 @@ void build_model_plan(sacx_handle* h) {
         if (t == Lf - 1 && bfold) {      // model.bwd2 folded: model.bwd1 generates its A operand
             add_gemm(h, plan, name, b[t], false);
             Launch& B1 = plan.back();
-            if (B1.gemm.t32 || B1.gemm.dwl) { fprintf(stderr, "sacx: model.bwd1 generation needs 16x16 tiles\n"); abort(); }
             B1.name = "model.bwd2+bwd1+final";
-            B1.gemm.rowk = 7;
+            set_rows(B1, GR_GEN_BWD2);      // (16x16 tiles)
             B1.gemm.has_mfinal = 1;
             B1.gemm.mfin = mf;
             for (const GemmProb& q : b[0]) { B1.flops += gemm_flops(q); B1.bytes += gemm_bytes(q); }
@@ -2946,8 +2950,9 @@ bool merged_body(sacx_handle* h, int slot, int prev_slot, std::vector<Launch>& o
                 C.grid += pln->grid;
                 C.name += "+alpha";
                 ln_done = true;
-            } else if (!head_done && ph && (C.kind == Launch::AHEAD || (C.kind == Launch::GEMM && C.gemm.rowk == 3))) {
-                // the head rows: a standalone actor.head, or the rows folded into q.fwd0
+            } else if (!head_done && ph && (C.kind == Launch::AHEAD || (C.kind == Launch::GEMM && C.gemm.rowk == GR_ACTOR_HEAD))) {
+                // the head rows: a standalone actor.head, or the rows folded into q.fwd0 (as a k_fwd2 pair:
+                // GR_PAIR_HEAD, the same value)
                 HeadArgs& a = C.kind == Launch::AHEAD ? C.head : C.gemm.head;
                 const HeadSeg& sg = ph->head.seg[0];
                 if (a.nseg >= 4) return false;
@@ -2993,7 +2998,7 @@ bool merged_body(sacx_handle* h, int slot, int prev_slot, std::vector<Launch>& o
                     }
                     final_done = true;
                 }
-            } else if (afin_next && C.kind == Launch::GEMM && C.gemm.mode == GM_DX && C.gemm.rowk == 1) {
+            } else if (afin_next && C.kind == Launch::GEMM && C.gemm.mode == GM_DX && C.gemm.rowk == GR_QHEAD) {
                 // q.head+critic.bwd1: every target row block finishes the previous update's alpha step
                 C.gemm.fin = pf->fin;
                 C.gemm.fin.pre = h->ptr<AfinPre>("ws.afin");
@@ -3142,8 +3147,12 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
             Launch C = L;
             // (a k_fwd2 launch finalises alpha in its last alpha block, not in a workgroup of its own)
             const int fin_wg = C.gemm.has_final && C.gemm.mode != GM_FWD2 ? 1 : 0;
+            // a k_gemm launch's slots: its workgroups -- but the has_mfinal workgroup has none, and k_fwd2
+            // numbers its 2-D grid's tiles and rows itself (f2_slot)
             const int nwg1 = L.kind == Launch::GEMM
-                                 ? C.gemm.total_tiles + fin_wg + (C.gemm.rowk ? C.gemm.row_blocks : 0)
+                                 ? (C.gemm.mode != GM_FWD2 && !C.gemm.has_mfinal
+                                        ? gemm_workgroups(C.gemm)
+                                        : C.gemm.total_tiles + fin_wg + (C.gemm.rowk ? C.gemm.row_blocks : 0))
                                  : (L.kind == Launch::AHEAD ? (C.head.total_rows + 3) / 4 : C.grid);
             const int nwg = nwg1 * h->seeds;   // slots of every seed (seed-major)
             if (kt->used + 2 * nwg <= kt->cap) {
@@ -3155,11 +3164,12 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
                 kt->names.push_back(C.name);
                 kt->is_gemm.push_back(L.kind == Launch::GEMM);
                 if (L.kind != Launch::GEMM) kt->rowspan.push_back({0, 0});
-                else if (C.gemm.rowk == 3) kt->rowspan.push_back({fin_wg, fin_wg + C.gemm.row_blocks});
+                else if (C.gemm.rowk == GR_ACTOR_HEAD)     // (in any mode: head rows run ahead of the tiles)
+                    kt->rowspan.push_back({fin_wg, fin_wg + C.gemm.row_blocks});
                 else kt->rowspan.push_back({C.gemm.total_tiles + fin_wg, nwg1});
                 std::vector<int> cb;
                 if (L.kind == Launch::GEMM && C.gemm.mode == GM_FWD2) {
-                    const int nn = C.gemm.nprob / 2, r0 = C.gemm.rowk == 3 ? C.gemm.row_blocks : 0;
+                    const int nn = C.gemm.nprob / 2, r0 = C.gemm.rowk == GR_PAIR_HEAD ? C.gemm.row_blocks : 0;
                     for (int i = 0; i < nn; ++i) cb.push_back(r0 + C.gemm.probs[nn + i].tile_begin);
                 }
                 kt->cls.push_back(cb);
@@ -3262,7 +3272,7 @@ int chain_body(sacx_handle* h, int G, bool with_rng, int skip_kind, KTimeMap* kt
                     }
                     continue;
                 }
-                if (afin_skipped && L.kind == Launch::GEMM && L.gemm.rowk == 1 && L.gemm.fin.pre != nullptr) {
+                if (afin_skipped && L.kind == Launch::GEMM && L.gemm.rowk == GR_QHEAD && L.gemm.fin.pre != nullptr) {
                     Launch C = L;                        // its q.head half: alpha is already final in place
                     C.gemm.fin.pre = nullptr;
                     afin_skipped = false;
@@ -3950,7 +3960,7 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     for (int sl = 0; sl < h->nslot; ++sl)
         for (const Launch& L : h->plan[sl]) {
             const QHeadArgs* q = L.kind == Launch::QHEAD ? &L.qh
-                                 : (L.kind == Launch::GEMM && (L.gemm.rowk == 1 || L.gemm.rowk == 2)) ? &L.gemm.qh : nullptr;
+                                 : (L.kind == Launch::GEMM && gemm_rows_qhead(L.gemm.mode, L.gemm.rowk)) ? &L.gemm.qh : nullptr;
             if (q && q->ne > 0 && (q->Hm1 > 512 || q->H1 > 512))
                 return fail(h, "internal: q.head with expert rows beside a hidden layer wider than 512");
         }

@@ -63,7 +63,98 @@ enum Epi { EPI_FWD = 0, EPI_DACT = 1, EPI_ADAM = 2, EPI_STORE = 3 };
 // probs[n, 2n) layer 1 of the same nets (layer 1 reads layer 0's output); the layer-1 problems'
 // tile_begin / tiles_n count (16-row block, 64-column group) workgroups
 enum GemmMode { GM_FWD = 0, GM_DX = 1, GM_DW = 2, GM_FWD2 = 3 };
-// waves per k_fwd2 workgroup of the pair that carries actor-head rows (rowk 3): two workgroups per CU,
+
+// What a launch carries besides its plain tiles: GemmArgs::rowk, and the kernels' ROWK template
+// argument (an int, so the values are part of the kernel names).  Value 3 has one name per mode.
+//
+//  v  name            modes    what it adds, the GemmArgs members it reads, restrictions
+//  0  GR_NONE         all      nothing.  FWD / DX / DW: + one workgroup after the tiles when
+//                              has_mfinal (mfin; 2: the BC finalisation on fin).  FWD2: the plain pair
+//  1  GR_QHEAD        DX       row_blocks workgroups after the tiles run k_qhead<0> on qh (q.head: target,
+//                              loss rows, g, D2; with fin.pre set they also finish the previous
+//                              update's alpha step from the snapshot).  NQ = 8 when qh.H1 > 256
+//  2  GR_PIQHEAD      DX       row_blocks workgroups run k_qhead<1> on qh (pi.q.head; row_blocks may be 0),
+//                              and an epilogue on problems with pw set: per-tile partial dots of the
+//                              output rows into ppart (the action gradient's partials).  NQ as above
+//  3  GR_ACTOR_HEAD   FWD      the actor head (head; hfin for its alpha rows): seg[0] in the prologue of
+//                              the headp problems' tiles, the other rows as row_blocks workgroups ahead
+//                              of the tiles, from row 4 head_block0.  Its own kernel, k_gemm_head;
+//                              16x16 tiles only; NQ = 8 when head.H1 > 256
+//  3  GR_POLICY_HEAD  DW       the policy rows of the actor head (head, head_block0) as row_blocks
+//                              workgroups ahead of the dW + Adam tiles.  Never k_dwl; NQ as above
+//  3  GR_PAIR_HEAD    FWD2     the target / critic pair with GR_ACTOR_HEAD's prologue on headp pairs
+//                              and a plane of row_blocks head-row workgroups (head, hfin, head_block0;
+//                              has_final: the last alpha block finalises on fin, 2: snapshots it)
+//  4  GR_HEAD_BWD     DX       prologue: the actor head's backward on hbw; the A operand is generated
+//                              from it and wgen by a small MFMA, column tile 0 stores it.  One problem
+//                              (hbw set), 16x16 tiles only
+//  5  GR_HEAD_PART    FWD      epilogue on problems with pw set: the actor head's Ha2 . W3 as per-tile
+//                     FWD2     partial dots into ppart.  FWD2: layer 1 of the plain pair
+//  6  GR_GATHER       FWD      the fit's layer 0: the A rows are replay records gathered through mg and
+//                     FWD2     normalised on load; column tile 0 stores them and the targets.  One
+//                              seed, 16x16 tiles (FWD2: layer 0 up to 512 wide)
+//  7  GR_GEN_BWD2     DX       the fit's model.bwd1 with model.bwd2 generated on its operand loads from
+//                              the problems' gd / wgen, column tile 0 storing it to gst; + GR_NONE's
+//                              has_mfinal workgroup.  One seed, 16x16 tiles
+//  8  GR_MSE_HEAD     FWD      epilogue on problems with mse set: the world-model head's loss and output
+//                              gradient (se_raw, spe_raw, dmean, dden, part; ctl for epsilon)
+//  9  GR_PREGATHERED  FWD2     GR_GATHER's wide pair on rows a pre-gather launch wrote (plain A)
+//
+// gemm_variant_ok() below says which (mode, value, tiles, packing) the launchers hold a kernel for.
+enum GemmRows : int32_t {
+    GR_NONE = 0,
+    GR_QHEAD = 1,
+    GR_PIQHEAD = 2,
+    GR_ACTOR_HEAD = 3, GR_POLICY_HEAD = 3, GR_PAIR_HEAD = 3,
+    GR_HEAD_BWD = 4,
+    GR_HEAD_PART = 5,
+    GR_GATHER = 6,
+    GR_GEN_BWD2 = 7,
+    GR_MSE_HEAD = 8,
+    GR_PREGATHERED = 9,
+    GR_COUNT = 10
+};
+// Q-head rows after the tiles, and which k_qhead they run
+__host__ __device__ constexpr bool gemm_rows_qhead(int mode, int rows) {
+    return mode == GM_DX && (rows == GR_QHEAD || rows == GR_PIQHEAD);
+}
+__host__ __device__ constexpr int gemm_qhead_mode(int rows) { return rows == GR_PIQHEAD ? 1 : 0; }
+// actor-head rows ahead of the tiles (k_gemm; k_fwd2's GR_PAIR_HEAD holds them in a plane of its grid)
+__host__ __device__ constexpr bool gemm_rows_head(int mode, int rows) {
+    return (mode == GM_FWD && rows == GR_ACTOR_HEAD) || (mode == GM_DW && rows == GR_POLICY_HEAD);
+}
+// the partial-dot epilogue (pw / ppart)
+__host__ __device__ constexpr bool gemm_rows_part(int mode, int rows) {
+    return (mode == GM_DX && rows == GR_PIQHEAD) || (mode == GM_FWD && rows == GR_HEAD_PART);
+}
+// the variants whose workgroup after the tiles is the has_mfinal finalisation
+__host__ __device__ constexpr bool gemm_rows_mfinal(int rows) { return rows == GR_NONE || rows == GR_GEN_BWD2; }
+// variants of the world-model fit alone: one seed, 16x16 tiles
+__host__ __device__ constexpr bool gemm_rows_fit_only(int rows) {
+    return rows == GR_GATHER || rows == GR_GEN_BWD2 || rows == GR_PREGATHERED;
+}
+// Exactly the launches launch_gemm holds a kernel for (dwl: GemmArgs::dwl, 1 / 2 = k_dwl's tile shapes;
+// packed: nseeds > 1).  Anything else is a plan-building error: the host aborts on it.
+__host__ __device__ constexpr bool gemm_variant_ok(int mode, int rows, bool t32, bool packed, int dwl) {
+    if (dwl) return (dwl == 1 || dwl == 2) && mode == GM_DW && rows == GR_NONE && !t32;
+    if (gemm_rows_fit_only(rows) && (t32 || packed)) return false;
+    switch (mode) {
+    case GM_FWD:
+        return rows == GR_NONE || rows == GR_HEAD_PART || rows == GR_MSE_HEAD || rows == GR_GATHER ||
+               (rows == GR_ACTOR_HEAD && !t32);
+    case GM_DX:
+        return rows == GR_NONE || rows == GR_QHEAD || rows == GR_PIQHEAD || rows == GR_GEN_BWD2 ||
+               (rows == GR_HEAD_BWD && !t32);
+    case GM_DW:
+        return rows == GR_NONE || rows == GR_POLICY_HEAD;
+    case GM_FWD2:                      // k_fwd2: one seed, fp32, 16x16 MFMA tiles
+        return !t32 && !packed && (rows == GR_NONE || rows == GR_PAIR_HEAD || rows == GR_HEAD_PART ||
+                                   rows == GR_GATHER || rows == GR_PREGATHERED);
+    }
+    return false;
+}
+
+// waves per k_fwd2 workgroup of the pair that carries actor-head rows (GR_PAIR_HEAD): two workgroups per CU,
 // so the 256 tiles and the head rows run in one round; its head rows take NW / 4 blocks of 4 rows each
 #define SACX_FWD2_HEAD_NW 8
 
@@ -120,18 +211,15 @@ struct GemmProb {
     // GM_FWD / GM_DX: this problem's operands take float4 loads along k (host-checked strides and
     // alignment); the launch's VEC template only says whether any problem does
     int32_t vec;
-    // GM_DX in a q-head launch (rowk 2) / GM_FWD in an actor launch (rowk 5): per-row partial
-    // dots of the tile's output row with the rows of pw -- ppart[(m * pw_n + j) * tiles_n + tn] =
-    // sum over the tile's 16 columns n of C[m][n] * pw[j * pw_ld + n * pw_cs], j < pw_n <= 8.
-    // rowk 2: the policy rows' action gradient through the critic's layer-0 action rows (summed
-    // by the folded actor head backward; C may then be null).  rowk 5: the actor head
-    // mu / logstd rows = Ha2 . W3 (summed, + bias, by the head rows and prologues).
+    // GR_PIQHEAD / GR_HEAD_PART: per-row partial dots of the tile's output row with the rows of
+    // pw -- ppart[(m * pw_n + j) * tiles_n + tn] = sum over the tile's 16 columns n of
+    // C[m][n] * pw[j * pw_ld + n * pw_cs], j < pw_n <= 8 (GR_PIQHEAD: C may be null)
     const float* pw;
     float* ppart;
     int32_t pw_ld, pw_cs, pw_n;
-    // GM_DX with rowk 4: the folded actor head backward problem (GemmArgs::hbw)
+    // GR_HEAD_BWD: the folded actor head backward problem (GemmArgs::hbw)
     int32_t hbw;
-    // GM_DX with rowk 7 (model.bwd1 of the fit with model.bwd2 folded in): the A operand, the
+    // GR_GEN_BWD2 (model.bwd1 of the fit with model.bwd2 folded in): the A operand, the
     // layer-2 delta D2 = (D3 . W2^T) (.) act'(H2), is generated on load from A = H2 [M, K] and
     // gd = D3 [M, g_o] (row stride gd_ld) through wgen = W2_ext [K (+1), g_o] (row stride g_o),
     // with model.bwd2's exact MFMA sequence (16-wide output slabs t, j = 0 2 / 1 3 pairs, the
@@ -188,7 +276,7 @@ struct WbfArgs {
     int32_t nseeds;
 };
 
-// rowk 4 (GM_DX, actor.bwd1): the actor head backward (k_actor_bwd's policy-row work) runs as
+// GR_HEAD_BWD (GM_DX, actor.bwd1): the actor head backward (k_actor_bwd's policy-row work) runs as
 // the tile prologue.  Per row: ga = (g0 * sum ppart_q0 + g1 * sum ppart_q1) / a_den, the
 // tanh-Gaussian backward (A5) -> Da3[row][0, Aout) (and E), then the A operand
 // Da2[row][k] = (sum_o Da3[row][o] W3a[k][o]) * act'(Ha2[row][k]) is generated on load by a
@@ -305,7 +393,7 @@ struct HeadArgs {
     const float *ma_mean, *ma_den;
     float logstd_init;     // mode 2: GaussianActor.logstd_init (continuous_actors.py:39-44)
     int32_t output_norm;   // mode 2: --actor_output_norm (continuous_actors.py:68-72)
-    // nullable: the head's Ha2 . W3 as per-column-tile partials written by actor.fwd1 (rowk 5),
+    // nullable: the head's Ha2 . W3 as per-column-tile partials written by actor.fwd1 (GR_HEAD_PART),
     // part[(row * Aout + o) * tq + i], i < tq (<= 16, a multiple of 4); row = the H2 row
     const float* part;
     int32_t tq;
@@ -327,7 +415,7 @@ struct HeadArgs {
 };
 
 // world-model fit inputs: the step's minibatch rows gathered from the replay ring (k_mgather, or
-// on load by model.fwd0's tiles: GemmArgs rowk 6)
+// on load by model.fwd0's tiles: GR_GATHER)
 struct MGatherArgs {        // rows [0, 2*mb): model k = row / mb
     const float* replay; int64_t cap; int32_t stride;
     int32_t S, A, mb;
@@ -380,35 +468,41 @@ struct GemmArgs {
     // (alpha.final folded into a launch of the next update, see get_graph)
     int32_t has_final;
     FinalArgs fin;
-    // GM_DX: rowk = 1 / 2 appends row_blocks workgroups running k_qhead<0> / <1> on qh
-    // (horizontal fusion: the heads and the unscaled dX GEMM are independent)
+    // rowk: a GemmRows value (the table above says which of the members below each one reads);
+    // row_blocks: the workgroups of its row kernel (horizontal fusion: rows and tiles are independent)
     int32_t rowk, row_blocks;
     QHeadArgs qh;
-    // GM_FWD with rowk = 3: the actor head (GemmArgs::head) -- seg[0] in the prologue of the
-    // headp problems, the other rows as row_blocks extra workgroups (from row head_block0 * 4);
-    // hfin: the alpha-row partials (alpha_mode)
     HeadArgs head;
-    FinalArgs hfin;
+    FinalArgs hfin;        // the head's alpha-row partials (alpha_mode)
     int32_t head_block0;
-    HeadBwdArgs hbw;       // rowk 4 (GM_DX)
+    HeadBwdArgs hbw;
     uint64_t* ktime;       // measurement only: per-workgroup start / end ticks (nullable)
     // packed seeds (sacx_config.seeds): grid z = nseeds independent learners whose arena blocks
     // sit sstride bytes apart; every arena pointer is relocated by blockIdx.z * sstride
     int64_t sstride;
     int32_t nseeds;
-    // world-model fit (ROWK 0 launches): one extra workgroup after the tiles finalises the fit step
+    // world-model fit (gemm_rows_mfinal launches): one extra workgroup after the tiles finalises the fit step
     // (k_mfinal's work: loss statistics, t_model and mfit_seq advance)
     int32_t has_mfinal;
     // GM_DW: the optimiser step counter was already advanced in this step (the folded model
     // finalisation runs before model.adam): the Adam step is t + 1 - t_adv
     int32_t t_adv;
     MFinalArgs mfin;
-    // GM_FWD rowk 6 (model.fwd0 of the fit): problem p's A rows are replay records gathered by the
-    // step's indices (model p's minibatch) and normalised on load; column tile 0 stores them to
-    // the problem's A (X, read by model.adam) and each tile stores its 16 columns of the targets
+    // GR_GATHER (model.fwd0 of the fit): problem p's A rows are model p's minibatch; column tile 0
+    // stores them to the problem's A (X, read by model.adam) and each tile its 16 columns of the targets
     MGatherArgs mg;
 };
 static_assert(sizeof(GemmArgs) <= 4096 - 16, "GemmArgs travels as kernel arguments, behind a KHdr");
+
+// The workgroups (grid x) of a GM_FWD / GM_DX / GM_DW launch on k_gemm / k_gemm_head: the alpha
+// finalisation ahead of everything (has_final; dX launches and GR_POLICY_HEAD take none), the variant's
+// row kernel, the tiles, and has_mfinal's workgroup behind them (not beside actor-head rows)
+inline int gemm_workgroups(const GemmArgs& a) {
+    const int fin = a.has_final ? 1 : 0, mfin = a.has_mfinal ? 1 : 0;
+    if (gemm_rows_head(a.mode, a.rowk)) return a.total_tiles + (a.mode == GM_FWD ? fin : 0) + a.row_blocks;
+    if (a.mode == GM_DX) return a.total_tiles + (gemm_rows_qhead(a.mode, a.rowk) ? a.row_blocks : 0) + mfin;
+    return a.total_tiles + fin + mfin;
+}
 
 // The scalars that pick a k_gemm / k_dwl workgroup's role and problem (total_tiles, row_blocks,
 // the problems' first tiles, nprob, has_final, xcd_map), packed as 9 x 12-bit fields + 8 flag bits

@@ -147,6 +147,25 @@ def test_launch_header_round_trip(tmp_path):
     assert "0 mismatches" in out, out
 
 
+def test_gemm_variant_table(tmp_path):
+    """The k_gemm launch variants (sacx_internal.h GemmRows): the enumerators keep the values 0..9
+    that the kernel names carry; gemm_variant_ok accepts exactly the (mode, value, tile, packing,
+    k_dwl) combinations the launcher holds a kernel for, over the whole product; gemm_workgroups
+    equals the launcher's grid formulas on random launch geometries."""
+    import os
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not on PATH")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "gvar"
+    subprocess.check_call(["g++", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "sac-expert_amd", "csrc"),
+                           os.path.join(root, "tests", "gemm_variant_check.cpp"), "-o", str(exe)])
+    out = subprocess.check_output([str(exe)], text=True)
+    assert "480 combinations, 36000 grid draws, 0 mismatches" in out, out
+
+
 def test_mt_jump_windows(tmp_path):
     """The segmented sampler's jump-ahead (csrc/mt_jump.cpp: MT19937's characteristic polynomial
     by Berlekamp-Massey, x^(kL) mod phi): the 624-word windows k L + 1 .. k L + 624 rebuilt as
