@@ -33,6 +33,8 @@ in fp64 on the same forward formulas.
 Precision modes: ``np.float64`` (reference-quality arithmetic) and
 ``np.float32`` (op-by-op emulation of the TF fp32 graph: every elementwise op
 rounds to fp32, constants are cast the way TF casts python / numpy scalars).
+Operand modes (``GEMM_OPERANDS``): "exact", and "bf16" -- the operands of every GEMM the device's
+config C5 runs on bf16 MFMAs rounded to nearest even, the contract of DESIGN.md section 6.6.
 
 Parity status: the random streams are pinned bit-exactly against NumPy's own
 legacy ``RandomState`` (the reference's RNG; see oracle/mt19937.c and
@@ -316,6 +318,41 @@ MATMUL_ORDERS = ("default", "reversed", "split4")
 MATMUL_ORDER = "default"
 
 
+# Operands of the device's bf16 MFMA GEMMs (config C5).  "exact": no rounding
+# (every fp32-path test).  "bf16": each operand element of a GEMM the device runs on
+# v_mfma_f32_16x16x32_bf16 is RNE(v), v the value the fp32 path feeds the same MFMA; sums, epilogues
+# (the forward bias among them), the row kernels (the actor's and the critics' output layers, their dX,
+# the dX of a first layer), master weights and Adam keep the state's dtype, and nothing is rounded twice.
+GEMM_OPERANDS = "exact"
+# The fused two-hidden-layer update plan factors the critics' per-row loss gradient g out of their
+# layer-1 dX GEMM (Dq1 = g (.) M1): the GEMM's A operand is the unit delta
+# w3 (.) act'(H2), and g rides on the layer-0 dW GEMM's delta operand (M1 * g, rounded after the
+# product).  False: the generic per-layer plan, whose deltas are the loss-scaled ones throughout.
+BF16_UNIT_DELTAS = True
+
+
+def bf16_rne(x):
+    """x rounded to the nearest bfloat16 (ties to even) on its float32 bit pattern, inf and NaN kept,
+    returned in x's dtype."""
+    a = np.asarray(x)
+    f = np.ascontiguousarray(a, dtype=np.float32)
+    u = f.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000).astype(np.uint32).view(np.float32)
+    r = np.where(np.isnan(f), f, r)
+    return r.astype(a.dtype if a.dtype.kind == "f" else np.float32).reshape(a.shape)
+
+
+def _rb(x):
+    """A GEMM operand as the device's MFMA takes it."""
+    return bf16_rne(x) if GEMM_OPERANDS == "bf16" else x
+
+
+def _rb_dw(x):
+    """An operand of a dW GEMM (apart from _rb so that tests/test_oracle_bf16.py can show that its bars
+    see a dW GEMM left unrounded)."""
+    return _rb(x)
+
+
 def matmul(h, w):
     if h.dtype != np.float32 or MATMUL_ORDER == "default":
         return h @ w
@@ -328,13 +365,19 @@ def matmul(h, w):
     raise ValueError(MATMUL_ORDER)
 
 
-def mlp_forward(params, x, act):
+def mlp_forward(params, x, act, rows_head=False):
+    """``rows_head``: the output layer runs on a row kernel (the actor's and the critics' heads in the
+    update plans), not as a GEMM: its operands stay unrounded under GEMM_OPERANDS = "bf16".  The bias is
+    added in the GEMM's fp32 epilogue: never rounded."""
     hs = []
     h = x
     nl = len(params) // 2
     out = None
     for l in range(nl):
-        z = matmul(h, params[2 * l]) + params[2 * l + 1]
+        if rows_head and l == nl - 1:
+            z = matmul(h, params[2 * l]) + params[2 * l + 1]
+        else:
+            z = matmul(_rb(h), _rb(params[2 * l])) + params[2 * l + 1]
         if l < nl - 1:
             h = act_fwd(z, act[l] if isinstance(act, (list, tuple)) else act)
             hs.append(h)
@@ -343,7 +386,15 @@ def mlp_forward(params, x, act):
     return out, hs
 
 
-def mlp_backward(params, x, hs, dout, act, need_dx=False, need_dw=True):
+def mlp_backward(params, x, hs, dout, act, need_dx=False, need_dw=True, rows_head=False, row_scale=None,
+                 dx_gemm=False):
+    """Under GEMM_OPERANDS = "bf16": every dW is a GEMM (both operands rounded; the bias gradient is its
+    all-ones row times the rounded delta, so it sums rounded values), every dX between hidden layers too;
+    the output layer's dX is unrounded with ``rows_head`` (a row kernel), and so is the first layer's (the
+    action gradient: a row kernel or an fp32 epilogue) unless ``dx_gemm`` (the layers behind the actor's
+    layer norm: their first dX is the GEMM actor.bwd1).  ``row_scale`` [n]: ``dout`` is the unit delta and the true one is
+    row_scale[:, None] * dout -- the dX chain carries the unit delta, the dW operands the scaled one
+    (BF16_UNIT_DELTAS); the returned dx is the unit one."""
     nl = len(params) // 2
     grads = [None] * len(params)
     d = dout
@@ -351,12 +402,20 @@ def mlp_backward(params, x, hs, dout, act, need_dx=False, need_dw=True):
     for l in reversed(range(nl)):
         inp = x if l == 0 else hs[l - 1]
         if need_dw:
-            grads[2 * l] = inp.T @ d
-            grads[2 * l + 1] = d.sum(axis=0)
+            ds = d if row_scale is None else d * row_scale[:, None]
+            grads[2 * l] = _rb_dw(inp).T @ _rb_dw(ds)
+            grads[2 * l + 1] = _rb_dw(ds).sum(axis=0)
         if l > 0:
-            d = (d @ params[2 * l].T) * act_grad(hs[l - 1], act[l - 1] if isinstance(act, (list, tuple)) else act)
+            da = act_grad(hs[l - 1], act[l - 1] if isinstance(act, (list, tuple)) else act)
+            if rows_head and l == nl - 1:
+                d = (d @ params[2 * l].T) * da
+            else:
+                d = (_rb(d) @ _rb(params[2 * l]).T) * da
         elif need_dx:
-            dx = d @ params[0].T
+            if dx_gemm and not (rows_head and nl == 1):
+                dx = _rb(d) @ _rb(params[0]).T
+            else:
+                dx = d @ params[0].T
     return grads, dx
 
 
@@ -370,29 +429,31 @@ LN_EPS = 1e-3
 
 def actor_forward(params, x, cfg):
     if not cfg.layer_norm:
-        return mlp_forward(params, x, cfg.aacts)
+        return mlp_forward(params, x, cfg.aacts, rows_head=True)
     dt = x.dtype.type
-    z = x @ params[0] + params[1]
+    z = _rb(x) @ _rb(params[0]) + params[1]
     mu = z.mean(-1, keepdims=True)
     d = z - mu
     rstd = _F(dt, 1) / np.sqrt((d * d).mean(-1, keepdims=True) + _F(dt, LN_EPS))
     xh = d * rstd
     h1 = np.tanh(params[2] * xh + params[3])
-    out, hs = mlp_forward(params[4:], h1, cfg.aacts[1:])
+    out, hs = mlp_forward(params[4:], h1, cfg.aacts[1:], rows_head=True)
     return out, [h1] + hs + [xh, rstd]
 
 
 def actor_backward(params, x, hs, dout, cfg):
     """Gradients of the actor weight list (same order as params)."""
     if not cfg.layer_norm:
-        return mlp_backward(params, x, hs, dout, cfg.aacts)[0]
+        return mlp_backward(params, x, hs, dout, cfg.aacts, rows_head=True)[0]
     h1, rest, xh, rstd = hs[0], hs[1:-2], hs[-2], hs[-1]
-    g_rest, dh1 = mlp_backward(params[4:], h1, rest, dout, cfg.aacts[1:], need_dx=True)
+    g_rest, dh1 = mlp_backward(params[4:], h1, rest, dout, cfg.aacts[1:], need_dx=True, rows_head=True, dx_gemm=True)
     one = np.ones((), h1.dtype)
     dy = dh1 * (one - h1 * h1)
     gg = dy * params[2]
     dz = rstd * ((gg - gg.mean(-1, keepdims=True)) - xh * (gg * xh).mean(-1, keepdims=True))
-    return [x.T @ dz, dz.sum(axis=0), (dy * xh).sum(axis=0), dy.sum(axis=0)] + g_rest
+    # the layer-0 dW, and gamma / beta as the column sums of dY * xhat and dY: GEMM problems of actor.adam
+    return [_rb_dw(x).T @ _rb_dw(dz), _rb_dw(dz).sum(axis=0), _rb_dw(dy * xh).sum(axis=0),
+            _rb_dw(dy).sum(axis=0)] + g_rest
 
 
 # ---------------------------------------------------------------------------
@@ -528,21 +589,29 @@ def sac_update(st: SACState, cfg: Config, nrm: Normalizers, batch, noise_t, nois
     mu_t, ls_t = split_head(out_t, st.logstd, cfg)
     a_t, nlp_t, _ = head_evaluate(mu_t, ls_t, n1, lim, dt)
     xq_t = np.concatenate([sp_n, _norm(a_t, nrm.a_mean, nrm.a_den)], axis=1)
-    qt = [mlp_forward(net, xq_t, cfg.cacts)[0][:, 0] * nrm.ret_den for net in st.q_targ]
+    qt = [mlp_forward(net, xq_t, cfg.cacts, rows_head=True)[0][:, 0] * nrm.ret_den for net in st.q_targ]
     next_value = np.minimum(qt[0], qt[1]) + alpha * nlp_t
     y = r + F(cfg.gamma) * ((F(1) - d) * next_value)
     if keep is not None:
-        keep.update(sp_n=sp_n, actor_h_t=hs_t, mu_t=mu_t, a_t=a_t, nlp_t=nlp_t, qt=qt, y=y)
+        keep.update(sp_n=sp_n, actor_h_t=hs_t, mu_t=mu_t, ls_t=ls_t, a_t=a_t, nlp_t=nlp_t, qt=qt, y=y)
 
     # ---------------- critic (_update_critic, :232-259)
     s_n = _norm(s, nrm.s_mean, nrm.s_den)
     xq = np.concatenate([s_n, _norm(a, nrm.a_mean, nrm.a_den)], axis=1)
+    if keep is not None:
+        keep.update(s_n=s_n, xq=xq, noise=np.concatenate([n1.ravel(), n2.ravel()]))
+    # the fused plan's critic dX GEMMs take the unit delta, the per-row loss gradient apart (bf16 only:
+    # the exact modes keep their arithmetic bit for bit)
+    unit = GEMM_OPERANDS == "bf16" and BF16_UNIT_DELTAS
     for k in range(2):
-        q, hs = mlp_forward(st.q[k], xq, cfg.cacts)
+        q, hs = mlp_forward(st.q[k], xq, cfg.cacts, rows_head=True)
         e = q[:, 0] - y
         stats["q%d_loss" % (k + 1)] = float(np.mean(F(0.5) * e * e))
         dq = (e * F(1.0 / B))[:, None]
-        grads, _ = mlp_backward(st.q[k], xq, hs, dq, cfg.cacts)
+        if unit:
+            grads, _ = mlp_backward(st.q[k], xq, hs, np.ones_like(dq), cfg.cacts, rows_head=True, row_scale=dq[:, 0])
+        else:
+            grads, _ = mlp_backward(st.q[k], xq, hs, dq, cfg.cacts, rows_head=True)
         if keep is not None:
             keep["q%d_h" % k] = hs
             keep["q%d_out" % k] = q[:, 0]
@@ -554,7 +623,7 @@ def sac_update(st: SACState, cfg: Config, nrm: Normalizers, batch, noise_t, nois
     mu_p, ls_p = split_head(out_p, st.logstd, cfg)
     a_p, nlp_p, cache_p = head_evaluate(mu_p, ls_p, n2, lim, dt)
     xq_p = np.concatenate([s_n, _norm(a_p, nrm.a_mean, nrm.a_den)], axis=1)
-    fq = [mlp_forward(net, xq_p, cfg.cacts) for net in st.q]
+    fq = [mlp_forward(net, xq_p, cfg.cacts, rows_head=True) for net in st.q]
     q1p, q2p = fq[0][0][:, 0], fq[1][0][:, 0]
     minq = np.minimum(q1p, q2p)
     p_loss = np.mean(-alpha * nlp_p - minq)
@@ -565,8 +634,13 @@ def sac_update(st: SACState, cfg: Config, nrm: Normalizers, batch, noise_t, nois
     sel2 = np.where(q2p < q1p, F(1), np.where(q1p == q2p, F(0.5), F(0)))
     dxa = None
     for k, sel in enumerate((sel1, sel2)):
-        _, dx = mlp_backward(st.q[k], xq_p, fq[k][1], (gmin * sel)[:, None], cfg.cacts,
-                             need_dx=True, need_dw=False)
+        if unit:
+            _, dx = mlp_backward(st.q[k], xq_p, fq[k][1], np.ones((B, 1), dt), cfg.cacts,
+                                 need_dx=True, need_dw=False, rows_head=True)
+            dx = dx * (gmin * sel)[:, None]
+        else:
+            _, dx = mlp_backward(st.q[k], xq_p, fq[k][1], (gmin * sel)[:, None], cfg.cacts,
+                                 need_dx=True, need_dw=False, rows_head=True)
         part = dx[:, S:] / nrm.a_den
         dxa = part if dxa is None else dxa + part
     c = np.full(B, -w_sac * alpha * F(1.0 / B), dt)
@@ -636,10 +710,10 @@ def sac_update(st: SACState, cfg: Config, nrm: Normalizers, batch, noise_t, nois
         g_logstd = np.zeros_like(st.logstd)
     else:
         dout_a = DMU
-        g_logstd = DL.sum(axis=0, keepdims=True)
+        g_logstd = _rb_dw(DL).sum(axis=0, keepdims=True)      # actor.adam's all-ones row times E
     grads_a = actor_backward(actor_all, X, Hs, dout_a, cfg)
     if keep is not None:
-        keep.update(actor_h_p=hs_p, mu_p=mu_p, a_p=a_p, nlp_p=nlp_p, q1p=q1p, q2p=q2p,
+        keep.update(actor_h_p=hs_p, mu_p=mu_p, ls_p=ls_p, a_p=a_p, nlp_p=nlp_p, q1p=q1p, q2p=q2p,
                     dxa=dxa, dmu=DMU, dl=DL, actor_grads=grads_a, g_logstd=g_logstd)
     stats["p_loss"] = float(p_loss)
     adam_step(st.actor + [st.logstd], hook("actor", grads_a + [g_logstd]), st.opt_actor, cfg.lr_pi, dt)

@@ -2516,9 +2516,12 @@ void build_model_plan(sacx_handle* h) {
     const int nt = (Om + 15) / 16;    // fit-loss partials per row (16-column tiles of model.fwd2)
     const int ldO = (int)r4(O);       // D3 row stride
     const int ntm = (mb + 15) / 16;   // GaussianModel: logstd-gradient partials per column (row tiles)
-    // model.bwd2 generated on model.bwd1's operand loads (GR_GEN_BWD2) for narrow heads (S + 1 <= 32)
+    // model.bwd2 generated on model.bwd1's operand loads (GR_GEN_BWD2) for narrow heads (S + 1 <= 32).
+    // fp32 only: the generation is an fp32 MFMA, while model.bwd2 as a launch of its own is a bf16 GEMM
+    // under config C5 -- the fold would leave the head's dX operands unrounded in this one variant
+    // (every GEMM operand is rounded, whichever launch carries the GEMM)
     const bool bfold = fuse && h->mfuse >= 3 && O <= 32 && h->mtile != 2 && h->unaligned_b && !h->gm && !h->srn &&
-                       Dm == 2 && !h->wide;
+                       Dm == 2 && !h->wide && !h->cfg.gemm_bf16;
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
     // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>

@@ -117,6 +117,20 @@ def oracle_step(st, ocfg, nrm, buf, R, expert=None, keep=None):
     return O.sac_update(st, ocfg, nrm, O.gather(buf, R["idx"]), *n, expert=ex, keep=keep)
 
 
+def net_grads(eng, net, layers=3):
+    """A net's gradients of the last update read back through Adam's first moment (m_1 = g * (1 - beta1)):
+    [W0, b0, W1, b1, ...] of the segments <net>.l<i> (the bias is the last row of each)."""
+    m = eng.v["adam_m"][0]
+    out = []
+    for i in range(layers):
+        seg = eng.segments[f"{net}.l{i}"]
+        off = seg["offset"] // 4
+        n = seg["rows"] * seg["cols"]
+        w = m[off: off + n].cpu().numpy().reshape(seg["rows"], seg["cols"]) / B1
+        out += [w[:-1], w[-1]]
+    return out
+
+
 def relerr(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

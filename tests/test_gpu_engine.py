@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import sac_oracle as O
-from helpers import B1, load_learner, make_learner, make_pair, oracle_step, relerr
+from helpers import B1, load_learner, make_learner, make_pair, net_grads, oracle_step, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -163,16 +163,7 @@ def _one_step_compare(act, normalizers="identity", per_state_std=False, use_expe
         assert abs(row[i] - stats[k]) <= 2e-5 * abs(stats[k]) + 1e-7, (k, row[i], stats[k])
     assert abs(row[4] - stats["alpha"]) <= 1e-6 * abs(stats["alpha"])
     # gradients through Adam's first moment (m_1 = g * (1 - beta1))
-    def grads_of(net):
-        m = eng.v["adam_m"][0]
-        out = []
-        for i in range(3):
-            seg = eng.segments[f"{net}.l{i}"]
-            off = seg["offset"] // 4
-            n = seg["rows"] * seg["cols"]
-            w = m[off: off + n].cpu().numpy().reshape(seg["rows"], seg["cols"]) / B1
-            out += [w[:-1], w[-1]]
-        return out
+    grads_of = lambda net: net_grads(eng, net)
     for k in range(2):
         for gd, go in zip(grads_of(f"q{k}"), keep[f"q{k}_grads"]):
             assert relerr(gd, go) < 2e-4
