@@ -570,8 +570,28 @@ int sacx_trpo_plan_info(sacx_handle* h, int64_t rows, struct sacx_launch_info* o
  *     the Hessian of the mean kl at cur = ref; the line search uses the categorical kl; set_weights
  *     (:109-117) floors nothing.
  *   sacx_actor_act, its _host forms, sacx_rollout and sacx_sim_collect fail: a softmax handle samples
- *     on the host from sacx_ppo_dist's logits (:22-42; off the hot path). */
+ *     on the host from sacx_ppo_dist's logits (:22-42), or on the device with sacx_softmax_act /
+ *     sacx_softmax_act_host (below). */
 int sacx_softmax_init(sacx_handle* h);
+
+/* SoftMaxActor.sample (discrete_actors.py:22-42) on the device, for a bound softmax handle.
+ * obs [n,S] -> act_out [n] int32 action indices.  The logits are the actor net's (normaliser, MLP).
+ * deterministic == 0: u = np.random.random(size=(n, A)) from the device copy of the global MT19937
+ *   stream, row-major, two words per double (((w0>>5) * 2^26 + (w1>>6)) / 2^53, no rejection; the
+ *   gauss cache -- has_gauss, gauss -- is left as it is); g = float32(-log(-log u)) formed in f64
+ *   and rounded once (u = 0: g = -inf); the action is the first-index argmax of the f32
+ *   (logits - rowmax) + g.  u_out (device [n,A] doubles, or NULL) receives u itself.
+ * deterministic != 0: draws nothing, the stream is untouched; the argmax of the logits.
+ * n <= 16 rows of a two-layer net without layer norm take one workgroup per row (as
+ * sacx_actor_act's few-rows path); everything else the generic chain in chunks of 1,024 rows.
+ * Device pointers, stream-ordered.  On a packed-learners handle the call acts for the learner chosen
+ * with sacx_seed_select.  Fails on an unbound handle, on a handle without sacx_softmax_init, for
+ * n < 0 and for null obs / act_out. */
+int sacx_softmax_act(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, int32_t* act_out,
+                     double* u_out);
+/* sacx_softmax_act with HOST obs[n,S] in and HOST act_out[n] out, through the act half of the mapped
+ * pinned staging buffer; synchronous, as sacx_actor_act_host. */
+int sacx_softmax_act_host(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, int32_t* act_out);
 
 /* --- packed on-policy learners: K PPO and VCritic steps in one launch chain --------------------
  * The reference's only parallelism is --runs K (sac_eo/train.py:148-152): K independent learners.

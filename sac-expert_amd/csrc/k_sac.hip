@@ -4432,7 +4432,8 @@ struct ActShared {
     float part[4][ACT_ROWS_DIM];
     float outs[64];
 };
-template <bool PF>
+// TAIL = false (k_softmax_rows): the row's outputs stay in L.outs, behind a barrier, for the caller's own tail
+template <bool PF, bool TAIL = true>
 __device__ __forceinline__ void act_rows_body(const ActRowArgs& g_in, const int row, ActShared& L) {
     float(&xs)[ACT_ROWS_DIM] = L.xs;
     float(&h1s)[ACT_ROWS_DIM] = L.h1s;
@@ -4504,7 +4505,9 @@ __device__ __forceinline__ void act_rows_body(const ActRowArgs& g_in, const int 
             if (lane == 0) outs[wave] = s + b3;
         }
         __syncthreads();
-        if (wave == 0) act_tail(g, outs, row, lane, ls, u);
+        if constexpr (TAIL) {
+            if (wave == 0) act_tail(g, outs, row, lane, ls, u);
+        }
         return;
     }
     for (int c = t; c < S; c += 1024) xs[c] = (g.obs[(size_t)row * S + c] - g.s_mean[c]) / g.s_den[c];
@@ -4525,6 +4528,7 @@ __device__ __forceinline__ void act_rows_body(const ActRowArgs& g_in, const int 
         if (lane == 0) outs[o] = s + g.W3[(size_t)g.H1 * Aout + o];
     }
     __syncthreads();
+    if constexpr (!TAIL) return;
     if (wave != 0) return;
     const float ls = jok && !g.per_state_std ? g.logstd[lane] : 0.f;
     const float u = (jok && g.noise != nullptr) ? g.noise[(size_t)row * A + lane] : 0.f;
@@ -4635,6 +4639,111 @@ void launch_act_rng(const ActRowArgs& a, int m, const RngArgs& r, hipStream_t s,
     if (polar && r.pairs != nullptr && r.n_norm > 0)   // the split sampler's polar transform, as launch_rng
         hipLaunchKernelGGL(k_polar, dim3(std::min((r.pcap + 255) / 256, SACX_POLAR_WGS), r.nupd, seeds_z(r.nseeds)),
                            dim3(256), 0, s, r);
+}
+
+// ==================================================================== SoftMaxActor.sample
+// discrete_actors.py:22-42 on the device.  k_rng_unif draws u = np.random.random(size=(n, A)) from the
+// global stream (random_sample: two words per double, no rejection, the gauss cache untouched) and
+// leaves the Gumbel noise g = float32(-log(-log u)), formed in f64 and rounded once, in act.noise;
+// the pick is the first-index argmax of the f32 (logits - rowmax) + g, one wave per row.
+// One workgroup; the ring, the twist and the state written back are rng_body's.
+__global__ __launch_bounds__(RNG_THREADS) void k_rng_unif(UnifArgs a) {
+    __shared__ RngShared S;
+    const int t = threadIdx.x;
+    for (int i = t; i < 624; i += RNG_THREADS) rng_put(S, i, a.st->key[i]);
+    const int pos0 = a.st->pos;
+    int q = pos0;        // next stream word (block 0 word 0 = 0)
+    int gen = 624;       // stream words [0, gen) exist; [gen - RNG_RW, gen) resident
+    __syncthreads();
+    // makes words [q, q_end) resident (uniform; q_end - q <= RNG_RW - 1248), no further than `rem` needs
+    auto ensure = [&](int q_end, int rem) {
+        if (q_end <= gen) return;
+        const int keep = q > 0 ? ((q - 1) / 624) * 624 : 0;   // the last consumed word's block stays
+        int tgt = max(q_end, q + rem);
+        tgt = min(tgt, keep + RNG_RW);
+        rng_twist(S, gen, tgt);
+        gen = tgt;
+    };
+    constexpr int CH = 8 * RNG_THREADS;                 // doubles per round (16384 words)
+    for (int done = 0; done < a.n; done += CH) {
+        const int cnt = min(CH, a.n - done);
+        ensure(q + 2 * cnt, 2 * (a.n - done));
+        for (int i = t; i < cnt; i += RNG_THREADS) {
+            const uint32_t w0 = mt_temper(rng_word(S, q + 2 * i)), w1 = mt_temper(rng_word(S, q + 2 * i + 1));
+            const double u = ((double)(int32_t)(w0 >> 5) * 67108864.0 + (double)(int32_t)(w1 >> 6)) / 9007199254740992.0;
+            a.g_out[done + i] = (float)(-log(-log(u)));     // u = 0: log -> -inf, g = -inf (never a NaN)
+            if (a.u_out != nullptr) a.u_out[done + i] = u;
+        }
+        q += 2 * cnt;
+        __syncthreads();                                // the round's reads, before the next twist overwrites
+    }
+    if (q > pos0) {      // state: the block holding the last consumed word (generated to its end), the position
+        const int b = (q - 1) / 624;
+        ensure(624 * (b + 1), 0);
+        for (int i = t; i < 624; i += RNG_THREADS) a.st->key[i] = rng_at(S, 624 * b + i);
+        if (t == 0) a.st->pos = q - b * 624;
+    }
+}
+
+void launch_rng_unif(const UnifArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_rng_unif, dim3(1), dim3(RNG_THREADS), 0, s, a);
+}
+
+// one wave: the first-index argmax of (l - max l) + g over lanes < A (A <= 32); g = null: of l itself
+__device__ __forceinline__ int softmax_pick(float l, const float* g, int lane, int A) {
+    const bool ok = lane < A;
+    float v = ok ? l : -INFINITY;
+    float mx = v;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if (ok) {
+        v = v - mx;
+        if (g != nullptr) v = v + g[lane];
+    }
+    int idx = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float v2 = __shfl_xor(v, o);
+        const int i2 = __shfl_xor(idx, o);
+        if (v2 > v || (v2 == v && i2 < idx)) { v = v2; idx = i2; }
+    }
+    return idx;          // (every lane holds it; all -inf: lane 0, as np.argmax)
+}
+
+// the chain path: logits O [m, A] (sacx_ppo_dist's), one wave per row
+__global__ __launch_bounds__(256) void k_softmax_pick(SoftmaxPickArgs p) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= p.m) return;
+    const float l = lane < p.A ? p.O[(size_t)row * p.ldO + lane] : 0.f;
+    const int idx = softmax_pick(l, p.g ? p.g + (size_t)row * p.A : nullptr, lane, p.A);
+    if (lane == 0) p.out[row] = idx;
+}
+
+void launch_softmax_pick(const SoftmaxPickArgs& p, hipStream_t s) {
+    hipLaunchKernelGGL(k_softmax_pick, dim3((p.m + 3) / 4), dim3(256), 0, s, p);
+}
+
+// the few-rows path: k_act_rows' net on one workgroup per row, then the pick on wave 0
+// (g.noise: the Gumbel rows or null; g.out: the int32 action indices [m])
+template <bool PF>
+__global__ __launch_bounds__(1024) void k_softmax_rows(ActRowArgs g) {
+    __shared__ ActShared L;
+    const int row = blockIdx.x;
+    act_rows_body<PF, false>(g, row, L);
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        const float l = lane < g.A ? L.outs[lane] : 0.f;
+        const int idx = softmax_pick(l, g.noise ? g.noise + (size_t)row * g.A : nullptr, lane, g.A);
+        if (lane == 0) reinterpret_cast<int32_t*>(g.out)[row] = idx;
+    }
+    act_rows_done(g.done);
+}
+
+void launch_softmax_rows(const ActRowArgs& a, int m, hipStream_t s) {
+    const bool pf = a.S <= 128 && a.H0 <= 256 && a.H1 <= 256 && a.Aout <= 16;
+    if (pf) hipLaunchKernelGGL(k_softmax_rows<true>, dim3(m), dim3(1024), 0, s, a);
+    else hipLaunchKernelGGL(k_softmax_rows<false>, dim3(m), dim3(1024), 0, s, a);
 }
 
 // ==================================================================== k_qhead

@@ -5702,6 +5702,85 @@ int sacx_ppo_dist(sacx_handle* h, const float* s, int64_t n, float* mean_out, fl
     return ppo_rows_pass(h, s, n, r);
 }
 
+// SoftMaxActor.sample (discrete_actors.py:22-42) on the device: per chunk the uniform draw
+// u = np.random.random(size=(m, A)) as Gumbel noise in act.noise (k_rng_unif), the logits, the pick.
+// Few rows (act_rows_ok, as sacx_actor_act): one workgroup per row (k_softmax_rows); otherwise
+// sacx_ppo_dist's chain into ppo.O and k_softmax_pick.  done: the rows' completion counter (_host form)
+static int softmax_act(sacx_handle* h, const char* who, const float* obs, int64_t n, int32_t deterministic,
+                       int32_t* act_out, double* u_out, uint32_t* done) {
+    if (!h) return fail(h, "not bound");
+    if (!h->softmax)
+        return fail(h, std::string(who) + ": not a softmax handle (sacx_softmax_init); a Gaussian handle acts with sacx_actor_act");
+    if (!h->bound) return fail(h, "not bound");
+    if (n < 0 || (n > 0 && (!obs || !act_out))) return fail(h, std::string(who) + ": bad arguments");
+    if (settle(h)) return -1;
+    const int S = h->S, A = h->A;
+    auto W = [&](const std::string& nm) { return h->f(nm); };
+    float* const noise = deterministic ? nullptr : W("act.noise");
+    auto draw = [&](int m, int64_t row0) {       // the chunk's rows of u, in stream order
+        UnifArgs r{};
+        r.st = h->ptr<RngState>("rng"); r.g_out = noise; r.u_out = u_out ? u_out + row0 * A : nullptr; r.n = m * A;
+        launch_rng_unif(r, h->stream);
+    };
+    if (act_rows_ok(h, n)) {
+        if (!deterministic) draw((int)n, 0);
+        ActRowArgs a = act_rows_args(h, obs, noise, reinterpret_cast<float*>(act_out));
+        a.done = done;
+        launch_softmax_rows(a, (int)n, h->stream);
+        HIPCHK(h, hipGetLastError());
+        return 0;
+    }
+    for (int64_t at = 0; at < n; at += ACT_CAP) {
+        const int m = (int)std::min<int64_t>(ACT_CAP, n - at);
+        if (!deterministic) draw(m, at);
+        const PpoDist d = ppo_forward(h, obs + at * S, m);
+        SoftmaxPickArgs p{};
+        p.O = d.O; p.g = noise; p.out = act_out + at; p.m = m; p.A = A; p.ldO = h->Aout;
+        launch_softmax_pick(p, h->stream);
+    }
+    HIPCHK(h, hipGetLastError());
+    return 0;
+}
+
+int sacx_softmax_act(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, int32_t* act_out,
+                     double* u_out) {
+    return softmax_act(h, "sacx_softmax_act", obs, n, deterministic, act_out, u_out, nullptr);
+}
+
+// host pointers: the rows through the act half of the pinned mapped buffer, synchronous
+// (as sacx_actor_act_host; the indices come back in the same buffer, behind the observations)
+int sacx_softmax_act_host(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, int32_t* act_out) {
+    if (!h) return fail(h, "not bound");
+    if (!h->softmax)
+        return fail(h, "sacx_softmax_act_host: not a softmax handle (sacx_softmax_init); a Gaussian handle acts with sacx_actor_act");
+    if (!h->bound) return fail(h, "not bound");
+    if (n < 0 || (n > 0 && (!obs || !act_out))) return fail(h, "sacx_softmax_act_host: bad arguments");
+    const int S = h->S;
+    const int64_t chunk = std::min<int64_t>(ACT_CAP, STAGE_CAP / (S + 1));
+    if (chunk <= 0) return fail(h, "an observation row is larger than the pinned staging buffer (use sacx_softmax_act)");
+    for (int64_t at = 0; at < n; at += chunk) {
+        const int64_t m = std::min(chunk, n - at);
+        if (stage_alloc(h)) return -1;
+        float* p = h->pin + STAGE_CAP;          // the act half: its last reader was a synchronous act
+        float* g = h->pin_dev + STAGE_CAP;
+        std::memcpy(p, obs + at * S, sizeof(float) * m * S);
+        const bool rows = act_rows_ok(h, m);     // k_softmax_rows: the host polls the rows' count
+        const int rc = softmax_act(h, "sacx_softmax_act_host", g, m, deterministic, reinterpret_cast<int32_t*>(g + m * S),
+                                   nullptr, rows ? h->done_dev : nullptr);
+        if (rc) return rc;
+        if (rows) h->done_seq += (uint32_t)m;    // only once the launch that counts them is queued
+        h->act_ev_live = !(rows && h->act_poll && h->app_ctr);
+        if (h->act_ev_live) HIPCHK(h, hipEventRecord(h->act_ev, h->stream));
+        if (rows) {
+            if (act_rows_wait(h)) return -1;
+        } else {
+            HIPCHK(h, hipEventSynchronize(h->act_ev));
+        }
+        std::memcpy(act_out + at, p + m * S, sizeof(int32_t) * m);
+    }
+    return 0;
+}
+
 int sacx_ppo_kl(sacx_handle* h, const float* s, const float* mean_ref, const float* logstd_ref, int64_t n,
                 float* kl_out) {
     if (ppo_check(h)) return -1;

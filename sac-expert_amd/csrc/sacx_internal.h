@@ -875,6 +875,20 @@ struct ActRowArgs {
     uint32_t* done;
 };
 
+// SoftMaxActor.sample on the device (sacx_softmax_act): the uniform draw and the pick
+struct UnifArgs {
+    RngState* st;              // the selected learner's stream
+    float* g_out;              // [n] Gumbel noise float32(-log(-log u))
+    double* u_out;             // [n] the uniforms themselves, or null
+    int32_t n;                 // doubles drawn (rows * A)
+};
+struct SoftmaxPickArgs {
+    const float* O;            // logits [m, A], row stride ldO
+    const float* g;            // Gumbel noise [m, A], or null (deterministic: argmax of the logits)
+    int32_t* out;              // [m] action indices
+    int32_t m, A, ldO;
+};
+
 // ---------------------------------------------------------------- PPO actor update
 // The on-policy actor step of a trainable GaussianActor handle (actor_gaussian =
 // SACX_ACTOR_GAUSSIAN_TRAIN; ppo.py:41-147, :225-239, continuous_actors.py:74-192).
@@ -998,6 +1012,9 @@ void launch_ppo_reduce(const PpoReduceArgs& a, hipStream_t s);
 void launch_ppo_set(PpoPar* dst, const PpoPar& v, PpoCtl* ctl, float* acc, int64_t n, hipStream_t s);
 void launch_gnorm_part(const GNormArgs& a, hipStream_t s);
 void launch_act_rows(const ActRowArgs& a, int m, hipStream_t s);
+void launch_rng_unif(const UnifArgs& a, hipStream_t s);
+void launch_softmax_pick(const SoftmaxPickArgs& p, hipStream_t s);
+void launch_softmax_rows(const ActRowArgs& a, int m, hipStream_t s);   // a.out: int32 indices [m]
 // rows + the sampler draw beside them (+ a deferred 1-row append as one more workgroup when app is set)
 void launch_act_rng(const ActRowArgs& a, int m, const RngArgs& r, hipStream_t s, const AppendArgs* app = nullptr, bool polar = true);
 void launch_gemm(const GemmArgs& a, hipStream_t s);

@@ -47,7 +47,7 @@ EXPORTS = [
     "sacx_vcritic_steps", "sacx_vcritic_end", "sacx_vcritic_plan_info",
     "sacx_sim_collect", "sacx_model_losses_eval", "sacx_rollout_launches",
     "sacx_trpo_init", "sacx_trpo_begin", "sacx_trpo_grad", "sacx_trpo_fvp", "sacx_trpo_step", "sacx_trpo_plan_info",
-    "sacx_softmax_init",
+    "sacx_softmax_init", "sacx_softmax_act", "sacx_softmax_act_host",
     "sacx_learners_init", "sacx_ppo_steps_packed", "sacx_vcritic_steps_packed",
 ]
 
@@ -242,6 +242,8 @@ def lib():
         "sacx_vcritic_plan_info": (ctypes.c_int, [vp, i32, P(LaunchInfo), i32, P(i32)]),
         "sacx_trpo_init": (ctypes.c_int, [vp]),
         "sacx_softmax_init": (ctypes.c_int, [vp]),
+        "sacx_softmax_act": (ctypes.c_int, [vp, vp, i64, i32, vp, vp]),
+        "sacx_softmax_act_host": (ctypes.c_int, [vp, vp, i64, i32, vp]),
         "sacx_learners_init": (ctypes.c_int, [vp, i32]),
         "sacx_ppo_steps_packed": (ctypes.c_int, [vp, vp, i64, i32, P(PpoParams), i32]),
         "sacx_vcritic_steps_packed": (ctypes.c_int, [vp, vp, i64, i32, P(f32), i32]),

@@ -10,7 +10,9 @@ arguments and reads a ``_nn`` nobody builds); this is the one reading that makes
 Until an algorithm binds it the actor holds its weights in the Keras ``get_weights()`` order; once
 bound they live in the arena of a trainable engine built with ``softmax=True``, and ``neglogp`` /
 ``entropy`` / ``kl`` / ``get_kl_info`` run on the GPU (``sacx_ppo_*`` in their categorical meaning).
-``sample`` takes the logits from the engine and draws on the host: sampling is off the hot path.
+``sample`` takes the logits from the engine and draws on the host; with ``device_sample = True`` (the
+model-free loop sets it: there ``sample`` runs once per env step) the draw and the pick run on the device
+too (``Engine.softmax_act`` / ``softmax_act_host``), from the same stream.
 """
 import numpy as np
 
@@ -40,6 +42,7 @@ class SoftMaxActor:
     output_norm = False
     std_mult = 1.0
     softmax = True
+    device_sample = False       # True: sample() draws and picks on the device (Engine.softmax_act*)
 
     def __init__(self, env, layers, activations, gain, init_type='orthogonal', layer_norm=False, rng=None):
         space = env.action_space
@@ -116,6 +119,13 @@ class SoftMaxActor:
         ``u = np.random.random(size=(n, A))`` drawn under the engine's copy of the global stream, then
         the Gumbel argmax.  The deterministic form draws nothing.  ``tf.squeeze`` on the result."""
         eng = self._softmax_engine()
+        if self.device_sample:
+            rows = self._rows(s)
+            if rows.shape[0] <= 16:                      # the env loop's few rows: one pinned copy each way
+                a = eng.softmax_act_host(rows, deterministic)
+            else:
+                a = eng.softmax_act(rows, deterministic).cpu().numpy()
+            return _as_out(np.squeeze(a.astype(np.int64)))
         logits = eng.dist(self._rows(s))[0].cpu().numpy()
         u = None
         if not deterministic:

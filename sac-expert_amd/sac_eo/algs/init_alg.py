@@ -23,4 +23,11 @@ def init_alg(idx, env, env_eval, env_expert, actor, critics, q_targets, q_critic
             raise NotImplementedError(f"alg_type 'mbrl' with mf_algo {mf_algo!r}: TRPO is not built; pass --mf_algo ppo")
         from .mbrl_onpolicy_alg import MBRLOnPolicyAlg
         return MBRLOnPolicyAlg(idx, env, env_eval, actor, critics, models, alg_kwargs, mf_update_kwargs)
+    if alg_type == "mfrl":
+        # the model-free on-policy loop (base_onpolicy_alg.py): PPO or TRPO on the true environment
+        mf_algo = alg_kwargs.get("mf_algo", "trpo")
+        if mf_algo not in ("ppo", "trpo"):
+            raise ValueError(f"alg_type 'mfrl': invalid mf_algo {mf_algo!r} (ppo or trpo)")
+        from .mfrl_onpolicy_alg import MFRLOnPolicyAlg
+        return MFRLOnPolicyAlg(idx, env, env_eval, actor, critics, alg_kwargs, mf_update_kwargs)
     raise ValueError("invalid alg_type")

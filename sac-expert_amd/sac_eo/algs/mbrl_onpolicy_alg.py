@@ -24,7 +24,6 @@ TRPO (``alg_kwargs['mf_algo'] == 'trpo'``) runs when the class is constructed di
 ``sac_eo.algs.model_free.trpo.TRPO`` and an engine with ``trpo=True``, and the loop logs whatever keys
 ``update`` returns.  ``init_alg`` (the front door of ``python -m sac_eo.train``) still refuses it.
 """
-import contextlib
 import dataclasses
 import time
 
@@ -34,16 +33,16 @@ from ..common.buffers import TrajectoryBuffer
 from ..common.corruptor import TrajectoryCorruptor
 from ..common.logger import Logger
 from ..common.normalizer import RunningNormalizers
-from ..common.samplers import trajectory_sampler
 from ..engine import Engine, EngineConfig
 from .base import epoch_minibatches
+from .onpolicy_base import OnPolicyLoop
 from .model_free import PPO, VCriticUpdate
 from .model_free.ppo import aggregate_rows
 
 MAX_ROWS = 1 << 24          # the trainable handle's bound on buffer_capacity
 
 
-class MBRLOnPolicyAlg:
+class MBRLOnPolicyAlg(OnPolicyLoop):
     """Base class for MBRL algorithms with on-policy updates (``mbrl_onpolicy_alg.py:11-33``)."""
 
     def __init__(self, idx, env, env_eval, actor, critics, models, alg_kwargs, mf_update_kwargs):
@@ -85,25 +84,8 @@ class MBRLOnPolicyAlg:
 
     # ------------------------------------------------------------------ setup
     def _setup(self, k):
-        """base_onpolicy_alg.py:66-109 and mbrl_onpolicy_alg.py:35-59."""
-        self.gamma, self.lam = k["gamma"], k["lam"]
-        self.env_buffer_size = int(k["env_buffer_size"]) if k.get("env_buffer_size") else None
-        self.init_rms_stats = k.get("init_rms_stats")
-        self.save_path, self.checkpoint_file = k.get("save_path", "./logs"), k.get("checkpoint_file", "TEMPLOG")
-        self.save_freq, self.eval_freq = k.get("save_freq"), k.get("eval_freq")
-        self.last_eval = 0
-        self.eval_num_traj = k.get("eval_num_traj", 5)
-        self.mf_algo_name = k["mf_algo"]
-        self.total_timesteps = int(k.get("total_timesteps", 0) or 0)
-        self.env_horizon = k["env_horizon"]
-        self.env_batch_type = k["env_batch_type"]
-        self.env_batch_size_init, self.env_batch_size = k["env_batch_size_init"], k["env_batch_size"]
-        self.s_noise_std, self.s_noise_type = float(k.get("s_noise_std") or 0.0), k.get("s_noise_type", "all")
-        self.critic_lr = k["critic_lr"]
-        self.critic_update_it, self.critic_nminibatch = k["critic_update_it"], k["critic_nminibatch"]
-        self.num_mf_updates = k["num_mf_updates"]
-        self.alg_seed = k.get("alg_seed")
-        self.rng = np.random.default_rng(self.alg_seed)
+        """base_onpolicy_alg.py:66-109 (OnPolicyLoop._setup_base) and mbrl_onpolicy_alg.py:35-59."""
+        self._setup_base(k)
         self.sim_buffer_size = int(k["sim_buffer_size"]) if k.get("sim_buffer_size") else None
         self.sim_horizon, self.sim_batch_type, self.sim_batch_size = k["sim_horizon"], k["sim_batch_type"], k["sim_batch_size"]
         self.model_lr = k["model_lr"]
@@ -188,84 +170,24 @@ class MBRLOnPolicyAlg:
         eng.rng_set_state(np.random.get_state())       # adopt the global stream
         return eng
 
-    @contextlib.contextmanager
-    def _host_rng(self):
-        np.random.set_state(self.engine.rng_get_state())
-        try:
-            yield
-        finally:
-            self.engine.rng_set_state(np.random.get_state())
-
-    def _set_rms(self):
-        """Shares normalizers with all relevant classes (base :199-204, mbrl :61-65)."""
-        self.actor.set_rms(self.normalizer)
-        for critic in self.critics:
-            critic.set_rms(self.normalizer)
-        self.corruptor.set_rms(self.normalizer)
-        for model in self.models:
-            model.set_rms(self.normalizer)
-        self.normalizer.push_to(self.engine)
+    def _rms_users(self):
+        """The world models share the normalizers too (mbrl :61-65)."""
+        return self.models
 
     # ------------------------------------------------------------------ env data
-    def _collect_expert_data(self):
-        return None
-
-    def _collect_env_data(self, num_timesteps, update_normalizers=True):
-        """base_onpolicy_alg.py:115-172."""
-        t0 = time.time()
-        batch_size = self.env_batch_size_init if num_timesteps == 0 else self.env_batch_size
-        steps_start, traj_start = self.env_data.steps_total, self.env_data.traj_total
-        cur, J_all = 0, []
-        while cur < batch_size:
-            horizon = int(np.minimum(batch_size - cur, self.env_horizon)) if self.env_batch_type == "steps" \
-                else self.env_horizon
-            s, a, r, sp, d, J = trajectory_sampler(self.env, self.actor, horizon, eval=True, corruptor=self.corruptor)
-            if update_normalizers:
-                self.normalizer.update_rms(s, a, r, sp)
-                self.normalizer.push_to(self.engine)
-            self.env_data.add(s, a, r, sp, d)
-            self.engine.append(s, a, r, sp, np.asarray(d, np.float32))
-            if horizon == self.env_horizon:
-                J_all.append(J)
-            cur = self.env_data.steps_total - steps_start if self.env_batch_type == "steps" \
-                else self.env_data.traj_total - traj_start
-        steps_new = self.env_data.steps_total - steps_start
-        J_ave = float(np.mean(J_all)) if J_all else float("nan")
-        self.current_reward = J_ave
-        self.logger.log_train({"J_tot": J_ave, "steps": steps_new, "traj": self.env_data.traj_total - traj_start,
-                               "time_env_data": time.time() - t0})
-        return steps_new
-
-    def _evaluate(self, num_timesteps):
-        """base_onpolicy_alg.py:174-197."""
-        t0 = time.time()
-        J = [trajectory_sampler(self.env_eval, self.actor, self.env_horizon, eval=True, deterministic=True)[-1]
-             for _ in range(self.eval_num_traj)]
-        self.logger.log_train({"J_tot_eval": float(np.mean(J)), "steps_eval": num_timesteps - self.last_eval,
-                               "time_eval": time.time() - t0})
-        self.last_eval = num_timesteps
+    def _store_trajectory(self, s, a, r, sp, d):
+        """The host TrajectoryBuffer, and the device ring the world models and the rollouts read."""
+        self.env_data.add(s, a, r, sp, d)
+        self.engine.append(s, a, r, sp, np.asarray(d, np.float32))
 
     # ------------------------------------------------------------------ update
     def _update(self):
         self._update_models()
         self._update_actor_critic()
 
-    def _answer(self, req):
-        """One learner's own answer to a request of the loop: the update on its engine."""
-        if req[0] == "critic_update":
-            return self.critic_update.update(req[1], req[2])
-        if req[0] == "actor_update":
-            return self.mf_algo.update(req[1])
-        raise ValueError(req[0])
-
-    def _drive(self, gen):
-        """Runs a generator of the loop to its end, answering every request on this learner."""
-        try:
-            req = next(gen)
-            while True:
-                req = gen.send(self._answer(req))
-        except StopIteration as stop:
-            return stop.value
+    def _update_gen(self):
+        self._update_models()
+        yield from self._update_actor_critic_gen()
 
     def _fit(self, batches, rows, base):
         """The device steps of a list of [B, model_batch] index arrays into the training rows."""
@@ -393,46 +315,9 @@ class MBRLOnPolicyAlg:
         self.logger.log_train({"ent_agg": np.float32(ent), "kl_agg": np.float32(kl), "alpha_agg": self.mf_algo.alpha,
                                "time_ac_agg": time.time() - t_ac})
 
-    # ------------------------------------------------------------------ loop
-    def train(self, total_timesteps, params):
-        """base_onpolicy_alg.py:285-349."""
-        return self._drive(self._train_loop(total_timesteps, params))
-
-    def _train_loop(self, total_timesteps, params):
-        """base_onpolicy_alg.py:285-349 as a generator (the requests of _update_actor_critic_gen)."""
-        self._set_rms()
-        self._collect_expert_data()
-        pts = lambda freq: np.concatenate((np.arange(0, total_timesteps, freq)[1:], [total_timesteps]))
-        checkpoints = np.array([total_timesteps]) if self.save_freq is None else pts(self.save_freq)
-        evaluate = self.eval_freq is not None
-        eval_points = pts(self.eval_freq) if evaluate else None
-        ck = ev = 0
-        num_timesteps = 0
-        if evaluate:
-            self._evaluate(num_timesteps)
-        while num_timesteps < total_timesteps:
-            num_timesteps += self._collect_env_data(num_timesteps)
-            self._update_models()
-            yield from self._update_actor_critic_gen()
-            if evaluate and num_timesteps >= eval_points[ev]:
-                self._evaluate(num_timesteps)
-                ev = min(ev + 1, len(eval_points) - 1)
-            if num_timesteps >= checkpoints[ck]:
-                self._dump_and_save(params)
-                ck = min(ck + 1, len(checkpoints) - 1)
-        self._dump_and_save(params)
-        return self.checkpoint_name
-
+    # ------------------------------------------------------------------ log
     def _dump_stats(self):
         """base_onpolicy_alg.py:351-364 + mbrl_onpolicy_alg.py:321-329."""
-        return {"actor_weights": self.actor.get_weights(),
-                "critic_weights": [c.get_weights() for c in self.critics],
-                "rms_stats": self.normalizer.get_rms_stats(),
+        return {**super()._dump_stats(),
                 "model_weights": [m.get_weights() for m in self.models],
                 "reward_weights": [m.get_reward_weights() for m in self.models]}
-
-    def _dump_and_save(self, params):
-        self.logger.log_params(params)
-        self.logger.log_final(self._dump_stats())
-        self.logger.dump_and_save(self.save_path, self.checkpoint_name)
-        self.logger.reset()

@@ -610,6 +610,36 @@ class Engine:
         self._keep_eval = x
         return pi, nlp
 
+    def softmax_act(self, obs, deterministic: bool = False, return_u: bool = False):
+        """SoftMaxActor.sample (discrete_actors.py:22-42) on the device: obs [n, S] or [S] -> action
+        indices [n] (int32, a CUDA tensor; 0-d for a single row).  Unless deterministic,
+        u = np.random.random(size=(n, A)) comes from the device copy of the global NumPy stream;
+        return_u=True also returns it ([n, A] float64, CUDA; None when deterministic)."""
+        single = np.ndim(obs) == 1 if not torch.is_tensor(obs) else obs.dim() == 1
+        S, A = self.cfg.s_dim, self.cfg.a_dim
+        o = self._dev(obs, (-1, S))
+        n = int(o.shape[0])
+        out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        u = torch.empty((n, A), dtype=torch.float64, device=self.device) if return_u and not deterministic else None
+        N.check(self.lib.sacx_softmax_act(self.h, ctypes.c_void_p(o.data_ptr()), n, int(bool(deterministic)),
+                                          ctypes.c_void_p(out.data_ptr()),
+                                          ctypes.c_void_p(u.data_ptr()) if u is not None else None),
+                self.h, "softmax_act")
+        self._keep_act = o
+        a = out[0] if single else out
+        return (a, u) if return_u else a
+
+    def softmax_act_host(self, obs, deterministic: bool = False) -> np.ndarray:
+        """softmax_act for the env loop: host obs [n, S] or [S] -> host action indices [n] (int32; 0-d for
+        one row).  One pinned copy each way inside the library; synchronous."""
+        S = self.cfg.s_dim
+        single = np.ndim(obs) == 1 if not torch.is_tensor(obs) else obs.dim() == 1
+        o = self._host_f32(obs, (-1, S))
+        out = np.empty((o.shape[0],), dtype=np.int32)
+        N.check(self.lib.sacx_softmax_act_host(self.h, o.ctypes.data, int(o.shape[0]), int(bool(deterministic)),
+                                               out.ctypes.data), self.h, "softmax_act_host")
+        return out[0] if single else out
+
     # ------------------------------------------------------------------ PPO actor update
     # (EngineConfig(actor_gaussian="train"); every call fails with a message on any other engine)
     @property

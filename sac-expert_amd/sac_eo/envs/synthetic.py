@@ -29,6 +29,30 @@ class Box:
         return x.shape == self.shape and np.all(x >= self.low) and np.all(x <= self.high)
 
 
+class Discrete:
+    """gym.spaces.Discrete subset: n, shape (), sample(), seed(), contains(); no low / high."""
+
+    def __init__(self, n):
+        self.n = int(n)
+        self.shape = ()
+        self.dtype = np.int64
+        self.np_random = np.random.RandomState(0)
+
+    def seed(self, seed=None):
+        self.np_random = np.random.RandomState(seed)
+
+    def sample(self):
+        return int(self.np_random.randint(self.n))
+
+    def contains(self, x):
+        x = np.asarray(x)
+        return x.shape == () and x.dtype.kind in "iu" and 0 <= int(x) < self.n
+
+
+# obs_dim, actions of the discrete tasks (classic control / Box2D)
+DISCRETE_ENV_SPECS = {"CartPole-v1": (4, 2), "Acrobot-v1": (6, 3), "LunarLander-v2": (8, 4)}
+
+
 class SyntheticEnv:
     """s' = 0.9 s + 0.5 tanh(W_s s + W_a a) + noise, r = s'_0 - 0.1 |a|^2 (a cheetah-like
     'forward velocity' minus control cost).  Its randomness comes from its own
@@ -78,8 +102,34 @@ class SyntheticEnv:
         return sp.copy(), r, done, {}
 
 
+class SyntheticDiscreteEnv(SyntheticEnv):
+    """SyntheticEnv's dynamics with a Discrete action space: action i selects the fixed row i of W_a,
+    s' = 0.9 s + 0.5 tanh(W_s s + W_a[i]) + noise, r = s'_0."""
+
+    def __init__(self, name="CartPole-v1", max_episode_steps=1000, terminate=False):
+        s, n = DISCRETE_ENV_SPECS[name]
+        super().__init__(name, obs_dim=s, act_dim=n, max_episode_steps=max_episode_steps, terminate=terminate)
+        self.action_space = Discrete(n)
+
+    def step(self, a):
+        i = int(np.asarray(a).reshape(()))
+        if not 0 <= i < self.action_space.n:
+            raise ValueError(f"action {i} outside Discrete({self.action_space.n})")
+        s = self._s
+        sp = 0.9 * s + 0.5 * np.tanh(s @ self._Ws + self._Wa[i]) \
+            + 0.01 * self.np_random.normal(size=s.shape)
+        sp = sp.astype(np.float32)
+        r = float(sp[0])
+        self._t += 1
+        done = bool(self.terminate and np.abs(sp).max() > 10.0) or self._t >= self._max_episode_steps
+        self._s = sp
+        return sp.copy(), r, done, {}
+
+
 def init_env(env_type="gym", env_name="HalfCheetah-v3", task_name=None):
     """sac_eo/envs/init_env (gym path): RescaleAction(-1, 1) shapes of the named task."""
     if env_type not in ("gym", "synthetic"):
         raise ValueError(f"env_type {env_type!r} is not available here (gym-style synthetic only)")
+    if env_name in DISCRETE_ENV_SPECS:
+        return SyntheticDiscreteEnv(env_name)
     return SyntheticEnv(env_name)

@@ -7,7 +7,8 @@ ONE device handle in lock-step (sac_eo.algs.lockstep: one launch chain per times
 of them, each run's log identical to its serial run's), or -- with ``--serial_runs``, or where
 lock-step cannot hold (SAC with early-terminating episodes, ``--env_batch_type traj``,
 ``--actor_layer_norm``) -- one after another.  ``--alg_type mbrl --mf_algo ppo --pack_runs`` trains the
-runs of one process as the packed learners of one engine (``EngineConfig(learners=K)``), in lock-step.  No data moves between learners (SURVEY §8e:
+runs of one process as the packed learners of one engine (``EngineConfig(learners=K)``), in lock-step.  ``--alg_type mfrl`` (the model-free on-policy
+loop, PPO or TRPO: how an expert is trained here) trains its runs one after another.  No data moves between learners (SURVEY §8e:
 replicas).  As in the reference (``:159-191``), the runs' checkpoint logs are gathered into one
 pickled list ``<env_type>_<env>_<alg_type>_<mf_algo>[_<save_file>]_<date>`` and removed."""
 import copy
@@ -149,6 +150,13 @@ def main(argv=None):
     if args.alg_type in ("sac", "sac_imit", "bc"):
         # SAC uses the squashed actor; the device BC trains the squashed actor only
         inputs_dict["actor_kwargs"]["actor_squash"] = True
+    if args.alg_type == "mfrl":
+        # the model-free on-policy loop: the plain GaussianActor (or, on a Discrete space, the SoftMaxActor),
+        # PPO or TRPO; its runs train one after another, each on its own engine (--pack_runs does not apply)
+        if args.actor_squash:
+            raise ValueError("--alg_type mfrl trains the plain GaussianActor: --actor_squash is not supported")
+        if inputs_dict["actor_kwargs"].get("actor_output_norm"):
+            raise ValueError("--alg_type mfrl: --actor_output_norm has no backward on the device")
     if args.alg_type == "mbrl":
         # the model-based on-policy loop trains the plain GaussianActor (actor_squash stays False); its runs
         # train one after another (lockstep_ok), each on its own engine -- or, with --pack_runs, as the packed
