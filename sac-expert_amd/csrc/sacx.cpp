@@ -2669,17 +2669,23 @@ void build_model_plan(sacx_handle* h) {
             if (p.mse) return true;
         return false;
     };
+    int n_fwd0 = 1;                                  // launches of level 0
     for (int i = 0; i <= Lf; ++i) {
         const std::string name = "model.fwd" + std::to_string(i);
         const int t32_fit = h->tile32;
         if (i == 0) {
-            add_gemm(h, plan, name, f[0], false);    // (<= SACX_MAX_MODELS problems: one launch)
+            // the gather folded into layer 0's operand loads: one launch (gfold needs !srn, so f[0] holds
+            // nm <= SACX_MAX_MODELS problems); otherwise, with the reward nets' layer 0 beside the models',
+            // up to 2 nm problems, GEMM_MAXP to a launch as at every other level
             if (gfold) {
+                add_gemm(h, plan, name, f[0], false);
                 Launch& F = plan.back();
                 set_rows(F, GR_GATHER);         // (16x16 tiles: a row is a whole record)
                 F.gemm.mg = mg;
                 F.name = "model.gather+fwd0";
                 F.bytes += 4.0 * nm * mb * (2.0 * S + A + 1 + O);
+            } else {
+                n_fwd0 = add_gemm_split(h, plan, name, f[0], false);
             }
             continue;
         }
@@ -2689,13 +2695,18 @@ void build_model_plan(sacx_handle* h) {
         } else if (i == Lf && h->mtile == 1 && (h->mt32 & 8) && !h->gm && !h->srn) {
             h->tile32 = 2;     // the heads (+ the MSE loss epilogue) on 32x32 tiles (mt32 bit 8; MSE heads only)
         }
-        add_gemm_split(h, plan, name, f[i], false);
+        const size_t first = plan.size();
+        const int n_lv = add_gemm_split(h, plan, name, f[i], false);
         h->tile32 = t32_fit;
+        // fuse_fwd2 pairs the plan's last two launches: layer 0 and layer 1, each ONE launch (a split level
+        // -- more than GEMM_MAXP nets, which is more than k_fwd2's 4 -- keeps its launches as they are)
+        const bool pair01 = i == 1 && n_fwd0 == 1 && n_lv == 1;
         // the gathered layer 0 and layer 1 as ONE k_fwd2 launch (SACX_MFWD2, default; K0 = S + A <= 32)
-        if (i == 1 && gfold && h->mfwd2) fuse_fwd2(h, plan, "model.gather+fwd01");
+        if (pair01 && gfold && h->mfwd2) fuse_fwd2(h, plan, "model.gather+fwd01");
         // or, pre-gathered, layer 0 (GR_PREGATHERED: H0 <= 512, plain A) and layer 1 the same way
-        if (i == 1 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32 && !h->wide) fuse_fwd2(h, plan, "model.fwd01", true);
-        if (i == Lf && fuse) plan.back().name = "model.fwd" + std::to_string(i) + "+loss";
+        if (pair01 && pre && h->mfwd2 && h->mtile != 2 && S + A <= 32 && !h->wide) fuse_fwd2(h, plan, "model.fwd01", true);
+        if (i == Lf && fuse)       // (every launch of a split last level: model.fwd<i>+loss, model.fwd<i>.1+loss)
+            for (size_t j = std::min(first, plan.size() - 1); j < plan.size(); ++j) plan[j].name += "+loss";
     }
     if (!fuse) {
         Launch L{};

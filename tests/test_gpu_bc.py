@@ -35,6 +35,8 @@ CASES = {
     "one_model": dict(hidden=(64, 64), model_hidden=(96, 96), num_models=1, ne=11),
     # sections 7 / 7 / 6: 14 rows used, 14 A normals
     "three_models": dict(hidden=(64, 64), model_hidden=(96, 96), num_models=3, ne=20),
+    # the advertised maximum: eight sections of 2 rows, every world model a problem of the model launches
+    "eight_models": dict(hidden=(64, 64), model_hidden=(96, 96), num_models=8, ne=16),
     "deep": dict(hidden=(48, 64, 48), model_hidden=(64, 96, 64), ne=12),
     "layer_norm": dict(hidden=(64, 80, 48), model_hidden=(96, 96), ne=12, layer_norm=True),
     "pss_elu": dict(hidden=(64, 64, 64), model_hidden=(96, 96), ne=12, per_state_std=True, act="elu"),

@@ -29,6 +29,8 @@ SHAPES = {
     "pendulum": dict(S=3, A=1, model_hidden=(32, 32), nm=2),
     "halfcheetah": dict(S=17, A=6, model_hidden=(96,), nm=3),
     "gauss": dict(S=3, A=1, model_hidden=(32, 32), nm=2, gaussian_model=True),
+    # the advertised maximum; sim_collect rolls out its last model
+    "eight": dict(S=3, A=1, model_hidden=(32, 32), nm=8, collect_model=7),
 }
 
 
@@ -80,7 +82,8 @@ def make_case(shape, seed=3, logstd=None, std_mult=1.0, capacity=CAP, appended=A
 
 
 COLLECT = [("pendulum", 1, 1, False), ("pendulum", 5, 5, False), ("halfcheetah", 5, 5, False),
-           ("halfcheetah", 1, 5, True), ("halfcheetah", 4097, 2, False), ("gauss", 5, 5, False)]
+           ("halfcheetah", 1, 5, True), ("halfcheetah", 4097, 2, False), ("gauss", 5, 5, False),
+           ("eight", 5, 5, False), ("eight", 1, 5, True)]
 
 
 @pytest.mark.parametrize("shape,n,H,det", COLLECT)
@@ -89,8 +92,9 @@ def test_sim_collect_against_the_restatement(gpu_available, shape, n, H, det):
     assert held["s"].shape[0] == CAP and not np.array_equal(held["s"], eng.v["replay"][:, :ocfg.S].cpu().numpy())
     rs = np.random.RandomState(77)
     eng.rng_set_state(rs.get_state())
-    got = [t.cpu().numpy() for t in eng.sim_collect(1, n, H, deterministic=det, delta_clip=0.8, reward_clip=2.0)]
-    idx, ref = M.sim_collect(st, ocfg, nrm, held["s"], n, H, 1, rs, deterministic=det, delta_clip=0.8, reward_clip=2.0)
+    k = SHAPES[shape].get("collect_model", 1)
+    got = [t.cpu().numpy() for t in eng.sim_collect(k, n, H, deterministic=det, delta_clip=0.8, reward_clip=2.0)]
+    idx, ref = M.sim_collect(st, ocfg, nrm, held["s"], n, H, k, rs, deterministic=det, delta_clip=0.8, reward_clip=2.0)
     S = ocfg.S
     errs = {k: relerr(g, r) for k, g, r in zip(("s", "a", "r", "sp"), got, ref)}
     print(f"{shape} n={n} H={H} det={det}: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
@@ -165,40 +169,60 @@ def test_graph_replay_equals_eager(gpu_available, monkeypatch):
     assert np.array_equal(outs["graph"][2][1], outs["eager"][2][1]) and outs["graph"][2][2:5] == outs["eager"][2][2:5]
 
 
-def test_model_fit_equals_an_eo_handle(gpu_available):
-    """3 steps of model_fit (2 models, minibatch 16) on the world-models handle and on an SAC-EO handle
-    with the same weights, normaliser and ring: the same launches and arithmetic, bit for bit."""
-    idx = np.random.RandomState(13).randint(CAP, size=(3, 2, 16))
+def _fit_on_both_handle_kinds(shape, steps=3):
+    nm = SHAPES[shape]["nm"]
+    idx = np.random.RandomState(13).randint(CAP, size=(steps, nm, 16))
     res = []
     for expert in (False, True):
-        eng, ocfg, st, nrm, held = make_case("pendulum", expert=expert)
+        eng, ocfg, st, nrm, held = make_case(shape, expert=expert)
         eng.model_fit(idx)
         eng.sync()
-        res.append(([w for k in range(2) for w in eng.get_net(f"m{k}")], eng.model_stats(3).copy()))
+        res.append(([w for k in range(nm) for w in eng.get_net(f"m{k}")], eng.model_stats(steps).copy()))
         if not expert:
-            init = [np.asarray(w, np.float32) for k in range(2) for w in st.models[k]]
+            init = [np.asarray(w, np.float32) for k in range(nm) for w in st.models[k]]
             assert not any(np.array_equal(a, b) for a, b in zip(res[0][0], init))      # trained
         eng.close()
+    assert len(res[0][0]) == len(res[1][0]) == nm * (2 * len(SHAPES[shape]["model_hidden"]) + 2)
     for a, b in zip(res[0][0], res[1][0]):
         assert np.array_equal(a, b)
     assert np.array_equal(res[0][1], res[1][1]) and np.all(np.isfinite(res[0][1]))
 
 
-@pytest.mark.parametrize("shape", ["halfcheetah", "gauss"])
-@pytest.mark.parametrize("n", [1, 17, 1025, 4100])
-def test_model_losses_eval(gpu_available, shape, n):
+def test_model_fit_equals_an_eo_handle(gpu_available):
+    """3 steps of model_fit (2 models, minibatch 16) on the world-models handle and on an SAC-EO handle
+    with the same weights, normaliser and ring: the same launches and arithmetic, bit for bit."""
+    _fit_on_both_handle_kinds("pendulum")
+
+
+def test_model_fit_equals_an_eo_handle_eight_models(gpu_available):
+    """The same at 8 models: 24 dW problems, three model.adam launches on either handle kind."""
+    _fit_on_both_handle_kinds("eight")
+
+
+def _losses_eval(shape, n, models):
     eng, ocfg, st, nrm, held = make_case(shape)
     r = np.random.RandomState(n)
     s = (r.normal(size=(n, ocfg.S)) * 1.5).astype(np.float32)
     a = r.uniform(-1, 1, (n, ocfg.A)).astype(np.float32)
     sp = (s + r.normal(size=(n, ocfg.S)) * 0.3).astype(np.float32)
     rr = r.normal(size=n).astype(np.float32)
-    for k in range(2):
+    for k in models:
         got = eng.model_losses_eval(k, s, sp, a, rr)
         ref = M.losses_eval(st, ocfg, nrm, k, s, sp, a, rr)
         print(f"{shape} n={n} model {k}: mse {got[0]:.6g} / {ref[0]:.6g}  r {got[1]:.6g} / {ref[1]:.6g}")
         assert abs(got[0] - ref[0]) <= 2e-5 * abs(ref[0]) and abs(got[1] - ref[1]) <= 2e-5 * abs(ref[1]), (got, ref)
     eng.close()
+
+
+@pytest.mark.parametrize("shape", ["halfcheetah", "gauss"])
+@pytest.mark.parametrize("n", [1, 17, 1025, 4100])
+def test_model_losses_eval(gpu_available, shape, n):
+    _losses_eval(shape, n, range(2))
+
+
+@pytest.mark.parametrize("n", [1, 1025])
+def test_model_losses_eval_eight_models(gpu_available, n):
+    _losses_eval("eight", n, (0, 5, 7))
 
 
 def test_refusals_on_the_device(gpu_available):
