@@ -1348,527 +1348,6 @@ void xbf_wire(sacx_handle* h, std::vector<Launch>& plan, int slot) {
     }
 }
 
-void build_plan(sacx_handle* h, int slot, bool record_probs) {
-    std::vector<Launch>& plan = h->plan[slot];
-    plan.clear();
-    h->probs_cursor = 0;
-    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, B = h->B, ne = h->ne, Aout = h->Aout;
-    const int Hm0 = h->Hm0, Hm1 = h->Hm1, half = ne / 2;
-    const int Hc0 = h->Hc0, Hc1 = h->Hc1;   // the critics' hidden sizes (--critic_layers; H0 / H1: the actor's)
-    // expert rows of world model k: [k * half, (k + 1) * half) with 2 or more models (the expert term
-    // takes models 0 and 1, SAC_expert.py:325-326), all with one
-    const int nm = std::min(h->nm, 2), mrows = nm == 1 ? ne : half;
-    const int ldS = h->ldS, ldQ = h->ldQ;
-    const int a0 = h->aact[0], a1 = h->aact[1], c0 = h->cact[0], c1 = h->cact[1], m0 = h->macts[0], m1 = h->macts[1];
-    const bool eo = h->cfg.use_expert != 0;
-    const std::string sl = "slot" + std::to_string(slot);
-    float* noise = h->f(sl + ".noise");
-    float* noise_t = noise;
-    float* noise_pi = noise + (size_t)B * A;
-    float* noise_e = noise + (size_t)2 * B * A;
-    float* noise_al = noise + (size_t)(2 * B + ne) * A;
-    auto W = [&](const std::string& n) { return h->f(n); };
-    float *Xa = W(sl + ".Xa"), *Xq = W(sl + ".Xq"), *Xt = W(sl + ".Xt"), *Xp = W(sl + ".Xp"), *Xm = W(sl + ".Xm");
-    float *r_in = W(sl + ".r"), *d_in = W(sl + ".d"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
-    float *Ha1 = W("ws.Ha1"), *Ha2 = W("ws.Ha2");
-    float *Hq1 = W("ws.Hq1"), *Hq2 = W("ws.Hq2"), *Dq1 = W("ws.Dq1"), *Dq2 = W("ws.Dq2");
-    float *Hp1 = W("ws.Hp1"), *Hp2 = W("ws.Hp2"), *Dp1 = W("ws.Dp1");
-    float *Hm1b = W("ws.Hm1"), *Hm2b = W("ws.Hm2"), *Dm1 = W("ws.Dm1"), *Dm2 = W("ws.Dm2");
-    float *Da1 = W("ws.Da1"), *Da2 = W("ws.Da2"), *Da3 = W("ws.Da3"), *E = W("ws.E");
-    float *Hl1 = W("ws.Hl1"), *Hl2 = W("ws.Hl2");
-    const char* qn[4] = {"t0", "t1", "q0", "q1"};
-
-    plan_inputs(h, plan, slot);
-    // ---- actor forward on [sp ; s ; s_e]
-    // the two forward layers of a net as two launches (a fused two-layer tile recomputing
-    // layer 0 per column tile measured slower once the alpha branch and the heads share
-    // launches: 12.06k vs 12.33k updates/s, DESIGN.md section 6)
-    auto fwd_pair = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
-        add_gemm(h, plan, name + "0", p0, record_probs);
-        add_gemm(h, plan, name + "1", p1, record_probs);
-    };
-    // the same pair as ONE k_fwd2 launch where it qualifies (fuse_fwd2), else the two launches
-    auto fwd_pair2 = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
-        fwd_pair(name, p0, p1);
-        if (h->fwd2) fuse_fwd2(h, plan, name + "01");
-    };
-    const int Ra4 = (h->Ra + 3) & ~3;       // first row of the alpha rows (ws.Hl1 / ws.Hl2 alias Ha1 / Ha2)
-    // --actor_layer_norm: layer 0 writes the pre-norm Z, k_ln turns it into tanh(LN(Z)) in place
-    auto ln_fwd = [&](const std::string& name, int r0, int r1) {
-        Launch L{};
-        L.kind = Launch::LNORM;
-        L.name = name;
-        LNArgs& a = L.ln;
-        a.mode = 0; a.H = H0; a.Z = Ha1; a.nrange = 1; a.r[0] = r0; a.r[1] = r1;
-        a.gamma = W("actor.ln"); a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.cache_rows = h->Ra;
-        L.grid = (r1 - r0 + 3) / 4;
-        L.flops = 8.0 * (r1 - r0) * H0;
-        L.bytes = 4.0 * (r1 - r0) * H0 * 3;
-        plan.push_back(L);
-    };
-    // actor.fwd1 writes the head's Ha2 . W3 as per-column-tile partials (GR_HEAD_PART), so the head
-    // rows and the target-tile prologues sum 16 values per output instead of re-reading Ha2
-    // rows.  SACX_HEAD_PART=0 keeps the row dots (A/B measurement).
-    const char* hpe = std::getenv("SACX_HEAD_PART");
-    const int tqh = (H1 + 15) / 16;
-    const bool head_part = Aout <= 8 && H1 <= 256 && H1 % 64 == 0 &&
-                           (hpe ? std::atoi(hpe) != 0 : h->tile32_plan == 0);
-    float* hpart = W("ws.hpart");
-    // layer 1 of the actor on `rows` rows from row r0 of Ha1 / Ha2 (+ the head partials)
-    auto actor_fwd1 = [&](int r0, int rows) {
-        GemmProb p = prob_fwd(Ha1 + (size_t)r0 * H0, H0, rows, H0, W("actor.l1"), H1, Ha2 + (size_t)r0 * H1, a1);
-        if (head_part) {
-            p.pw = W("actor.l2"); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;   // W3[n][o] at n * Aout + o
-            p.ppart = hpart + (size_t)r0 * Aout * tqh;
-        }
-        return p;
-    };
-    auto mark_part = [&]() { if (head_part) set_rows(plan.back(), GR_HEAD_PART); };
-    if (h->ln) {
-        add_gemm(h, plan, "actor.fwd0", {prob_fwd(Xa, ldS, h->Ra, S, W("actor.l0"), H0, Ha1, ACT_NONE)}, record_probs);
-        ln_fwd("actor.ln", 0, h->Ra);
-        add_gemm(h, plan, "actor.fwd1", {actor_fwd1(0, h->Ra)}, record_probs);
-        mark_part();
-    } else {
-        fwd_pair("actor.fwd", {prob_fwd(Xa, ldS, h->Ra, S, W("actor.l0"), H0, Ha1, a0)}, {actor_fwd1(0, h->Ra)});
-        mark_part();
-        if (h->fwd2) fuse_fwd2(h, plan, "actor.fwd01");
-    }
-    // actor.head folded into q.fwd0 (plain SAC): the target tiles compute their rows' actions
-    // in a prologue, the policy rows (and the previous update's alpha rows) run as extra
-    // workgroups of the same launch.  SACX_FUSE_HEAD=0 keeps the separate launch.
-    const char* fh = std::getenv("SACX_FUSE_HEAD");
-    // Packed seeds (>= 4) keep the separate launch: the prologue recomputes each tile's 16 rows
-    // once per column tile, which a full GPU of seeds pays for (measured 34.3k vs 31.6k updates/s
-    // at 8 seeds); one seed gains the launch it saves.
-    // SAC-EO as well: the expert rows (sample -> the world models' inputs Xm) ride as row
-    // workgroups of q.fwd0, and the models' forward shifts one launch later (layer 0 in q.fwd1,
-    // layer 1 in pi.q.fwd0, the MSE head in pi.q.fwd1)
-    const bool fuse_head = Aout <= 16 && S + A <= 64 && H1 % 16 == 0 && H1 <= 512 &&
-                           (fh ? std::atoi(fh) != 0 : h->plan_seeds < 4);
-    HeadArgs head_fused{};
-    // actor.head.bwd folded into actor.bwd1 (plain SAC; the expert rows' model gradients keep
-    // the row kernel): pi.q.bwd1 writes per-tile partial action gradients, actor.bwd1's tiles
-    // finish them.  SACX_FOLD_HBW=0 keeps the separate launch (A/B measurement).
-    const char* fhb = std::getenv("SACX_FOLD_HBW");
-    const int tq = (Hc0 + 15) / 16;        // action-gradient partials per row (the critics' layer-0 tiles)
-    // The folded launch itself keeps 16x16 tiles (its prologue and generated A operand); the
-    // partial-writing launches may take 32x32 tiles.  On 32x32 (packed) plans both folds are off
-    // by default: there the launches are bound by workgroup residency, not by their number, and
-    // the folds' extra work loses (HC 8 seeds, A/B x2: both on 42.3k, hbw fold only 43.4k, head
-    // partials only 43.1k, both off 43.9k updates/s; tools/pk_ab.sh).
-    const bool fold_hbw = Aout <= 8 && H1 <= 256 && H1 % 16 == 0 && Hc0 <= 256 && Hc0 % 64 == 0 &&
-                          (!eo || (Hm0 <= 512 && Hm0 % 64 == 0)) &&
-                          (fhb ? std::atoi(fhb) != 0 : h->tile32_plan == 0);
-    // ---- actor head
-    if (fuse_head) {
-        HeadArgs& a = head_fused;
-        a.H2 = Ha2; a.ldh = H1; a.W3 = W("actor.l2"); a.logstd = W("actor.logstd");
-        a.part = head_part ? hpart : nullptr; a.tq = tqh;
-        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
-        a.ma_mean = W(mnorm(h, "a_mean")); a.ma_den = W(mnorm(h, "a_den"));
-        // q.fwd0 carries the target rows (tile prologues) and, folded, the previous update's
-        // alpha rows; the policy rows ride as extra workgroups of critic.adam (policy_head)
-        a.nseg = 1;
-        a.seg[0] = {0, B, 0, 0, noise_t, nullptr, W("ws.nlp_t")};
-        // total_rows = Ra: merged_body appends the previous update's alpha rows at round4(Ra),
-        // where their layer-2 outputs live (ws.Hl2 aliases Ha2 from row round4(Ra))
-        a.total_rows = h->Ra;
-        a.cache_row0 = 1 << 30;             // no backward cache from these rows (target, alpha)
-        a.cache_row1 = 1 << 30;
-        if (eo) {                           // SAC-EO expert rows: sample() into Xm, cached
-            a.nseg = 2;
-            a.seg[1] = {2 * B, 2 * B + ne, 1, 0, noise_e, Xm, nullptr};
-            a.cache_row0 = B;
-            a.cache_row1 = h->Ra;
-        }
-        a.c_t = W("ws.c_t"); a.c_std = W("ws.c_std"); a.c_u = W("ws.c_u"); a.c_mask = W("ws.c_mask");
-        a.alpha_mode = 0;
-    } else {
-        Launch L{};
-        L.kind = Launch::AHEAD;
-        L.name = "actor.head";
-        L.frees_slot = true;
-        HeadArgs& a = L.head;
-        a.H2 = Ha2; a.ldh = H1; a.W3 = W("actor.l2"); a.logstd = W("actor.logstd");
-        a.part = head_part ? hpart : nullptr; a.tq = tqh;
-        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
-        a.ma_mean = W(mnorm(h, "a_mean")); a.ma_den = W(mnorm(h, "a_den"));
-        a.nseg = eo ? 3 : 2;
-        a.seg[0] = {0, B, 0, 0, noise_t, Xt, W("ws.nlp_t")};
-        a.seg[1] = {B, 2 * B, 0, 0, noise_pi, Xp, W("ws.nlp_p")};
-        a.seg[2] = {2 * B, 2 * B + ne, 1, 0, noise_e, Xm, nullptr};
-        a.total_rows = h->Ra;
-        a.cache_row0 = B;
-        a.cache_row1 = h->Ra;
-        a.c_t = W("ws.c_t"); a.c_std = W("ws.c_std"); a.c_u = W("ws.c_u"); a.c_mask = W("ws.c_mask");
-        a.alpha_mode = 0;
-        L.grid = (h->Ra + 3) / 4;
-        L.flops = 2.0 * h->Ra * H1 * Aout;
-        L.bytes = 4.0 * h->Ra * (H1 + 6.0 * A);
-        plan.push_back(L);
-    }
-    // ---- target / critic / model forward
-    if (fuse_head) {
-        std::vector<GemmProb> p0, p1;
-        for (int k = 0; k < 4; ++k) {
-            const std::string n = qn[k];
-            GemmProb q0 = prob_fwd(k < 2 ? Xt : Xq, ldQ, B, S + A, W(n + ".l0"), Hc0, Hq1 + (size_t)k * B * Hc0, c0);
-            q0.headp = k < 2;
-            GemmProb q1 = prob_fwd(Hq1 + (size_t)k * B * Hc0, Hc0, B, Hc0, W(n + ".l1"), Hc1, Hq2 + (size_t)k * B * Hc1, c1);
-            p0.push_back(q0);
-            p1.push_back(q1);
-        }
-        add_gemm(h, plan, "q.fwd0+actor.head", p0, record_probs);
-        Launch& L = plan.back();
-        set_rows(L, GR_ACTOR_HEAD);
-        L.gemm.head = head_fused;
-        L.gemm.head_block0 = eo ? (2 * B) / 4 : ((h->Ra + 3) & ~3) / 4;
-        L.gemm.row_blocks = eo ? (h->Ra + 3) / 4 - (2 * B) / 4 : 0;   // + the alpha rows (merged_body)
-        L.grid += L.gemm.row_blocks;
-        L.flops += 2.0 * B * H1 * Aout;
-        L.bytes += 4.0 * B * (H1 + 6.0 * A);
-        L.frees_slot = true;
-        if (eo) {                           // the models' layer 0 on Xm (written by the rows above)
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                p1.push_back(prob_fwd(Xm + (size_t)k * half * ldQ, ldQ, mrows, S + A, W(n + ".l0"), Hm0,
-                                      Hm1b + (size_t)k * half * Hm0, m0));
-            }
-        }
-        add_gemm(h, plan, "q.fwd1", p1, record_probs);
-        if (h->fwd2 && !eo) fuse_fwd2(h, plan, "q.fwd01+actor.head");
-    } else {
-        std::vector<GemmProb> p0, p1;
-        for (int k = 0; k < 4; ++k) {
-            const std::string n = qn[k];
-            p0.push_back(prob_fwd(k < 2 ? Xt : Xq, ldQ, B, S + A, W(n + ".l0"), Hc0, Hq1 + (size_t)k * B * Hc0, c0));
-            p1.push_back(prob_fwd(Hq1 + (size_t)k * B * Hc0, Hc0, B, Hc0, W(n + ".l1"), Hc1, Hq2 + (size_t)k * B * Hc1, c1));
-        }
-        if (eo) {
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                p0.push_back(prob_fwd(Xm + (size_t)k * half * ldQ, ldQ, mrows, S + A, W(n + ".l0"), Hm0,
-                                      Hm1b + (size_t)k * half * Hm0, m0));
-                p1.push_back(prob_fwd(Hm1b + (size_t)k * half * Hm0, Hm0, mrows, Hm0, W(n + ".l1"), Hm1,
-                                      Hm2b + (size_t)k * half * Hm1, m1));
-            }
-        }
-        fwd_pair("q.fwd", p0, p1);
-    }
-    // ---- critic backward.  By linearity Dq1 = g (.) M1 with M1 = ((w3 (.) act'(Hq2)) Wq1^T) (.) act'(Hq1)
-    // independent of the per-row loss gradient g, so the dX GEMM (A generated from Hq2 and w3)
-    // shares one launch with the q.head rows (target, g, loss rows, Dq2, expert MSE + Dm2), and
-    // critic.adam applies g to layer 0 (row-scaled B).
-    {
-        QHeadArgs q{};
-        q.mode = 0; q.B = B; q.H1 = Hc1; q.H2 = Hq2;
-        for (int k = 0; k < 4; ++k) q.W3[k] = W(std::string(qn[k]) + ".l2");
-        q.act = c1; q.D2 = Dq2; q.g = W("ws.gq"); q.loss_rows = W("ws.lq");
-        q.alpha = W("alpha"); q.nlp = W("ws.nlp_t"); q.r = r_in; q.d = d_in;
-        q.gamma = h->cfg.gamma; q.ret_den = W("norm.ret_den"); q.w_sac = 1.f;
-        // the SAC-EO world-model head on the expert rows runs as GEMM problems (mse epilogue)
-        // in the pi.q.fwd0 launch, not as rows here
-        q.ne = 0; q.ctl = h->ctl();
-        std::vector<GemmProb> pb;
-        for (int k = 0; k < 2; ++k) {
-            const std::string n = "q" + std::to_string(k);
-            GemmProb p = prob_dx(Hq2 + (size_t)(2 + k) * B * Hc1, B, Hc1, W(n + ".l1"), Hc0,
-                                 Hq1 + (size_t)(2 + k) * B * Hc0, Dq1 + (size_t)k * B * Hc0, c0);
-            p.wgen = W(n + ".l2");             // w3 column of W3_ext
-            p.gen_act = c1;                    // act'(Hq2); the epilogue takes act'(Hq1)
-            pb.push_back(p);
-        }
-        add_gemm(h, plan, "q.head+critic.bwd1", pb, record_probs);
-        Launch& L = plan.back();
-        set_rows(L, GR_QHEAD);
-        L.gemm.row_blocks = (B + 3) / 4;
-        L.gemm.qh = q;
-        L.grid += L.gemm.row_blocks;
-        L.flops += 2.0 * B * Hc1 * 4 + 2.0 * B * Hc1 * 2;
-        L.bytes += 4.0 * (4.0 * B * Hc1 + 2.0 * B * Hc1 * 2);
-        std::vector<GemmProb> pw;
-        for (int k = 0; k < 2; ++k) {
-            const std::string n = "q" + std::to_string(k), t = "t" + std::to_string(k);
-            GemmProb p0 = prob_dw(Xq, ldQ, S + A, B, Dq1 + (size_t)k * B * Hc0, Hc0, W(n + ".l0"), W(t + ".l0"), GRP_Q);
-            p0.bscale = W("ws.gq") + (size_t)k * B;   // Dq1 = g (.) M1
-            pw.push_back(p0);
-            pw.push_back(prob_dw(Hq1 + (size_t)(2 + k) * B * Hc0, Hc0, Hc0, B, Dq2 + (size_t)k * B * Hc1, Hc1, W(n + ".l1"),
-                                 W(t + ".l1"), GRP_Q));
-            pw.push_back(prob_dw(Hq2 + (size_t)(2 + k) * B * Hc1, Hc1, Hc1, B, W("ws.gq") + (size_t)k * B, 1,
-                                 W(n + ".l2"), W(t + ".l2"), GRP_Q));
-        }
-        add_gemm(h, plan, "critic.adam", pw, record_probs, !fuse_head);
-        if (fuse_head) {                    // the policy rows of actor.head (read from pi.q.fwd0 on)
-            Launch& L = plan.back();
-            HeadArgs a = head_fused;
-            a.nseg = 1;
-            a.seg[0] = {B, 2 * B, 0, 0, noise_pi, Xp, W("ws.nlp_p")};
-            a.total_rows = 2 * B;
-            a.cache_row0 = B;
-            a.cache_row1 = h->Ra;
-            L.name += "+actor.head";
-            set_rows(L, GR_POLICY_HEAD);
-            L.gemm.head = a;
-            L.gemm.head_block0 = B / 4;
-            L.gemm.row_blocks = (2 * B + 3) / 4 - B / 4;
-            L.grid += L.gemm.row_blocks;
-            L.flops += 2.0 * B * H1 * Aout;
-            L.bytes += 4.0 * B * (H1 + 6.0 * A);
-        }
-        if (h->dp_ranks > 0) dp_split_adam(h, plan, "q0.l0", "q1.l2", "t0.l0", GRP_Q);
-    }
-    // ---- policy loss through the updated critics: the same linearity; pi.q.head's rows
-    // (min, tie split, loss rows, g0 / g1) share the unscaled dX launch, actor.head.bwd applies
-    // g0 / g1.  The SAC-EO world-model dX (needs q.head's Dm2) rides in the same launch.
-    {
-        std::vector<GemmProb> p0, p1;
-        for (int k = 0; k < 2; ++k) {
-            const std::string n = "q" + std::to_string(k);
-            p0.push_back(prob_fwd(Xp, ldQ, B, S + A, W(n + ".l0"), Hc0, Hp1 + (size_t)k * B * Hc0, c0));
-            p1.push_back(prob_fwd(Hp1 + (size_t)k * B * Hc0, Hc0, B, Hc0, W(n + ".l1"), Hc1, Hp2 + (size_t)k * B * Hc1, c1));
-        }
-        // SAC-EO: world-model layer 2 on the expert rows + MSE epilogue (needs Hm2 from q.fwd1),
-        // riding in the pi.q.fwd0 launch (a launch of its own when that one is fused)
-        std::vector<GemmProb> pm;
-        const int mtn = (S + 15) / 16;
-        if (eo) {
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                GemmProb p{};
-                p.A = Hm2b + (size_t)k * half * Hm1; p.lda = Hm1; p.a_kc = 1; p.ones_row = -1;
-                p.B = W(n + ".l2"); p.ldb = h->Om; p.b_kc = 0;       // W_ext [(Hm1+1) x Om], Om = S (+1)
-                p.M = mrows; p.N = S; p.K = Hm1;                     // delta-s columns only
-                p.bias = W(n + ".l2") + (size_t)Hm1 * h->Om;
-                p.C = W("ws.dout") + (size_t)k * half * S; p.ldc = S;
-                p.epi = EPI_FWD; p.act = ACT_NONE;
-                p.mse = 1; p.grad_scale = 1.f / (float)mrows;       // MSE_loss = mean over the rows
-                p.dclip = h->cfg.delta_clip_pred > 0.f ? h->cfg.delta_clip_pred : 0.f;
-                p.se_raw = se_raw + (size_t)k * half * S; p.spe_raw = spe_raw + (size_t)k * half * S;
-                p.dmean = W("mnorm.d_mean"); p.dden = W("mnorm.d_den");
-                p.part = W("ws.mse") + (size_t)k * half * mtn;
-                pm.push_back(p);
-            }
-        }
-        if (eo && fuse_head) {               // the models' layer 1 on Hm1 (from q.fwd1)
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                p0.push_back(prob_fwd(Hm1b + (size_t)k * half * Hm0, Hm0, mrows, Hm0, W(n + ".l1"), Hm1,
-                                      Hm2b + (size_t)k * half * Hm1, m1));
-            }
-        }
-        if (eo) fwd_pair("pi.q.fwd", p0, p1);
-        else fwd_pair2("pi.q.fwd", p0, p1);
-        if (eo) {                            // plan.back() is pi.q.fwd1: fold into pi.q.fwd0 (or, with
-                                             // the fused head, into pi.q.fwd1: Hm2 comes from pi.q.fwd0)
-            Launch& F0 = plan[plan.size() - (fuse_head ? 1 : 2)];
-            std::vector<Launch> one;
-            add_gemm(h, one, "model.head", pm, false);
-            h->probs_cursor -= (int)pm.size();
-            if (!merge_gemm(F0.gemm, one[0].gemm)) { fprintf(stderr, "sacx: model.head merge\n"); abort(); }
-            F0.name += "+model.head";
-            F0.grid = F0.gemm.total_tiles;
-            F0.flops += one[0].flops;
-            F0.bytes += one[0].bytes;
-        }
-        QHeadArgs q{};
-        q.mode = 1; q.B = B; q.H1 = Hc1; q.H2 = Hp2;
-        q.W3[0] = W("q0.l2"); q.W3[1] = W("q1.l2"); q.W3[2] = nullptr; q.W3[3] = nullptr;
-        q.act = c1; q.D2 = nullptr; q.g = W("ws.gp"); q.loss_rows = W("ws.lp");
-        q.alpha = W("alpha"); q.nlp = W("ws.nlp_p");
-        q.w_sac = eo ? (float)(1.0 - (double)h->cfg.epsilon) : 1.f;
-        q.ret_den = W("norm.ret_den");
-        q.ne = 0; q.ctl = h->ctl();
-        std::vector<GemmProb> pb;
-        for (int k = 0; k < 2; ++k) {
-            const std::string n = "q" + std::to_string(k);
-            GemmProb p = prob_dx(Hp2 + (size_t)k * B * Hc1, B, Hc1, W(n + ".l1"), Hc0, Hp1 + (size_t)k * B * Hc0,
-                                 Dp1 + (size_t)k * B * Hc0, c0);
-            p.wgen = W(n + ".l2");
-            p.gen_act = c1;
-            pb.push_back(p);
-        }
-        if (eo) {                            // Dm2 = dout . Wm2[:, :S]^T (.) act'(Hm2)
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                GemmProb p = prob_dx(W("ws.dout") + (size_t)k * half * S, mrows, S, W(n + ".l2"), Hm1,
-                                     Hm2b + (size_t)k * half * Hm1, Dm2 + (size_t)k * half * Hm1, m1);
-                p.ldb = h->Om;                       // B[n][k] = W_ext[n][k], row stride Om
-                pb.push_back(p);
-            }
-        }
-        if (fold_hbw) {                      // partial action gradients instead of Dp1 (read by no one else)
-            for (int k = 0; k < 2; ++k) {
-                GemmProb& p = pb[k];
-                p.pw = W("q" + std::to_string(k) + ".l0") + (size_t)S * Hc0;   // action rows of W_ext
-                p.pw_ld = Hc0;
-                p.pw_cs = 1;
-                p.pw_n = A;
-                p.ppart = W("ws.apart") + (size_t)k * B * tq * A;
-                p.C = nullptr;
-            }
-        }
-        add_gemm(h, plan, "pi.q.head+pi.q.bwd1", pb, record_probs);
-        {
-            Launch& L = plan.back();
-            set_rows(L, GR_PIQHEAD);
-            L.gemm.row_blocks = (B + 3) / 4;
-            L.gemm.qh = q;
-            L.grid += L.gemm.row_blocks;
-            L.flops += 2.0 * B * Hc1 * 2 * 2;
-            L.bytes += 4.0 * (2.0 * B * Hc1 * 2);
-        }
-        if (eo) {                            // Dm1 = Dm2 . Wm1^T (.) act'(Hm1), for actor.head.bwd
-            std::vector<GemmProb> pd;
-            for (int k = 0; k < nm; ++k) {
-                const std::string n = "m" + std::to_string(k);
-                pd.push_back(prob_dx(Dm2 + (size_t)k * half * Hm1, mrows, Hm1, W(n + ".l1"), Hm0,
-                                     Hm1b + (size_t)k * half * Hm0, Dm1 + (size_t)k * half * Hm0, m0));
-            }
-            if (fold_hbw) {                  // partial action gradients of the expert rows instead of Dm1
-                const int tqm = (Hm0 + 15) / 16;
-                for (int k = 0; k < nm; ++k) {
-                    GemmProb& p = pd[k];
-                    p.pw = W("m" + std::to_string(k) + ".l0") + (size_t)S * Hm0;   // action rows of W_ext
-                    p.pw_ld = Hm0;
-                    p.pw_cs = 1;
-                    p.pw_n = A;
-                    p.ppart = W("ws.mpart") + (size_t)k * half * A * tqm;
-                    p.C = nullptr;
-                }
-            }
-            add_gemm(h, plan, "model.bwd1", pd, record_probs);
-            if (fold_hbw) set_rows(plan.back(), GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
-        }
-    }
-    // ---- actor backward
-    if (fold_hbw) {
-        // actor.head.bwd as the tile prologue of actor.bwd1: Da3 from the partials of pi.q.bwd1,
-        // Da2 generated on load (an MFMA from Da3 and W3a), stored by column tile 0
-        const int Rb = h->Rb;
-        GemmProb p = prob_dx(Ha2 + (size_t)B * H1, Rb, H1, W("actor.l1"), H0, Ha1 + (size_t)B * H0, Da1,
-                             h->ln ? ACT_TANH : a0);
-        p.wgen = W("actor.l2");              // W3a [(H1+1) x Aout]
-        p.gen_act = a1;                      // act'(Ha2)
-        p.hbw = 1;
-        add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
-        Launch& L = plan.back();
-        set_rows(L, GR_HEAD_BWD);
-        HeadBwdArgs& b = L.gemm.hbw;
-        b.B = B; b.A = A; b.Aout = Aout; b.per_state_std = h->cfg.per_state_std; b.tq = tq;
-        b.lim = h->cfg.act_limit; b.part = W("ws.apart"); b.gpol = W("ws.gp"); b.a_den = W("norm.a_den");
-        b.ma_den = W(mnorm(h, "a_den")); b.alpha = W("alpha");
-        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
-        b.Da3 = Da3; b.E = E; b.Da2 = Da2;
-        b.ne = ne; b.tqm = (Hm0 + 15) / 16; b.mpart = eo ? W("ws.mpart") : nullptr; b.ctl = eo ? h->ctl() : nullptr;
-        L.flops += 2.0 * B * 2 * Hc0 * A + 2.0 * Rb * H1 * Aout;
-        L.bytes += 4.0 * (2.0 * B * tq * A + 2.0 * Rb * H1);
-    }
-    {
-        Launch L{};
-        L.kind = Launch::ABWD;
-        L.name = "actor.head.bwd";
-        ActorBwdArgs& b = L.ab;
-        b.B = B; b.ne = ne; b.S = S; b.A = A; b.Aout = Aout; b.H0 = Hc0; b.H1 = H1; b.Hm0 = Hm0;   // Dp1 / Wq1: critic
-        b.per_state_std = h->cfg.per_state_std; b.lim = h->cfg.act_limit;
-        b.Dp1 = Dp1; b.Wq1[0] = W("q0.l0"); b.Wq1[1] = W("q1.l0");
-        b.Dm1 = Dm1; b.Wm1[0] = eo ? W("m0.l0") : nullptr; b.Wm1[1] = eo ? W(nm > 1 ? "m1.l0" : "m0.l0") : nullptr;
-        b.a_den = W("norm.a_den"); b.ma_den = W(mnorm(h, "a_den")); b.alpha = W("alpha"); b.ctl = h->ctl();
-        b.use_expert = eo;
-        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
-        b.W3a = W("actor.l2"); b.Ha2 = Ha2 + (size_t)B * H1; b.act = a1;
-        b.Da3 = Da3; b.Da2 = Da2; b.E = E;
-        b.gpol = W("ws.gp");
-        L.grid = (h->Rb + 3) / 4;
-        L.flops = 2.0 * B * 2 * Hc0 * A + 2.0 * ne * Hm0 * A + 2.0 * h->Rb * H1 * Aout;
-        L.bytes = 4.0 * (2.0 * B * Hc0 + ne * Hm0 + 2.0 * h->Rb * H1);
-        const int Rb = h->Rb;
-        if (!fold_hbw) {
-            plan.push_back(L);
-            add_gemm(h, plan, "actor.bwd1",      // layer-norm layer 0: tanh' at its output
-                     {prob_dx(Da2, Rb, H1, W("actor.l1"), H0, Ha1 + (size_t)B * H0, Da1, h->ln ? ACT_TANH : a0)},
-                     record_probs);
-        }
-        if (h->ln) {                          // dY -> dZ through the norm; dY*xhat, dY for gamma / beta
-            Launch N{};
-            N.kind = Launch::LNORM;
-            N.name = "actor.ln.bwd";
-            LNArgs& a = N.ln;
-            a.mode = 1; a.H = H0; a.Z = Da1; a.r[1] = Rb; a.gamma = W("actor.ln");
-            a.xhat = W("ws.ln_xhat"); a.rstd = W("ws.ln_rstd"); a.xrow0 = B;
-            a.gy = W("ws.ln_gy"); a.gb = W("ws.ln_gb");
-            N.grid = (Rb + 3) / 4;
-            N.flops = 8.0 * Rb * H0;
-            N.bytes = 4.0 * Rb * H0 * 5;
-            plan.push_back(N);
-        }
-        std::vector<GemmProb> pw;
-        pw.push_back(prob_dw(Xa + (size_t)B * ldS, ldS, S, Rb, Da1, H0, W("actor.l0"), nullptr, GRP_PI));
-        pw.push_back(prob_dw(Ha1 + (size_t)B * H0, H0, H0, Rb, Da2, H1, W("actor.l1"), nullptr, GRP_PI));
-        pw.push_back(prob_dw(Ha2 + (size_t)B * H1, H1, H1, Rb, Da3, Aout, W("actor.l2"), nullptr, GRP_PI));
-        if (!h->cfg.per_state_std) {
-            GemmProb p = prob_dw(E, 1, 0, Rb, E, A, W("actor.logstd"), nullptr, GRP_PI);
-            p.ones_row = 0;   // single all-ones row: column sums of E
-            pw.push_back(p);
-        }
-        if (h->ln) {          // gamma, beta: column sums of dY*xhat and dY
-            for (int k = 0; k < 2; ++k) {
-                float* gsrc = W(k ? "ws.ln_gb" : "ws.ln_gy");
-                GemmProb p = prob_dw(gsrc, 1, 0, Rb, gsrc, H0, W("actor.ln") + (size_t)k * H0, nullptr, GRP_PI);
-                p.ones_row = 0;
-                pw.push_back(p);
-            }
-        }
-        add_gemm(h, plan, "actor.adam", pw, record_probs);
-        if (h->dp_ranks > 0) dp_split_adam(h, plan, "actor.l0", "actor.logstd", "", GRP_PI);
-    }
-    // ---- alpha: updated actor on s, evaluate, Adam on alpha, statistics
-    const size_t alpha_first = plan.size();
-    // the alpha forward is folded into the next update's actor forward (merged_body): same fusion
-    if (h->ln) {
-        add_gemm(h, plan, "alpha.fwd0", {prob_fwd(Xa + (size_t)B * ldS, ldS, B, S, W("actor.l0"), H0, Hl1, ACT_NONE)},
-                 record_probs);
-        ln_fwd("alpha.ln", Ra4, Ra4 + B);
-        add_gemm(h, plan, "alpha.fwd1", {actor_fwd1(Ra4, B)}, record_probs);
-        mark_part();
-    } else {
-        fwd_pair("alpha.fwd", {prob_fwd(Xa + (size_t)B * ldS, ldS, B, S, W("actor.l0"), H0, Hl1, a0)},
-                 {actor_fwd1(Ra4, B)});
-        mark_part();
-        // fused as the actor pair is, so merged_body folds one k_fwd2 launch into the other
-        if (h->fwd2) fuse_fwd2(h, plan, "alpha.fwd01");
-    }
-    {
-        Launch L{};
-        L.kind = Launch::AHEAD;
-        L.name = "alpha.head";
-        HeadArgs& a = L.head;
-        a.H2 = Hl2; a.ldh = H1; a.W3 = W("actor.l2"); a.logstd = W("actor.logstd");
-        a.part = head_part ? hpart + (size_t)Ra4 * Aout * tqh : nullptr; a.tq = tqh;
-        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
-        a.nseg = 1;
-        a.seg[0] = {0, B, 0, 0, noise_al, nullptr, W("ws.nlp3")};
-        a.total_rows = B;
-        a.cache_row0 = 1 << 30;
-        a.c_t = nullptr;
-        a.alpha_mode = 1;
-        L.fin.red = W("red");                       // per-workgroup partials of sum(-nlp + H)
-        L.fin.target_entropy = h->cfg.target_entropy;
-        L.grid = (B + 3) / 4;
-        L.flops = 2.0 * B * H1 * Aout;
-        L.bytes = 4.0 * B * H1;
-        plan.push_back(L);
-    }
-    plan_alpha_final(h, plan, nm);
-    // alpha.fwd .. alpha.final only feed the next update's q.head
-    for (size_t i = alpha_first; i < plan.size(); ++i) plan[i].alpha_branch = true;
-    xbf_wire(h, plan, slot);
-    for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
-}
-
 // Appends one GEMM launch per GEMM_MAXP problems (a launch's problems travel by value): `name`,
 // then name.1, name.2, ...  Returns the launches added.
 int add_gemm_split(sacx_handle* h, std::vector<Launch>& plan, const std::string& name, const std::vector<GemmProb>& ps,
@@ -1882,10 +1361,12 @@ int add_gemm_split(sacx_handle* h, std::vector<Launch>& plan, const std::string&
 }
 
 // ---------------------------------------------------------------- shared plan builders
-// What the per-layer plans (generic SAC / SAC-EO, BC, the PPO step, a TRPO chunk) have in common: the
-// actor's forward, dX and dW chains over a caller's buffers, and the world models' expert-row problems.
-// What is specific to a caller (EPI_STORE, bscale, t_adv, the data-parallel split, folds) it applies to
-// what these return.
+// What the update plans (fused and generic SAC / SAC-EO, BC, the PPO step, a TRPO chunk) have in common: the
+// actor's forward, dX and dW chains over a caller's buffers, the critics' and the world models' problems by
+// net and layer, and the arguments of the head row kernels (k_actor_head, k_qhead, k_actor_bwd and the
+// head backward folded into actor.bwd1).  What is specific to a caller (EPI_STORE, bscale, wgen, headp,
+// t_adv, the data-parallel split, folds, a launch's flops / bytes once rows ride on it) it applies to what
+// these return.
 
 // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
 float* chain_buf(sacx_handle* h, const std::string& p, int i, int D) {
@@ -2026,14 +1507,18 @@ ParamRange actor_range(const sacx_handle* h) {
     return {h->arena ? h->f("actor.l0") : nullptr, (int64_t)((end - h->off_of("actor.l0")) / 4)};
 }
 
+// GaussianActor.logstd_init (continuous_actors.py:39-44), f32: log(std_mult), - log(log 2) with per_state_std
+float logstd_init(const sacx_handle* h) {
+    const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
+    return (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+}
+
 // the trainable GaussianActor's distribution over the output rows O [m, Aout]
 PpoDist ppo_dist(sacx_handle* h, const float* O) {
     PpoDist d{};
     d.O = O; d.A = h->A; d.Aout = h->Aout; d.per_state_std = h->cfg.per_state_std;
     d.logstd = h->f("actor.logstd");
-    // logstd_init (continuous_actors.py:39-44), f32, as sacx_actor_act's
-    const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-    d.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    d.logstd_init = logstd_init(h);
     d.softmax = h->softmax ? 1 : 0;
     return d;
 }
@@ -2101,6 +1586,491 @@ std::vector<GemmProb> model_bwd_probs(sacx_handle* h, int i) {
     return pb;
 }
 
+// The critics' problems by net and layer, as model_fwd_prob.  A chain (ws.Hq / ws.Dq: the target and critic
+// rows, ws.Hp / ws.Dp: the policy rows) holds one slab of B rows per net: t0 t1 q0 q1 in ws.Hq, q0 q1 in the
+// others.  Forward: `net`'s hidden layer i into slab `slab` of chain Hn, layer 0 reading X = [s | a]
+GemmProb critic_fwd_prob(sacx_handle* h, const std::string& net, const float* X, const std::string& Hn, int slab, int i) {
+    const NetDims& nc = h->nd[1];
+    const int Dc = nc.D(), B = h->B;
+    const float* in = i == 0 ? X : chain_buf(h, Hn, i - 1, Dc) + (size_t)slab * B * nc.h[i - 1];
+    return prob_fwd(in, i == 0 ? h->ldQ : nc.h[i - 1], B, i == 0 ? h->S + h->A : nc.h[i - 1], h->f(layer_name(net, i)), nc.h[i],
+                    chain_buf(h, Hn, i, Dc) + (size_t)slab * B * nc.h[i], nc.act[i]);
+}
+
+// dX: the delta at `net`'s hidden layer i to layer i - 1, slab `dslab` of chain Dn, with act' at slab `hslab`
+// of chain Hn.  gen: the A operand is slab `hslab` of Hn at layer i instead, for a caller that generates the
+// delta from it on load (wgen, gen_act)
+GemmProb critic_dx_prob(sacx_handle* h, const std::string& net, const std::string& Hn, int hslab, const std::string& Dn,
+                        int dslab, int i, bool gen = false) {
+    const NetDims& nc = h->nd[1];
+    const int Dc = nc.D(), B = h->B;
+    const float* D = gen ? chain_buf(h, Hn, i, Dc) + (size_t)hslab * B * nc.h[i] : chain_buf(h, Dn, i, Dc) + (size_t)dslab * B * nc.h[i];
+    return prob_dx(D, B, nc.h[i], h->f(layer_name(net, i)), nc.h[i - 1], chain_buf(h, Hn, i - 1, Dc) + (size_t)hslab * B * nc.h[i - 1],
+                   chain_buf(h, Dn, i - 1, Dc) + (size_t)dslab * B * nc.h[i - 1], nc.act[i - 1]);
+}
+
+// dW + Keras Adam + Polyak into t<k> of q<k>'s layer i on the critic rows Xq (i = Dc: the output layer, from
+// the loss gradient ws.gq)
+GemmProb critic_dw_prob(sacx_handle* h, int k, const float* Xq, int i) {
+    const NetDims& nc = h->nd[1];
+    const int Dc = nc.D(), B = h->B;
+    const std::string n = "q" + std::to_string(k), t = "t" + std::to_string(k);
+    const float* X = i == 0 ? Xq : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1];
+    const int K = i == 0 ? h->S + h->A : nc.h[i - 1];
+    if (i == Dc) return prob_dw(X, K, K, B, h->f("ws.gq") + (size_t)k * B, 1, h->f(layer_name(n, i)), h->f(layer_name(t, i)), GRP_Q);
+    return prob_dw(X, i == 0 ? h->ldQ : K, K, B, chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], nc.h[i],
+                   h->f(layer_name(n, i)), h->f(layer_name(t, i)), GRP_Q);
+}
+
+// k_qhead's arguments on the last hidden rows H2, D2 the delta it writes there (nullable).  mode 0 (q.head):
+// twin-Q target, TD target from the rewards r and terminals d, the critic losses; mode 1 (pi.q.head): min,
+// tie split, the policy loss rows and the output gradients of q0 / q1
+QHeadArgs q_head_args(sacx_handle* h, int mode, const float* H2, float* D2, const float* r, const float* d) {
+    const NetDims& nc = h->nd[1];
+    const int Dc = nc.D();
+    const char* nets[4] = {"t0", "t1", "q0", "q1"};
+    QHeadArgs q{};
+    q.mode = mode; q.B = h->B; q.H1 = h->Hc1; q.H2 = H2;
+    for (int k = 0; k < (mode ? 2 : 4); ++k) q.W3[k] = h->f(layer_name(nets[mode ? 2 + k : k], Dc));
+    q.act = nc.act[Dc - 1]; q.D2 = D2; q.g = h->f(mode ? "ws.gp" : "ws.gq"); q.loss_rows = h->f(mode ? "ws.lp" : "ws.lq");
+    q.alpha = h->f("alpha"); q.nlp = h->f(mode ? "ws.nlp_p" : "ws.nlp_t"); q.r = r; q.d = d;
+    if (mode == 0) q.gamma = h->cfg.gamma;
+    q.ret_den = h->f("norm.ret_den");
+    q.w_sac = (mode && h->cfg.use_expert) ? (float)(1.0 - (double)h->cfg.epsilon) : 1.f;
+    // (the SAC-EO world-model head on the expert rows runs as GEMM problems with the mse epilogue, not as rows here)
+    q.ne = 0; q.ctl = h->ctl();
+    return q;
+}
+
+// k_actor_head's arguments on the rows H2 of the actor's last hidden layer, `part` their head partials
+// (GR_HEAD_PART) or null; the caller adds the segments, the row counts, the cache rows and alpha_mode.
+// update: an update's actor.head -- its sample segments write the world models' inputs (their normaliser for
+// the action columns) and its cached rows feed the backward (ws.c_*).  alpha.head and the inference paths
+// have neither.
+HeadArgs head_args(sacx_handle* h, const float* H2, const float* part, bool update) {
+    HeadArgs a{};
+    a.H2 = H2; a.ldh = h->H1; a.W3 = h->f(actor_head_name(h)); a.logstd = h->f("actor.logstd");
+    a.part = part; a.tq = (h->H1 + 15) / 16;
+    a.H1 = h->H1; a.A = h->A; a.Aout = h->Aout; a.S = h->S; a.ldQ = h->ldQ; a.per_state_std = h->cfg.per_state_std;
+    a.lim = h->cfg.act_limit; a.a_mean = h->f("norm.a_mean"); a.a_den = h->f("norm.a_den");
+    if (update) {
+        a.ma_mean = h->f(mnorm(h, "a_mean")); a.ma_den = h->f(mnorm(h, "a_den"));
+        a.c_t = h->f("ws.c_t"); a.c_std = h->f("ws.c_std"); a.c_u = h->f("ws.c_u"); a.c_mask = h->f("ws.c_mask");
+    }
+    return a;
+}
+
+// actor.head as a launch of its own over rows [0, rows) of ws.Ha2, rows [cache0, rows) cached for the
+// backward; the segments are the caller's
+Launch actor_head_rows(sacx_handle* h, const float* part, int rows, int cache0) {
+    Launch L{};
+    L.kind = Launch::AHEAD;
+    L.name = "actor.head";
+    L.head = head_args(h, h->f("ws.Ha2"), part, true);
+    L.head.total_rows = rows;
+    L.head.cache_row0 = cache0;
+    L.head.cache_row1 = rows;
+    L.grid = (rows + 3) / 4;
+    L.flops = 2.0 * rows * h->H1 * h->Aout;
+    L.bytes = 4.0 * rows * (h->H1 + 6.0 * h->A);
+    return L;
+}
+
+// the SAC / SAC-EO update's: evaluate(sp) -> the target rows, evaluate(s) -> the policy rows, sample(s_e) ->
+// the world models' rows
+Launch actor_head_launch(sacx_handle* h, int slot, const float* part) {
+    const int B = h->B, A = h->A;
+    const std::string sl = "slot" + std::to_string(slot);
+    float* noise = h->f(sl + ".noise");
+    Launch L = actor_head_rows(h, part, h->Ra, B);
+    L.frees_slot = true;
+    HeadArgs& a = L.head;
+    a.nseg = h->cfg.use_expert ? 3 : 2;
+    a.seg[0] = {0, B, 0, 0, noise, h->f(sl + ".Xt"), h->f("ws.nlp_t")};
+    a.seg[1] = {B, 2 * B, 0, 0, noise + (size_t)B * A, h->f(sl + ".Xp"), h->f("ws.nlp_p")};
+    a.seg[2] = {2 * B, 2 * B + h->ne, 1, 0, noise + (size_t)2 * B * A, h->f(sl + ".Xm"), nullptr};
+    return L;
+}
+
+// alpha.head: evaluate(s) of the updated actor on the alpha rows (ws.Hl2), the per-workgroup partials of
+// sum(-nlp + H) for alpha.final
+Launch alpha_head_launch(sacx_handle* h, int slot, const float* part) {
+    const int B = h->B;
+    Launch L{};
+    L.kind = Launch::AHEAD;
+    L.name = "alpha.head";
+    HeadArgs& a = L.head;
+    a = head_args(h, h->f("ws.Hl2"), part, false);
+    a.nseg = 1;
+    a.seg[0] = {0, B, 0, 0, h->f("slot" + std::to_string(slot) + ".noise") + (size_t)(2 * B + h->ne) * h->A, nullptr, h->f("ws.nlp3")};
+    a.total_rows = B;
+    a.cache_row0 = 1 << 30;
+    a.alpha_mode = 1;
+    L.fin.red = h->f("red");
+    L.fin.target_entropy = h->cfg.target_entropy;
+    L.grid = (B + 3) / 4;
+    L.flops = 2.0 * B * h->H1 * h->Aout;
+    L.bytes = 4.0 * B * h->H1;
+    return L;
+}
+
+// The shapes the two partial folds have kernels for (the head's partial dots out of the actor's last layer;
+// the head backward as actor.bwd1's prologue, from partial action gradients).  A caller adds its own gating.
+bool head_part_shape(const sacx_handle* h) { return h->Aout <= 8 && h->H1 <= 256 && h->H1 % 64 == 0; }
+bool fold_hbw_shape(const sacx_handle* h) {
+    const bool critics = !h->bc, models = h->cfg.use_expert != 0;   // whose layer 0 writes the partials
+    return h->Aout <= 8 && h->H1 <= 256 && h->H1 % 16 == 0 && (!critics || (h->Hc0 <= 256 && h->Hc0 % 64 == 0)) &&
+           (!models || (h->Hm0 <= 512 && h->Hm0 % 64 == 0));
+}
+
+// A forward problem of the actor's last hidden layer also writes the head's dots with W3 as per-column-tile
+// partials (GR_HEAD_PART), from `ppart` on
+void head_part_dots(sacx_handle* h, GemmProb& p, float* ppart) {
+    p.pw = h->f(actor_head_name(h)); p.pw_ld = 1; p.pw_cs = h->Aout; p.pw_n = h->Aout;   // W3[n][o] at n * Aout + o
+    p.ppart = ppart;
+}
+
+// A dX problem down to the layer-0 output of a net on [s | a] writes per-tile partial action gradients
+// instead of C (read by no one else): its tiles' products with the action rows of that layer's W_ext [. x H0]
+void part_action_grad(sacx_handle* h, GemmProb& p, const float* W0, int H0, float* ppart) {
+    p.pw = W0 + (size_t)h->S * H0;
+    p.pw_ld = H0; p.pw_cs = 1; p.pw_n = h->A;
+    p.ppart = ppart;
+    p.C = nullptr;
+}
+
+// actor.head.bwd on the row kernel (k_actor_bwd): the action gradients of the B policy rows through layer 0
+// of q0 / q1 and of the expert rows through the world models', the tanh-Gaussian backward, the delta at the
+// actor's last hidden layer.  gpol: the policy rows' output gradients where ws.Dp1 is the unscaled delta
+// (the fused plan's linearity), null where it is the loss-scaled one.  B = 0: BC, the expert rows alone
+Launch actor_head_bwd_launch(sacx_handle* h, int B, bool expert, const float* gpol) {
+    const NetDims& na = h->nd[0];
+    const int ne = h->ne, rows = B + ne, A = h->A, H1 = h->H1, Hm0 = h->Hm0, Hc0 = B ? h->Hc0 : 0, Da = na.D();
+    const int nm = expert_split(h).nm;
+    Launch L{};
+    L.kind = Launch::ABWD;
+    L.name = "actor.head.bwd";
+    ActorBwdArgs& b = L.ab;
+    b.B = B; b.ne = ne; b.S = h->S; b.A = A; b.Aout = h->Aout; b.H0 = Hc0; b.H1 = H1; b.Hm0 = Hm0;   // Dp1 / Wq1: critic
+    b.per_state_std = h->cfg.per_state_std; b.lim = h->cfg.act_limit;
+    if (B) { b.Dp1 = h->f("ws.Dp1"); b.Wq1[0] = h->f("q0.l0"); b.Wq1[1] = h->f("q1.l0"); }
+    b.Dm1 = h->f("ws.Dm1");
+    if (expert) { b.Wm1[0] = h->f("m0.l0"); b.Wm1[1] = h->f(nm > 1 ? "m1.l0" : "m0.l0"); }
+    b.a_den = h->f("norm.a_den"); b.ma_den = h->f(mnorm(h, "a_den")); b.alpha = h->f("alpha"); b.ctl = h->ctl();
+    b.use_expert = expert;
+    b.c_t = h->f("ws.c_t"); b.c_std = h->f("ws.c_std"); b.c_u = h->f("ws.c_u"); b.c_mask = h->f("ws.c_mask");
+    b.W3a = h->f(actor_head_name(h)); b.Ha2 = h->f("ws.Ha2") + (size_t)B * H1;
+    b.act = (Da == 1 && h->ln) ? ACT_TANH : na.act[Da - 1];   // layer norm: tanh' at the norm's output
+    b.Da3 = h->f("ws.Da3"); b.Da2 = h->f("ws.Da2"); b.E = h->f("ws.E");
+    b.gpol = gpol;
+    L.grid = (rows + 3) / 4;
+    L.flops = 2.0 * B * 2 * Hc0 * A + 2.0 * ne * Hm0 * A + 2.0 * rows * H1 * h->Aout;
+    L.bytes = 4.0 * (2.0 * B * Hc0 + ne * Hm0 + 2.0 * rows * H1);
+    return L;
+}
+
+// actor.head.bwd as the tile prologue of actor.bwd1 (two-layer actors): Da3 from the per-tile partial action
+// gradients (part_action_grad: pi.q.bwd1's for the B policy rows, model.bwd1's for the expert rows), Da2
+// generated on load (an MFMA from Da3 and W3a) and stored by column tile 0.  Appends the launch and returns
+// it: the flops / bytes of the prologue are the caller's
+Launch& head_bwd_fold(sacx_handle* h, std::vector<Launch>& plan, int B, bool expert, bool record_probs) {
+    const int ne = h->ne, rows = B + ne, H0 = h->H0, H1 = h->H1;
+    GemmProb p = prob_dx(h->f("ws.Ha2") + (size_t)B * H1, rows, H1, h->f("actor.l1"), H0, h->f("ws.Ha1") + (size_t)B * H0,
+                         h->f("ws.Da1"), h->ln ? ACT_TANH : h->aact[0]);
+    p.wgen = h->f("actor.l2");               // W3a [(H1+1) x Aout]
+    p.gen_act = h->aact[1];                  // act'(Ha2)
+    p.hbw = 1;
+    add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
+    Launch& L = plan.back();
+    set_rows(L, GR_HEAD_BWD);
+    HeadBwdArgs& b = L.gemm.hbw;
+    b.B = B; b.A = h->A; b.Aout = h->Aout; b.per_state_std = h->cfg.per_state_std; b.tq = B ? (h->Hc0 + 15) / 16 : 0;
+    b.lim = h->cfg.act_limit; b.part = B ? h->f("ws.apart") : nullptr; b.gpol = B ? h->f("ws.gp") : nullptr;
+    b.a_den = h->f("norm.a_den"); b.ma_den = h->f(mnorm(h, "a_den")); b.alpha = h->f("alpha");
+    b.c_t = h->f("ws.c_t"); b.c_std = h->f("ws.c_std"); b.c_u = h->f("ws.c_u"); b.c_mask = h->f("ws.c_mask");
+    b.Da3 = h->f("ws.Da3"); b.E = h->f("ws.E"); b.Da2 = h->f("ws.Da2");
+    b.ne = ne; b.tqm = (h->Hm0 + 15) / 16; b.mpart = expert ? h->f("ws.mpart") : nullptr; b.ctl = expert ? h->ctl() : nullptr;
+    return L;
+}
+
+// ---------------------------------------------------------------- the fused update plan
+// Two hidden layers per net (any other depth: build_plan_generic).  The shared builders give the problems
+// and the row kernels' arguments; what makes this the fused plan stays here: the head folded into q.fwd0,
+// the policy rows on critic.adam, model.head merged into pi.q.fwd*, the linearity fusion of the critic and
+// policy backward, fuse_fwd2 and xbf_wire.
+void build_plan(sacx_handle* h, int slot, bool record_probs) {
+    std::vector<Launch>& plan = h->plan[slot];
+    plan.clear();
+    h->probs_cursor = 0;
+    const int S = h->S, A = h->A, H1 = h->H1, B = h->B, Aout = h->Aout, Rb = h->Rb;
+    const int Hm0 = h->Hm0, Hc0 = h->Hc0, Hc1 = h->Hc1;   // the critics' hidden sizes (--critic_layers; H0 / H1: the actor's)
+    // expert rows of world model k: [k * half, (k + 1) * half) with 2 or more models (the expert term
+    // takes models 0 and 1, SAC_expert.py:325-326), all with one
+    const ExpertSplit es = expert_split(h);
+    const int nm = es.nm, half = es.half;
+    const int ldS = h->ldS;
+    const int c1 = h->cact[1];
+    const bool eo = h->cfg.use_expert != 0;
+    const std::string sl = "slot" + std::to_string(slot);
+    float* noise = h->f(sl + ".noise");
+    float* noise_t = noise;
+    float* noise_pi = noise + (size_t)B * A;
+    float* noise_e = noise + (size_t)2 * B * A;
+    auto W = [&](const std::string& n) { return h->f(n); };
+    float *Xa = W(sl + ".Xa"), *Xq = W(sl + ".Xq"), *Xt = W(sl + ".Xt"), *Xp = W(sl + ".Xp"), *Xm = W(sl + ".Xm");
+    float *r_in = W(sl + ".r"), *d_in = W(sl + ".d"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
+    float *Ha2 = W("ws.Ha2"), *Hq2 = W("ws.Hq2"), *Hp2 = W("ws.Hp2");
+    const char* qn[4] = {"t0", "t1", "q0", "q1"};
+    auto qk = [](int k) { return "q" + std::to_string(k); };
+
+    plan_inputs(h, plan, slot);
+    // the two forward layers of a net as two launches (a fused two-layer tile recomputing
+    // layer 0 per column tile measured slower once the alpha branch and the heads share
+    // launches: 12.06k vs 12.33k updates/s, DESIGN.md section 6)
+    auto fwd_pair = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
+        add_gemm(h, plan, name + "0", p0, record_probs);
+        add_gemm(h, plan, name + "1", p1, record_probs);
+    };
+    // the same pair as ONE k_fwd2 launch where it qualifies (fuse_fwd2), else the two launches
+    auto fwd_pair2 = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
+        fwd_pair(name, p0, p1);
+        if (h->fwd2) fuse_fwd2(h, plan, name + "01");
+    };
+    // ---- actor forward on [sp ; s ; s_e]
+    const int Ra4 = (h->Ra + 3) & ~3;       // first row of the alpha rows (ws.Hl1 / ws.Hl2 alias Ha1 / Ha2)
+    // actor.fwd1 writes the head's Ha2 . W3 as per-column-tile partials (GR_HEAD_PART), so the head
+    // rows and the target-tile prologues sum 16 values per output instead of re-reading Ha2
+    // rows.  SACX_HEAD_PART=0 keeps the row dots (A/B measurement).
+    const char* hpe = std::getenv("SACX_HEAD_PART");
+    const int tqh = (H1 + 15) / 16;
+    const bool head_part = head_part_shape(h) && (hpe ? std::atoi(hpe) != 0 : h->tile32_plan == 0);
+    // the partials of the head rows from row r0 of Ha2 on
+    auto hpart = [&](int r0) { return head_part ? W("ws.hpart") + (size_t)r0 * Aout * tqh : nullptr; };
+    // the actor's two layers on a pass's rows (--actor_layer_norm: k_ln behind layer 0), layer 1 with the
+    // head partials, the pair as one k_fwd2 launch where it qualifies
+    auto actor_fwd = [&](const ActorPass& c, const std::string& name, const std::string& ln_name) {
+        actor_fwd_chain(h, plan, c, name, ln_name, record_probs);
+        if (head_part) {
+            head_part_dots(h, plan.back().gemm.probs[0], hpart(c.hrow0));
+            set_rows(plan.back(), GR_HEAD_PART);
+        }
+        if (!h->ln && h->fwd2) fuse_fwd2(h, plan, name + "01");
+    };
+    actor_fwd(actor_pass_ws(h, Xa, h->Ra, 0, h->Ra), "actor.fwd", "actor.ln");
+    // actor.head folded into q.fwd0 (plain SAC): the target tiles compute their rows' actions
+    // in a prologue, the policy rows (and the previous update's alpha rows) run as extra
+    // workgroups of the same launch.  SACX_FUSE_HEAD=0 keeps the separate launch.
+    const char* fh = std::getenv("SACX_FUSE_HEAD");
+    // Packed seeds (>= 4) keep the separate launch: the prologue recomputes each tile's 16 rows
+    // once per column tile, which a full GPU of seeds pays for (measured 34.3k vs 31.6k updates/s
+    // at 8 seeds); one seed gains the launch it saves.
+    // SAC-EO as well: the expert rows (sample -> the world models' inputs Xm) ride as row
+    // workgroups of q.fwd0, and the models' forward shifts one launch later (layer 0 in q.fwd1,
+    // layer 1 in pi.q.fwd0, the MSE head in pi.q.fwd1)
+    const bool fuse_head = Aout <= 16 && S + A <= 64 && H1 % 16 == 0 && H1 <= 512 &&
+                           (fh ? std::atoi(fh) != 0 : h->plan_seeds < 4);
+    // actor.head.bwd folded into actor.bwd1 (plain SAC; the expert rows' model gradients keep
+    // the row kernel): pi.q.bwd1 writes per-tile partial action gradients, actor.bwd1's tiles
+    // finish them.  SACX_FOLD_HBW=0 keeps the separate launch (A/B measurement).
+    const char* fhb = std::getenv("SACX_FOLD_HBW");
+    const int tq = (Hc0 + 15) / 16;        // action-gradient partials per row (the critics' layer-0 tiles)
+    // The folded launch itself keeps 16x16 tiles (its prologue and generated A operand); the
+    // partial-writing launches may take 32x32 tiles.  On 32x32 (packed) plans both folds are off
+    // by default: there the launches are bound by workgroup residency, not by their number, and
+    // the folds' extra work loses (HC 8 seeds, A/B x2: both on 42.3k, hbw fold only 43.4k, head
+    // partials only 43.1k, both off 43.9k updates/s; tools/pk_ab.sh).
+    const bool fold_hbw = fold_hbw_shape(h) && (fhb ? std::atoi(fhb) != 0 : h->tile32_plan == 0);
+    // ---- actor head
+    HeadArgs head_fused{};
+    if (fuse_head) {
+        HeadArgs& a = head_fused;
+        a = head_args(h, Ha2, hpart(0), true);
+        // q.fwd0 carries the target rows (tile prologues) and, folded, the previous update's
+        // alpha rows; the policy rows ride as extra workgroups of critic.adam (policy_head)
+        a.nseg = 1;
+        a.seg[0] = {0, B, 0, 0, noise_t, nullptr, W("ws.nlp_t")};
+        // total_rows = Ra: merged_body appends the previous update's alpha rows at round4(Ra),
+        // where their layer-2 outputs live (ws.Hl2 aliases Ha2 from row round4(Ra))
+        a.total_rows = h->Ra;
+        a.cache_row0 = 1 << 30;             // no backward cache from these rows (target, alpha)
+        a.cache_row1 = 1 << 30;
+        if (eo) {                           // SAC-EO expert rows: sample() into Xm, cached
+            a.nseg = 2;
+            a.seg[1] = {2 * B, 2 * B + h->ne, 1, 0, noise_e, Xm, nullptr};
+            a.cache_row0 = B;
+            a.cache_row1 = h->Ra;
+        }
+    } else {
+        plan.push_back(actor_head_launch(h, slot, hpart(0)));
+    }
+    // ---- target / critic / model forward
+    {
+        std::vector<GemmProb> p0, p1;
+        for (int k = 0; k < 4; ++k) {
+            p0.push_back(critic_fwd_prob(h, qn[k], k < 2 ? Xt : Xq, "ws.Hq", k, 0));
+            p1.push_back(critic_fwd_prob(h, qn[k], nullptr, "ws.Hq", k, 1));
+        }
+        if (fuse_head) {
+            p0[0].headp = p0[1].headp = 1;  // the target tiles' prologue
+            add_gemm(h, plan, "q.fwd0+actor.head", p0, record_probs);
+            Launch& L = plan.back();
+            set_rows(L, GR_ACTOR_HEAD);
+            L.gemm.head = head_fused;
+            L.gemm.head_block0 = eo ? (2 * B) / 4 : ((h->Ra + 3) & ~3) / 4;
+            L.gemm.row_blocks = eo ? (h->Ra + 3) / 4 - (2 * B) / 4 : 0;   // + the alpha rows (merged_body)
+            L.grid += L.gemm.row_blocks;
+            L.flops += 2.0 * B * H1 * Aout;
+            L.bytes += 4.0 * B * (H1 + 6.0 * A);
+            L.frees_slot = true;
+            // the models' layer 0 on Xm (written by the rows above)
+            for (int k = 0; eo && k < nm; ++k) p1.push_back(model_fwd_prob(h, Xm, k, 0));
+            add_gemm(h, plan, "q.fwd1", p1, record_probs);
+            if (h->fwd2 && !eo) fuse_fwd2(h, plan, "q.fwd01+actor.head");
+        } else {
+            for (int k = 0; eo && k < nm; ++k) {
+                p0.push_back(model_fwd_prob(h, Xm, k, 0));
+                p1.push_back(model_fwd_prob(h, Xm, k, 1));
+            }
+            fwd_pair("q.fwd", p0, p1);
+        }
+    }
+    // ---- critic backward.  By linearity Dq1 = g (.) M1 with M1 = ((w3 (.) act'(Hq2)) Wq1^T) (.) act'(Hq1)
+    // independent of the per-row loss gradient g, so the dX GEMM (A generated from Hq2 and w3)
+    // shares one launch with the q.head rows (target, g, loss rows, Dq2, expert MSE + Dm2), and
+    // critic.adam applies g to layer 0 (row-scaled B).
+    {
+        std::vector<GemmProb> pb;
+        for (int k = 0; k < 2; ++k) {
+            GemmProb p = critic_dx_prob(h, qk(k), "ws.Hq", 2 + k, "ws.Dq", k, 1, true);
+            p.wgen = W(qk(k) + ".l2");         // w3 column of W3_ext
+            p.gen_act = c1;                    // act'(Hq2); the epilogue takes act'(Hq1)
+            pb.push_back(p);
+        }
+        add_gemm(h, plan, "q.head+critic.bwd1", pb, record_probs);
+        Launch& L = plan.back();
+        set_rows(L, GR_QHEAD);
+        L.gemm.row_blocks = (B + 3) / 4;
+        L.gemm.qh = q_head_args(h, 0, Hq2, W("ws.Dq2"), r_in, d_in);
+        L.grid += L.gemm.row_blocks;
+        L.flops += 2.0 * B * Hc1 * 4 + 2.0 * B * Hc1 * 2;
+        L.bytes += 4.0 * (4.0 * B * Hc1 + 2.0 * B * Hc1 * 2);
+        std::vector<GemmProb> pw;
+        for (int k = 0; k < 2; ++k)
+            for (int i = 0; i <= 2; ++i) {
+                GemmProb p = critic_dw_prob(h, k, Xq, i);
+                if (i == 0) p.bscale = W("ws.gq") + (size_t)k * B;   // Dq1 = g (.) M1
+                pw.push_back(p);
+            }
+        add_gemm(h, plan, "critic.adam", pw, record_probs, !fuse_head);
+        if (fuse_head) {                    // the policy rows of actor.head (read from pi.q.fwd0 on)
+            Launch& L = plan.back();
+            HeadArgs a = head_fused;
+            a.nseg = 1;
+            a.seg[0] = {B, 2 * B, 0, 0, noise_pi, Xp, W("ws.nlp_p")};
+            a.total_rows = 2 * B;
+            a.cache_row0 = B;
+            a.cache_row1 = h->Ra;
+            L.name += "+actor.head";
+            set_rows(L, GR_POLICY_HEAD);
+            L.gemm.head = a;
+            L.gemm.head_block0 = B / 4;
+            L.gemm.row_blocks = (2 * B + 3) / 4 - B / 4;
+            L.grid += L.gemm.row_blocks;
+            L.flops += 2.0 * B * H1 * Aout;
+            L.bytes += 4.0 * B * (H1 + 6.0 * A);
+        }
+        if (h->dp_ranks > 0) dp_split_adam(h, plan, "q0.l0", "q1.l2", "t0.l0", GRP_Q);
+    }
+    // ---- policy loss through the updated critics: the same linearity; pi.q.head's rows
+    // (min, tie split, loss rows, g0 / g1) share the unscaled dX launch, actor.head.bwd applies
+    // g0 / g1.  The SAC-EO world-model dX (needs q.head's Dm2) rides in the same launch.
+    {
+        std::vector<GemmProb> p0, p1;
+        for (int k = 0; k < 2; ++k) {
+            p0.push_back(critic_fwd_prob(h, qk(k), Xp, "ws.Hp", k, 0));
+            p1.push_back(critic_fwd_prob(h, qk(k), nullptr, "ws.Hp", k, 1));
+        }
+        // the models' layer 1 on Hm1 (from q.fwd1)
+        for (int k = 0; eo && fuse_head && k < nm; ++k) p0.push_back(model_fwd_prob(h, Xm, k, 1));
+        if (eo) fwd_pair("pi.q.fwd", p0, p1);
+        else fwd_pair2("pi.q.fwd", p0, p1);
+        if (eo) {
+            // SAC-EO: world-model layer 2 on the expert rows + MSE epilogue (needs Hm2 from q.fwd1),
+            // riding in the pi.q.fwd0 launch (or, with the fused head, in pi.q.fwd1 = plan.back(): Hm2
+            // comes from pi.q.fwd0)
+            Launch& F0 = plan[plan.size() - (fuse_head ? 1 : 2)];
+            const std::vector<GemmProb> pm = model_head_probs(h, MSE_EXPERT, se_raw, spe_raw);
+            std::vector<Launch> one;
+            add_gemm(h, one, "model.head", pm, false);
+            h->probs_cursor -= (int)pm.size();
+            if (!merge_gemm(F0.gemm, one[0].gemm)) { fprintf(stderr, "sacx: model.head merge\n"); abort(); }
+            F0.name += "+model.head";
+            F0.grid = F0.gemm.total_tiles;
+            F0.flops += one[0].flops;
+            F0.bytes += one[0].bytes;
+        }
+        std::vector<GemmProb> pb;
+        for (int k = 0; k < 2; ++k) {
+            GemmProb p = critic_dx_prob(h, qk(k), "ws.Hp", k, "ws.Dp", k, 1, true);
+            p.wgen = W(qk(k) + ".l2");
+            p.gen_act = c1;
+            // partial action gradients instead of Dp1 (read by no one else)
+            if (fold_hbw) part_action_grad(h, p, W(qk(k) + ".l0"), Hc0, W("ws.apart") + (size_t)k * B * tq * A);
+            pb.push_back(p);
+        }
+        if (eo) {                            // Dm2 = dout . Wm2[:, :S]^T (.) act'(Hm2)
+            const std::vector<GemmProb> pd = model_bwd_probs(h, 2);
+            pb.insert(pb.end(), pd.begin(), pd.end());
+        }
+        add_gemm(h, plan, "pi.q.head+pi.q.bwd1", pb, record_probs);
+        {
+            Launch& L = plan.back();
+            set_rows(L, GR_PIQHEAD);
+            L.gemm.row_blocks = (B + 3) / 4;
+            L.gemm.qh = q_head_args(h, 1, Hp2, nullptr, nullptr, nullptr);
+            L.grid += L.gemm.row_blocks;
+            L.flops += 2.0 * B * Hc1 * 2 * 2;
+            L.bytes += 4.0 * (2.0 * B * Hc1 * 2);
+        }
+        if (eo) {                            // Dm1 = Dm2 . Wm1^T (.) act'(Hm1), for actor.head.bwd
+            std::vector<GemmProb> pd = model_bwd_probs(h, 1);
+            const int tqm = (Hm0 + 15) / 16;
+            // partial action gradients of the expert rows instead of Dm1
+            for (int k = 0; fold_hbw && k < nm; ++k)
+                part_action_grad(h, pd[k], W("m" + std::to_string(k) + ".l0"), Hm0, W("ws.mpart") + (size_t)k * half * A * tqm);
+            add_gemm(h, plan, "model.bwd1", pd, record_probs);
+            if (fold_hbw) set_rows(plan.back(), GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
+        }
+    }
+    // ---- actor backward: the policy and expert rows, rows [B, B + Rb) of Xa and of the hidden buffers
+    {
+        if (fold_hbw) {
+            // actor.head.bwd as the tile prologue of actor.bwd1, from the partials of pi.q.bwd1 / model.bwd1
+            Launch& L = head_bwd_fold(h, plan, B, eo, record_probs);
+            L.flops += 2.0 * B * 2 * Hc0 * A + 2.0 * Rb * H1 * Aout;
+            L.bytes += 4.0 * (2.0 * B * tq * A + 2.0 * Rb * H1);
+        } else {
+            plan.push_back(actor_head_bwd_launch(h, B, eo, W("ws.gp")));
+        }
+        // (the folded head backward is layer 1's dX already: the norm's backward alone follows it)
+        const ActorPass bw = actor_pass_ws(h, Xa + (size_t)B * ldS, Rb, B, h->Ra);
+        actor_bwd_chain(h, plan, bw, fold_hbw ? 0 : 1, record_probs);
+        add_gemm(h, plan, "actor.adam", actor_dw_probs(h, bw), record_probs);
+        if (h->dp_ranks > 0) dp_split_adam(h, plan, "actor.l0", "actor.logstd", "", GRP_PI);
+    }
+    // ---- alpha: updated actor on s, evaluate, Adam on alpha, statistics
+    const size_t alpha_first = plan.size();
+    // the alpha forward is folded into the next update's actor forward (merged_body): the same fusion as
+    // the actor pair's, so merged_body folds one k_fwd2 launch into the other
+    actor_fwd(actor_pass_ws(h, Xa + (size_t)B * ldS, B, Ra4, h->Ra), "alpha.fwd", "alpha.ln");
+    plan.push_back(alpha_head_launch(h, slot, hpart(Ra4)));
+    plan_alpha_final(h, plan, nm);
+    // alpha.fwd .. alpha.final only feed the next update's q.head
+    for (size_t i = alpha_first; i < plan.size(); ++i) plan[i].alpha_branch = true;
+    xbf_wire(h, plan, slot);
+    for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
+}
+
 // ---------------------------------------------------------------- the generic update plan
 // Nets of any depth (create_nn's layers list, nn_utils.py:100-138; SACX_GENERIC=1 also at two layers,
 // the parity check of this plan against the fused one): the update of build_plan in the reference's
@@ -2116,21 +2086,14 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
     h->probs_cursor = 0;
-    const int S = h->S, A = h->A, H1 = h->H1, B = h->B, ne = h->ne, Aout = h->Aout;
-    const int Hc1 = h->Hc1;
+    const int B = h->B, Hc1 = h->Hc1;
     const int nm = expert_split(h).nm;      // the expert term's models
-    const int ldS = h->ldS, ldQ = h->ldQ, Rb = h->Rb;
+    const int ldS = h->ldS, Rb = h->Rb;
     const bool eo = h->cfg.use_expert != 0;
-    const NetDims &na = h->nd[0], &nc = h->nd[1], &nmd = h->nd[2];
-    const int Da = na.D(), Dc = nc.D(), Dm = eo ? nmd.D() : 0;
+    const int Da = h->nd[0].D(), Dc = h->nd[1].D(), Dm = eo ? h->nd[2].D() : 0;
     const std::string sl = "slot" + std::to_string(slot);
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = layer_name;
-    float* noise = h->f(sl + ".noise");
-    float* noise_t = noise;
-    float* noise_pi = noise + (size_t)B * A;
-    float* noise_e = noise + (size_t)2 * B * A;
-    float* noise_al = noise + (size_t)(2 * B + ne) * A;
     float *Xa = W(sl + ".Xa"), *Xq = W(sl + ".Xq"), *Xt = W(sl + ".Xt"), *Xp = W(sl + ".Xp"), *Xm = W(sl + ".Xm");
     float *r_in = W(sl + ".r"), *d_in = W(sl + ".d"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
     const char* qn[4] = {"t0", "t1", "q0", "q1"};
@@ -2139,45 +2102,14 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     plan_inputs(h, plan, slot);
     // ---- actor forward on all Ra rows of Xa (the layer-norm cache holds them all)
     actor_fwd_chain(h, plan, actor_pass_ws(h, Xa, h->Ra, 0, h->Ra), "actor.fwd", "actor.ln", record_probs);
-    float* Ha_last = W("ws.Ha2");
-    auto head_base = [&](HeadArgs& a, const float* H2) {
-        a.H2 = H2; a.ldh = H1; a.W3 = W(L_("actor", Da)); a.logstd = W("actor.logstd");
-        a.part = nullptr; a.tq = (H1 + 15) / 16;
-        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
-        a.ma_mean = W(mnorm(h, "a_mean")); a.ma_den = W(mnorm(h, "a_den"));
-    };
-    {   // ---- actor head: evaluate(sp) -> target rows, evaluate(s) -> policy rows, sample(s_e) -> model rows
-        Launch L{};
-        L.kind = Launch::AHEAD;
-        L.name = "actor.head";
-        L.frees_slot = true;
-        HeadArgs& a = L.head;
-        head_base(a, Ha_last);
-        a.nseg = eo ? 3 : 2;
-        a.seg[0] = {0, B, 0, 0, noise_t, Xt, W("ws.nlp_t")};
-        a.seg[1] = {B, 2 * B, 0, 0, noise_pi, Xp, W("ws.nlp_p")};
-        a.seg[2] = {2 * B, 2 * B + ne, 1, 0, noise_e, Xm, nullptr};
-        a.total_rows = h->Ra;
-        a.cache_row0 = B;
-        a.cache_row1 = h->Ra;
-        a.c_t = W("ws.c_t"); a.c_std = W("ws.c_std"); a.c_u = W("ws.c_u"); a.c_mask = W("ws.c_mask");
-        a.alpha_mode = 0;
-        L.grid = (h->Ra + 3) / 4;
-        L.flops = 2.0 * h->Ra * H1 * Aout;
-        L.bytes = 4.0 * h->Ra * (H1 + 6.0 * A);
-        plan.push_back(L);
-    }
+    // ---- actor head: evaluate(sp) -> target rows, evaluate(s) -> policy rows, sample(s_e) -> model rows
+    plan.push_back(actor_head_launch(h, slot, nullptr));
     // ---- target / critic forward (t0, t1 on [sp | pi(sp)], q0, q1 on [s | a]; the world models' hidden
     // layers on the expert rows [s_e | pi(s_e)]), one launch per depth level
     for (int i = 0; i < std::max(Dc, Dm); ++i) {
         std::vector<GemmProb> ps;
         if (i < Dc)
-            for (int k = 0; k < 4; ++k) {
-                const float* in = i == 0 ? (k < 2 ? Xt : Xq) : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
-                ps.push_back(prob_fwd(in, i == 0 ? ldQ : nc.h[i - 1], B, i == 0 ? S + A : nc.h[i - 1], W(L_(qn[k], i)),
-                                      nc.h[i], chain_buf(h, "ws.Hq", i, Dc) + (size_t)k * B * nc.h[i], nc.act[i]));
-            }
+            for (int k = 0; k < 4; ++k) ps.push_back(critic_fwd_prob(h, qn[k], k < 2 ? Xt : Xq, "ws.Hq", k, i));
         if (i < Dm)
             for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
         add_gemm(h, plan, "q.fwd" + std::to_string(i), ps, record_probs);
@@ -2188,13 +2120,7 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
         Launch L{};
         L.kind = Launch::QHEAD;
         L.name = "q.head";
-        QHeadArgs& q = L.qh;
-        q.mode = 0; q.B = B; q.H1 = Hc1; q.H2 = W("ws.Hq2");
-        for (int k = 0; k < 4; ++k) q.W3[k] = W(L_(qn[k], Dc));
-        q.act = nc.act[Dc - 1]; q.D2 = W("ws.Dq2"); q.g = W("ws.gq"); q.loss_rows = W("ws.lq");
-        q.alpha = W("alpha"); q.nlp = W("ws.nlp_t"); q.r = r_in; q.d = d_in;
-        q.gamma = h->cfg.gamma; q.ret_den = W("norm.ret_den"); q.w_sac = 1.f;
-        q.ne = 0; q.ctl = h->ctl();
+        L.qh = q_head_args(h, 0, W("ws.Hq2"), W("ws.Dq2"), r_in, d_in);
         L.grid = (B + 3) / 4;
         L.flops = 2.0 * B * Hc1 * 4;
         L.bytes = 4.0 * (4.0 * B * Hc1 + 2.0 * B * Hc1);
@@ -2203,51 +2129,27 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     // ---- critic backward (dX down to layer 0's output), then dW + Keras Adam + Polyak into t0 / t1
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
-        for (int k = 0; k < 2; ++k)
-            pb.push_back(prob_dx(chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_(qn[2 + k], i)), nc.h[i - 1],
-                                 chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1],
-                                 chain_buf(h, "ws.Dq", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
+        for (int k = 0; k < 2; ++k) pb.push_back(critic_dx_prob(h, qn[2 + k], "ws.Hq", 2 + k, "ws.Dq", k, i));
         add_gemm(h, plan, "critic.bwd" + std::to_string(i), pb, record_probs);
     }
     {
         std::vector<GemmProb> pw;
-        for (int k = 0; k < 2; ++k) {
-            const std::string n = "q" + std::to_string(k), t = "t" + std::to_string(k);
-            for (int i = 0; i < Dc; ++i) {
-                const float* X = i == 0 ? Xq : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1];
-                const int K = i == 0 ? S + A : nc.h[i - 1];
-                pw.push_back(prob_dw(X, i == 0 ? ldQ : K, K, B, chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], nc.h[i],
-                                     W(L_(n, i)), W(L_(t, i)), GRP_Q));
-            }
-            pw.push_back(prob_dw(W("ws.Hq2") + (size_t)(2 + k) * B * Hc1, Hc1, Hc1, B, W("ws.gq") + (size_t)k * B, 1,
-                                 W(L_(n, Dc)), W(L_(t, Dc)), GRP_Q));
-        }
+        for (int k = 0; k < 2; ++k)
+            for (int i = 0; i <= Dc; ++i) pw.push_back(critic_dw_prob(h, k, Xq, i));
         const int n = add_gemm_split(h, plan, "critic.adam", pw, record_probs);
         if (h->dp_ranks > 0) dp_split_adam(h, plan, "q0.l0", L_("q1", Dc), "t0.l0", GRP_Q, n);
     }
     // ---- policy loss through the updated critics
     for (int i = 0; i < Dc; ++i) {
         std::vector<GemmProb> ps;
-        for (int k = 0; k < 2; ++k) {
-            const float* in = i == 0 ? Xp : chain_buf(h, "ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1];
-            ps.push_back(prob_fwd(in, i == 0 ? ldQ : nc.h[i - 1], B, i == 0 ? S + A : nc.h[i - 1],
-                                  W(L_("q" + std::to_string(k), i)), nc.h[i], chain_buf(h, "ws.Hp", i, Dc) + (size_t)k * B * nc.h[i],
-                                  nc.act[i]));
-        }
+        for (int k = 0; k < 2; ++k) ps.push_back(critic_fwd_prob(h, qn[2 + k], Xp, "ws.Hp", k, i));
         add_gemm(h, plan, "pi.q.fwd" + std::to_string(i), ps, record_probs);
     }
     {   // min, tie split, policy loss rows, the delta at the critics' last hidden layer (x d p / d Q_k)
         Launch L{};
         L.kind = Launch::QHEAD;
         L.name = "pi.q.head";
-        QHeadArgs& q = L.qh;
-        q.mode = 1; q.B = B; q.H1 = Hc1; q.H2 = W("ws.Hp2");
-        q.W3[0] = W(L_("q0", Dc)); q.W3[1] = W(L_("q1", Dc)); q.W3[2] = nullptr; q.W3[3] = nullptr;
-        q.act = nc.act[Dc - 1]; q.D2 = W("ws.Dp2"); q.g = W("ws.gp"); q.loss_rows = W("ws.lp");
-        q.alpha = W("alpha"); q.nlp = W("ws.nlp_p");
-        q.w_sac = eo ? (float)(1.0 - (double)h->cfg.epsilon) : 1.f;
-        q.ret_den = W("norm.ret_den");
-        q.ne = 0; q.ctl = h->ctl();
+        L.qh = q_head_args(h, 1, W("ws.Hp2"), W("ws.Dp2"), nullptr, nullptr);
         L.grid = (B + 3) / 4;
         L.flops = 2.0 * B * Hc1 * 2;
         L.bytes = 4.0 * (4.0 * B * Hc1);
@@ -2255,37 +2157,14 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     }
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
-        for (int k = 0; k < 2; ++k)
-            pb.push_back(prob_dx(chain_buf(h, "ws.Dp", i, Dc) + (size_t)k * B * nc.h[i], B, nc.h[i], W(L_("q" + std::to_string(k), i)),
-                                 nc.h[i - 1], chain_buf(h, "ws.Hp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1],
-                                 chain_buf(h, "ws.Dp", i - 1, Dc) + (size_t)k * B * nc.h[i - 1], nc.act[i - 1]));
+        for (int k = 0; k < 2; ++k) pb.push_back(critic_dx_prob(h, qn[2 + k], "ws.Hp", k, "ws.Dp", k, i));
         add_gemm(h, plan, "pi.q.bwd" + std::to_string(i), pb, record_probs);
     }
     if (eo)     // the world models' backward to their layer-0 output (the expert rows' action gradient)
         for (int i = Dm; i >= 1; --i) add_gemm(h, plan, "model.bwd" + std::to_string(i), model_bwd_probs(h, i), record_probs);
     // ---- actor backward: action gradients -> tanh-Gaussian backward -> the delta at the last hidden
     // layer (k_actor_bwd, from the loss-scaled deltas: gpol = null), dX to layer 0, dW + Adam
-    {
-        Launch L{};
-        L.kind = Launch::ABWD;
-        L.name = "actor.head.bwd";
-        ActorBwdArgs& b = L.ab;
-        b.B = B; b.ne = ne; b.S = S; b.A = A; b.Aout = Aout; b.H0 = h->Hc0; b.H1 = H1; b.Hm0 = h->Hm0;
-        b.per_state_std = h->cfg.per_state_std; b.lim = h->cfg.act_limit;
-        b.Dp1 = W("ws.Dp1"); b.Wq1[0] = W("q0.l0"); b.Wq1[1] = W("q1.l0");
-        b.Dm1 = W("ws.Dm1"); b.Wm1[0] = eo ? W("m0.l0") : nullptr; b.Wm1[1] = eo ? W(nm > 1 ? "m1.l0" : "m0.l0") : nullptr;
-        b.a_den = W("norm.a_den"); b.ma_den = W(mnorm(h, "a_den")); b.alpha = W("alpha"); b.ctl = h->ctl();
-        b.use_expert = eo;
-        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
-        b.W3a = W(L_("actor", Da)); b.Ha2 = Ha_last + (size_t)B * H1;
-        b.act = (Da == 1 && h->ln) ? ACT_TANH : na.act[Da - 1];   // layer norm: tanh' at the norm's output
-        b.Da3 = W("ws.Da3"); b.Da2 = W("ws.Da2"); b.E = W("ws.E");
-        b.gpol = nullptr;
-        L.grid = (Rb + 3) / 4;
-        L.flops = 2.0 * B * 2 * h->Hc0 * A + 2.0 * ne * h->Hm0 * A + 2.0 * Rb * H1 * Aout;
-        L.bytes = 4.0 * (2.0 * B * h->Hc0 + ne * h->Hm0 + 2.0 * Rb * H1);
-        plan.push_back(L);
-    }
+    plan.push_back(actor_head_bwd_launch(h, B, eo, nullptr));
     {   // the policy and expert rows: rows [B, B + Rb) of Xa and of the hidden buffers, [0, Rb) of the deltas
         const ActorPass bw = actor_pass_ws(h, Xa + (size_t)B * ldS, Rb, B, h->Ra);
         actor_bwd_chain(h, plan, bw, Da - 1, record_probs);
@@ -2295,25 +2174,7 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     // ---- alpha: the updated actor on s, evaluate, Adam on alpha, statistics
     const size_t alpha_first = plan.size();
     actor_fwd_chain(h, plan, actor_pass_ws(h, Xa + (size_t)B * ldS, B, Ra4, h->Ra), "alpha.fwd", "alpha.ln", record_probs);
-    {
-        Launch L{};
-        L.kind = Launch::AHEAD;
-        L.name = "alpha.head";
-        HeadArgs& a = L.head;
-        head_base(a, W("ws.Hl2"));
-        a.nseg = 1;
-        a.seg[0] = {0, B, 0, 0, noise_al, nullptr, W("ws.nlp3")};
-        a.total_rows = B;
-        a.cache_row0 = 1 << 30;
-        a.c_t = nullptr;
-        a.alpha_mode = 1;
-        L.fin.red = W("red");                       // per-workgroup partials of sum(-nlp + H)
-        L.fin.target_entropy = h->cfg.target_entropy;
-        L.grid = (B + 3) / 4;
-        L.flops = 2.0 * B * H1 * Aout;
-        L.bytes = 4.0 * B * H1;
-        plan.push_back(L);
-    }
+    plan.push_back(alpha_head_launch(h, slot, nullptr));
     plan_alpha_final(h, plan, nm);
     for (size_t i = alpha_first; i < plan.size(); ++i) plan[i].alpha_branch = true;
     for (Launch& L : plan) pack_seeds(L, (int64_t)h->seed_bytes, h->seeds);
@@ -2340,55 +2201,32 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
     h->probs_cursor = 0;
-    const int S = h->S, A = h->A, H0 = h->H0, H1 = h->H1, ne = h->ne, Aout = h->Aout;
-    const int Hm0 = h->Hm0, half = ne / 2;
-    const int nm = expert_split(h).nm;      // the expert term's models
-    const int ldQ = h->ldQ;
+    const int S = h->S, A = h->A, H1 = h->H1, ne = h->ne, Aout = h->Aout;
+    const int Hm0 = h->Hm0;
+    const ExpertSplit es = expert_split(h);
+    const int nm = es.nm;                   // the expert term's models
     const bool fold = !h->deep;
-    const NetDims &na = h->nd[0], &nmd = h->nd[2];
-    const int Da = na.D(), Dm = nmd.D();
+    const int Da = h->nd[0].D(), Dm = h->nd[2].D();
     const std::string sl = "slot" + std::to_string(slot);
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = layer_name;
     float* noise_e = h->f(sl + ".noise");
     float *Xa = W(sl + ".Xa"), *Xm = W(sl + ".Xm"), *se_raw = W(sl + ".se_raw"), *spe_raw = W(sl + ".spe_raw");
-    float* Ha_last = W("ws.Ha2");
 
     plan_inputs(h, plan, slot);
     const size_t body0 = plan.size();
     // ---- actor forward on the expert rows: rows [0, ne) of every actor-side buffer
     const ActorPass ap = actor_pass_ws(h, Xa, ne, 0, ne);
-    const int tqh = (H1 + 15) / 16;
-    const bool head_part = fold && Aout <= 8 && H1 <= 256 && H1 % 64 == 0 && h->tile32_plan == 0;
+    const bool head_part = fold && head_part_shape(h) && h->tile32_plan == 0;
     actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", record_probs);
     if (head_part) {                         // the head's Ha2 . W3 as per-column-tile partials of the last layer (GR_HEAD_PART)
-        GemmArgs& g = plan.back().gemm;      // (two layers: the norm's launch is behind layer 0's)
-        GemmProb& p = g.probs[0];
-        p.pw = W(L_("actor", Da)); p.pw_ld = 1; p.pw_cs = Aout; p.pw_n = Aout;
-        p.ppart = W("ws.hpart");
+        head_part_dots(h, plan.back().gemm.probs[0], W("ws.hpart"));   // (two layers: the norm's launch is behind layer 0's)
         set_rows(plan.back(), GR_HEAD_PART);
     }
     if (fold && !h->ln && h->fwd2) fuse_fwd2(h, plan, "actor.fwd01");
     {   // ---- actor head: sample(s_e) into the models' input rows (their normaliser for the action columns)
-        Launch L{};
-        L.kind = Launch::AHEAD;
-        L.name = "actor.head";
-        HeadArgs& a = L.head;
-        a.H2 = Ha_last; a.ldh = H1; a.W3 = W(L_("actor", Da)); a.logstd = W("actor.logstd");
-        a.part = head_part ? W("ws.hpart") : nullptr; a.tq = tqh;
-        a.H1 = H1; a.A = A; a.Aout = Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
-        a.ma_mean = W("mnorm.a_mean"); a.ma_den = W("mnorm.a_den");
-        a.nseg = 1;
-        a.seg[0] = {0, ne, 1, 0, noise_e, Xm, nullptr};
-        a.total_rows = ne;
-        a.cache_row0 = 0;
-        a.cache_row1 = ne;
-        a.c_t = W("ws.c_t"); a.c_std = W("ws.c_std"); a.c_u = W("ws.c_u"); a.c_mask = W("ws.c_mask");
-        a.alpha_mode = 0;
-        L.grid = (ne + 3) / 4;
-        L.flops = 2.0 * ne * H1 * Aout;
-        L.bytes = 4.0 * ne * (H1 + 6.0 * A);
+        Launch L = actor_head_rows(h, head_part ? W("ws.hpart") : nullptr, ne, 0);
+        L.head.nseg = 1;
+        L.head.seg[0] = {0, ne, 1, 0, noise_e, Xm, nullptr};
         plan.push_back(L);
     }
     // ---- world models 0 / 1 forward on [s_e | pi(s_e)]
@@ -2411,19 +2249,11 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     bool fin_folded = false;
     // ---- the models' backward down to their layer-0 output (the expert rows' action gradient)
     const int tqm = (Hm0 + 15) / 16;
-    const bool fold_hbw = fold && Aout <= 8 && H1 <= 256 && H1 % 16 == 0 && Hm0 <= 512 && Hm0 % 64 == 0 &&
-                          h->tile32_plan == 0;
+    const bool fold_hbw = fold && fold_hbw_shape(h) && h->tile32_plan == 0;
     for (int i = Dm; i >= 1; --i) {
         std::vector<GemmProb> pb = model_bwd_probs(h, i);
-        for (int k = 0; k < nm && i == 1 && fold_hbw; ++k) {   // partial action gradients instead of Dm1 (read by no one else)
-            GemmProb& p = pb[k];
-            p.pw = W(L_("m" + std::to_string(k), 0)) + (size_t)S * Hm0;   // action rows of W_ext
-            p.pw_ld = Hm0;
-            p.pw_cs = 1;
-            p.pw_n = A;
-            p.ppart = W("ws.mpart") + (size_t)k * half * A * tqm;
-            p.C = nullptr;
-        }
+        for (int k = 0; k < nm && i == 1 && fold_hbw; ++k)     // partial action gradients instead of Dm1
+            part_action_grad(h, pb[k], W("m" + std::to_string(k) + ".l0"), Hm0, W("ws.mpart") + (size_t)k * es.half * A * tqm);
         add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
         Launch& L = plan.back();
         if (i == 1 && fold_hbw) set_rows(L, GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
@@ -2435,43 +2265,12 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         }
     }
     // ---- actor backward: tanh-Gaussian backward -> the delta at the last hidden layer, dX, dW + Adam
-    if (fold_hbw) {
-        GemmProb p = prob_dx(Ha_last, ne, H1, W("actor.l1"), H0, W("ws.Ha1"), W("ws.Da1"), h->ln ? ACT_TANH : na.act[0]);
-        p.wgen = W("actor.l2");              // W3a [(H1+1) x Aout]
-        p.gen_act = na.act[1];               // act'(Ha2)
-        p.hbw = 1;
-        add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
-        Launch& L = plan.back();
-        set_rows(L, GR_HEAD_BWD);
-        HeadBwdArgs& b = L.gemm.hbw;
-        b.B = 0; b.A = A; b.Aout = Aout; b.per_state_std = h->cfg.per_state_std; b.tq = 0;
-        b.lim = h->cfg.act_limit; b.part = nullptr; b.gpol = nullptr; b.a_den = W("norm.a_den");
-        b.ma_den = W("mnorm.a_den"); b.alpha = W("alpha");
-        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
-        b.Da3 = W("ws.Da3"); b.E = W("ws.E"); b.Da2 = W("ws.Da2");
-        b.ne = ne; b.tqm = tqm; b.mpart = W("ws.mpart"); b.ctl = h->ctl();
+    if (fold_hbw) {                          // no policy rows (B = 0): the expert rows' partials alone
+        Launch& L = head_bwd_fold(h, plan, 0, true, record_probs);
         L.flops += 2.0 * ne * H1 * Aout;
         L.bytes += 4.0 * (ne * tqm * A + 2.0 * ne * H1);
     } else {
-        Launch L{};
-        L.kind = Launch::ABWD;
-        L.name = "actor.head.bwd";
-        ActorBwdArgs& b = L.ab;
-        b.B = 0; b.ne = ne; b.S = S; b.A = A; b.Aout = Aout; b.H0 = 0; b.H1 = H1; b.Hm0 = Hm0;
-        b.per_state_std = h->cfg.per_state_std; b.lim = h->cfg.act_limit;
-        b.Dp1 = nullptr; b.Wq1[0] = nullptr; b.Wq1[1] = nullptr;
-        b.Dm1 = W("ws.Dm1"); b.Wm1[0] = W("m0.l0"); b.Wm1[1] = W(nm > 1 ? "m1.l0" : "m0.l0");
-        b.a_den = W("norm.a_den"); b.ma_den = W("mnorm.a_den"); b.alpha = W("alpha"); b.ctl = h->ctl();
-        b.use_expert = 1;
-        b.c_t = W("ws.c_t"); b.c_std = W("ws.c_std"); b.c_u = W("ws.c_u"); b.c_mask = W("ws.c_mask");
-        b.W3a = W(L_("actor", Da)); b.Ha2 = Ha_last;
-        b.act = (Da == 1 && h->ln) ? ACT_TANH : na.act[Da - 1];   // layer norm: tanh' at the norm's output
-        b.Da3 = W("ws.Da3"); b.Da2 = W("ws.Da2"); b.E = W("ws.E");
-        b.gpol = nullptr;
-        L.grid = (ne + 3) / 4;
-        L.flops = 2.0 * ne * Hm0 * A + 2.0 * ne * H1 * Aout;
-        L.bytes = 4.0 * (ne * Hm0 + 2.0 * ne * H1);
-        plan.push_back(L);
+        plan.push_back(actor_head_bwd_launch(h, 0, true, nullptr));
     }
     // (the folded head backward is layer 1's dX already: the norm's backward alone follows it)
     actor_bwd_chain(h, plan, ap, fold_hbw ? 0 : Da - 1, record_probs);
@@ -4310,9 +4109,8 @@ static ActRowArgs act_rows_args(sacx_handle* h, const float* obs, float* noise, 
     a.mode = h->cfg.actor_gaussian ? 2 : 1;
     a.per_state_std = h->cfg.per_state_std;
     a.lim = h->cfg.act_limit;
-    if (h->cfg.actor_gaussian) {          // logstd_init (continuous_actors.py:39-44), f32
-        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-        a.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+    if (h->cfg.actor_gaussian) {
+        a.logstd_init = logstd_init(h);
         a.output_norm = h->cfg.actor_output_norm;
     }
     return a;
@@ -4462,8 +4260,7 @@ int sacx_actor_act_host_seeds(sacx_handle* h, const float* obs, int64_t n, int32
     a.per_state_std = h->cfg.per_state_std;
     a.lim = h->cfg.act_limit;
     if (h->cfg.actor_gaussian) {
-        const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-        a.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+        a.logstd_init = logstd_init(h);
         a.output_norm = h->cfg.actor_output_norm;
     }
     a.sstride = (int64_t)h->seed_bytes; a.nseeds = K; a.m = (int32_t)n;
@@ -4887,7 +4684,7 @@ static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t determ
     if (h->softmax) return fail(h, "a softmax handle samples on the host from sacx_ppo_dist's logits (discrete_actors.py:22-42)");
     if (!deterministic && spec_cancel(h)) return -1;   // a draw from the stream: undo the speculative one
     if (n < 0 || (n > 0 && (!obs || !act_out))) return fail(h, "bad arguments");
-    const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS;
+    const int S = h->S, A = h->A, ldS = h->ldS;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     if (act_rows_ok(h, n)) {
         // the env loop's few rows: the noise draw, then one workgroup per row (k_act_rows)
@@ -4916,17 +4713,12 @@ static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t determ
             launch_rng(r, h->stream);
         }
         launch_obs_norm(obs + done * S, m, S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), ldS, h->stream);
-        HeadArgs a{};
-        a.H2 = actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream);
-        a.ldh = H1; a.W3 = W(actor_head_name(h)); a.logstd = W("actor.logstd");
-        a.H1 = H1; a.A = A; a.Aout = h->Aout; a.S = S; a.ldQ = h->ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
+        HeadArgs a = head_args(h, actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream), nullptr, false);
         a.nseg = 1;
         // SquashedGaussianActor.sample (mode 1) or GaussianActor.sample (mode 2)
         a.seg[0] = {0, m, h->cfg.actor_gaussian ? 2 : 1, 0, noise, nullptr, nullptr, act_out + done * A};
-        if (h->cfg.actor_gaussian) {          // logstd_init (continuous_actors.py:39-44), f32
-            const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-            a.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+        if (h->cfg.actor_gaussian) {
+            a.logstd_init = logstd_init(h);
             a.output_norm = h->cfg.actor_output_norm;
         }
         a.total_rows = m;
@@ -4957,7 +4749,7 @@ int sacx_actor_evaluate(sacx_handle* h, const float* s, int64_t n, float* pi_out
     if (settle(h)) return -1;
     if (h->cfg.actor_gaussian) return fail(h, "GaussianActor handle: inference only (sacx_actor_act)");
     if (n < 0 || (n > 0 && (!s || !pi_out || !nlp_out))) return fail(h, "bad arguments");
-    const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS;
+    const int S = h->S, A = h->A, ldS = h->ldS;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     for (int64_t done = 0; done < n; done += ACT_CAP) {
         const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
@@ -4967,11 +4759,7 @@ int sacx_actor_evaluate(sacx_handle* h, const float* s, int64_t n, float* pi_out
         r.slot = -1; r.reset_seq = 0; r.nupd = 1;
         launch_rng(r, h->stream);
         launch_obs_norm(s + done * S, m, S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), ldS, h->stream);
-        HeadArgs a{};
-        a.H2 = actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream);
-        a.ldh = H1; a.W3 = W(actor_head_name(h)); a.logstd = W("actor.logstd");
-        a.H1 = H1; a.A = A; a.Aout = h->Aout; a.S = S; a.ldQ = h->ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
+        HeadArgs a = head_args(h, actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream), nullptr, false);
         a.nseg = 1;
         a.seg[0] = {0, m, 0, 0, W("act.noise"), nullptr, nlp_out + done, pi_out + done * A};   // mode 0: evaluate
         a.total_rows = m;
@@ -5168,7 +4956,7 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
         r.slot = -1; r.reset_seq = 0; r.nupd = 1;
         launch_rng(r, st);
     };
-    const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS, ldQ = h->ldQ;
+    const int S = h->S, A = h->A, ldS = h->ldS, ldQ = h->ldQ;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     const std::string mn = "m" + std::to_string(model);
     // steps outer, chunks inner: each step draws normal(size=(n, A)) in row order, exactly the
@@ -5204,11 +4992,7 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
             ra.idx = nullptr;
             // actor.sample: u = np.random.normal(size=(m, A))
             if (!deterministic && !first) draw(0, m * A, noise);
-            HeadArgs a{};
-            a.H2 = actor_hidden(h, W("roll.X"), ldS, m, W("roll.H1"), W("roll.H2"), st);
-            a.ldh = H1; a.W3 = W(actor_head_name(h)); a.logstd = W("actor.logstd");
-            a.H1 = H1; a.A = A; a.Aout = h->Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-            a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
+            HeadArgs a = head_args(h, actor_hidden(h, W("roll.X"), ldS, m, W("roll.H1"), W("roll.H2"), st), nullptr, false);
             a.ma_mean = W("mnorm.a_mean"); a.ma_den = W("mnorm.a_den");
             a.nseg = 1;
             // sample(): raw action to roll.A, normalised clip(a) (= a: |lim tanh| <= lim) into
@@ -5218,8 +5002,7 @@ static void enqueue_rollout(sacx_handle* h, int32_t model, const float* s_init, 
                 // GaussianActor.sample (continuous_actors.py:103-123; mode 2 as sacx_actor_act has it): the
                 // raw action to roll.A, the normalised actor.clip(a) into the model input
                 a.seg[0].mode = 2;
-                const double sm = h->cfg.actor_std_mult > 0.f ? h->cfg.actor_std_mult : 1.0;
-                a.logstd_init = (float)(std::log(sm) - (h->cfg.per_state_std ? std::log(std::log(2.0)) : 0.0));
+                a.logstd_init = logstd_init(h);
                 a.output_norm = h->cfg.actor_output_norm;
             }
             a.total_rows = m;
@@ -5342,7 +5125,7 @@ int sacx_expert_diag(sacx_handle* h, const float* s_e, const float* a_e, const f
     if (disc && h->nm < 2) return fail(h, "_calc_disc compares two world models (num_models >= 2)");
     if (!s_e || !sp_e || !out || (ea && !a_e) || (!disc && !a_e)) return fail(h, "null argument");
     if (settle(h)) return -1;
-    const int S = h->S, A = h->A, H1 = h->H1, ldS = h->ldS, ldQ = h->ldQ;
+    const int S = h->S, A = h->A, ldS = h->ldS, ldQ = h->ldQ;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     DiagArgs d{};
     d.n = n; d.S = S; d.A = A; d.ldS = ldS; d.ldQ = ldQ;
@@ -5366,11 +5149,7 @@ int sacx_expert_diag(sacx_handle* h, const float* s_e, const float* a_e, const f
         r.n_int = 0; r.n_norm = n * A; r.out_idx = nullptr; r.out_norm = W("roll.noise");
         r.slot = -1; r.reset_seq = 0; r.nupd = 1;
         launch_rng(r, h->stream);
-        HeadArgs a{};
-        a.H2 = actor_hidden(h, W("roll.X"), ldS, n, W("roll.H1"), W("roll.H2"), h->stream);
-        a.ldh = H1; a.W3 = W(actor_head_name(h)); a.logstd = W("actor.logstd");
-        a.H1 = H1; a.A = A; a.Aout = h->Aout; a.S = S; a.ldQ = ldQ; a.per_state_std = h->cfg.per_state_std;
-        a.lim = h->cfg.act_limit; a.a_mean = W("norm.a_mean"); a.a_den = W("norm.a_den");
+        HeadArgs a = head_args(h, actor_hidden(h, W("roll.X"), ldS, n, W("roll.H1"), W("roll.H2"), h->stream), nullptr, false);
         a.ma_mean = W("mnorm.a_mean"); a.ma_den = W("mnorm.a_den");
         a.nseg = 1;
         a.seg[0] = {0, n, 1, 0, W("roll.noise"), W("roll.Xm"), nullptr, W("roll.A")};

@@ -1,16 +1,15 @@
 #!/bin/bash
-# Build a variant of libsacx with extra kernel defines for A/B runs (SACX_LIBPATH=<out>):
-#   tools/build_variant.sh <name> "<-DSACX_...=... flags>"  -> tools/libvar/libsacx_<name>.so
+# Build a variant of libsacx for A/B runs (SACX_LIBPATH=<out>), from the Makefile's own object list and flags:
+#   tools/build_variant.sh <name> ["<-DSACX_...=... flags>"] [<source tree>]  -> tools/libvar/libsacx_<name>.so
+# <source tree>: another checkout's root (the parent commit's, `git worktree add`), default this one.
 set -eu
 cd "$(dirname "$0")/.."
-name=$1; flags=$2
-mkdir -p tools/libvar
-H=/opt/rocm/bin/hipcc
-F="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Iinclude -Isac-expert_amd/csrc"
-$H $F $flags -mllvm -amdgpu-kernarg-preload-count=4 -c -o tools/libvar/k_sac_$name.o sac-expert_amd/csrc/k_sac.hip
-$H $F $flags -c -o tools/libvar/sacx_$name.o sac-expert_amd/csrc/sacx.cpp
-$H $F $flags -c -o tools/libvar/mtj_$name.o sac-expert_amd/csrc/mt_jump.cpp
-$H --offload-arch=gfx950 -shared -o tools/libvar/libsacx_$name.so tools/libvar/k_sac_$name.o tools/libvar/sacx_$name.o \
-    tools/libvar/mtj_$name.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
-rm -f tools/libvar/k_sac_$name.o tools/libvar/sacx_$name.o tools/libvar/mtj_$name.o
-echo tools/libvar/libsacx_$name.so
+name=$1; flags=${2:-}; src=${3:-.}
+out=$PWD/tools/libvar
+csrc=$src/sac-expert_amd/csrc
+mkdir -p "$out"
+# the Makefile's FLAGS, so a command-line FLAGS (which replaces the Makefile's) only adds to them
+base=$(make -s -C "$csrc" --eval 'print-flags: ; @echo $(FLAGS)' print-flags)
+make -s -C "$csrc" -j"${MAX_JOBS:-4}" OUT="$out/libsacx_$name.so" OBJ="$out/obj_$name" FLAGS="$base $flags"
+rm -rf "$out/obj_$name"
+echo "tools/libvar/libsacx_$name.so"
