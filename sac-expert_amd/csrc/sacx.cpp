@@ -101,7 +101,6 @@ struct Launch {
     int grid = 0, block = 256;
     int pre_steps = 0;         // MGATHER: > 0 the pre-gather of that many fit steps (launch_mgather)
     double flops = 0, bytes = 0;
-    int gemm_first = 0;  // index of the first problem in the host table (GEMM)
     bool after_final = false;  // graph: waits for the previous update's alpha branch
     bool alpha_branch = false; // graph: runs on the side stream beside the next update's first launches
     bool frees_slot = false;   // graph: the launch that carries the folded alpha rows (last reader of a slot)
@@ -303,8 +302,6 @@ struct sacx_handle {
     std::vector<Launch> mpres;   // per seed: the pre-gather launch of its fit plan (kind RNG: none)
     std::vector<std::map<int, hipGraphExec_t>> mgraphs;   // per seed: fit steps per graph -> graph
     std::vector<int64_t> mfit_hosts;   // model steps issued per seed (mirror ctl->mfit_seq)
-    std::vector<GemmProb> probs;
-    int probs_cursor = 0;
     std::map<std::tuple<int, int, int>, hipGraphExec_t> graphs;   // (G, with_rng, skipped kind)
     std::vector<std::pair<RollKey, hipGraphExec_t>> roll_graphs;     // sacx_rollout replays
     std::vector<hipEvent_t> events;
@@ -905,15 +902,20 @@ AdamConsts adam_consts(const sacx_handle* h) {
     return c;
 }
 
-void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name, std::vector<GemmProb> ps,
-              bool record_probs, bool allow_dwl = true) {
+// The tile shapes a GEMM launch may take, in the values of sacx_handle::tile32 / dwl; -1: the handle's.  A plan
+// whose tiles are its own (the world-model fit, a TRPO chunk) passes them; every other launch takes the default
+struct GemmTiles { int tile32 = -1, dwl = -1; };
+
+void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name, std::vector<GemmProb> ps, GemmTiles tl = {}) {
+    if (tl.tile32 < 0) tl.tile32 = h->tile32;
+    if (tl.dwl < 0) tl.dwl = h->dwl;
     Launch L{};
     L.kind = Launch::GEMM;
     L.name = name;
     // 32x32 workgroup tiles for plain FWD / DX / DW launches when the handle asks for them
     // (packed seeds: many tiles per launch); head-prologue and fused two-layer launches stay 16x16
     // (tile32 = 2: forward / dX launches only -- the dW + Adam epilogue's registers cost occupancy)
-    bool t32 = h->tile32 > 0;
+    bool t32 = tl.tile32 > 0;
     // tile32 = 2 keeps dW + Adam on 16x16 tiles (their registers cost occupancy), except a launch
     // whose 16x16 tiles exceed what is resident at once (5 workgroups on each of 256 CUs): there
     // the last tiles start a whole workgroup time late (Humanoid critic.adam: 1,378 tiles, 11 us
@@ -923,15 +925,15 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
     for (auto& p : ps) tiles16 += ((p.M + 15) / 16) * ((p.N + 15) / 16);
     const bool dw_wide = tiles16 > h->dw_round_tiles;
     for (auto& p : ps)
-        t32 = t32 && p.headp == 0 && !(h->tile32 == 2 && p.epi == EPI_ADAM && !dw_wide) && p.hbw == 0;
+        t32 = t32 && p.headp == 0 && !(tl.tile32 == 2 && p.epi == EPI_ADAM && !dw_wide) && p.hbw == 0;
     // dW + Adam launches with long reductions take k_dwl (32x32 tiles, LDS-DMA staged rows)
-    bool dwl = h->dwl > 0 && allow_dwl;   // not where rows ride along (the policy head rows)
+    bool dwl = tl.dwl > 0;
     int kmax = 0;
     for (auto& p : ps) {
         dwl = dwl && p.epi == EPI_ADAM;
         kmax = std::max(kmax, (int)p.K);
     }
-    dwl = dwl && (h->dwl == 2 || kmax >= 512);
+    dwl = dwl && (tl.dwl == 2 || kmax >= 512);
     if (dwl) t32 = false;
     const int ts = (t32 || dwl) ? 32 : 16;
     const int tsn = dwl ? 16 * h->dwl_nh : ts;    // k_dwl: 32 x 16 NH tiles
@@ -944,9 +946,6 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
         L.bytes += gemm_bytes(p);
     }
     L.gemm.t32 = t32 ? 1 : 0;
-    // both slot plans address the same (slot-independent) problem table
-    L.gemm_first = h->probs_cursor;
-    h->probs_cursor += (int)ps.size();
     if (ps.size() > GEMM_MAXP) { fprintf(stderr, "sacx: too many GEMM problems in %s\n", name.c_str()); abort(); }
     // every problem of a launch must share the operand/epilogue mode (k_gemm template)
     auto mode_of = [](const GemmProb& p) {
@@ -993,7 +992,6 @@ void add_gemm(sacx_handle* h, std::vector<Launch>& plan, const std::string& name
     // so the others do not hold the mse operands in registers
     for (auto& p : ps)
         if (mode == GM_FWD && p.mse) L.gemm.rowk = GR_MSE_HEAD;
-    if (record_probs) h->probs.insert(h->probs.end(), ps.begin(), ps.end());
     L.gemm.dwl = dwl ? (h->dwl_nh == 1 ? 2 : 1) : 0;    // 2: 32x16 tiles, 1: 32x32
     L.gemm.mode = mode;
     L.gemm.vec = vec ? 1 : 0;
@@ -1088,7 +1086,6 @@ bool fuse_fwd2(sacx_handle* h, std::vector<Launch>& plan, const std::string& nam
     F.block = head ? SACX_FWD2_HEAD_NW * 64 : 1024;     // k_fwd2 waves (16; the fit's gather variant too)
     F.flops = L0.flops + L1.flops;
     F.bytes = L0.bytes + L1.bytes;
-    F.gemm_first = L0.gemm_first;
     plan.pop_back();
     plan.pop_back();
     plan.push_back(F);
@@ -1351,13 +1348,37 @@ void xbf_wire(sacx_handle* h, std::vector<Launch>& plan, int slot) {
 // Appends one GEMM launch per GEMM_MAXP problems (a launch's problems travel by value): `name`,
 // then name.1, name.2, ...  Returns the launches added.
 int add_gemm_split(sacx_handle* h, std::vector<Launch>& plan, const std::string& name, const std::vector<GemmProb>& ps,
-                   bool record_probs) {
+                   GemmTiles tl = {}) {
     int n = 0;
     for (size_t i = 0; i < ps.size(); i += GEMM_MAXP, ++n) {
         std::vector<GemmProb> part(ps.begin() + i, ps.begin() + std::min(ps.size(), i + GEMM_MAXP));
-        add_gemm(h, plan, n == 0 ? name : name + "." + std::to_string(n), part, record_probs);
+        add_gemm(h, plan, n == 0 ? name : name + "." + std::to_string(n), part, tl);
     }
     return n;
+}
+
+// The plan's last n launches (a dW family) store their gradients at +3 p_stride instead of applying them: a
+// clip or a sum over chunks comes first
+void store_grads(std::vector<Launch>& plan, int n) {
+    for (int j = 0; j < n; ++j) {
+        Launch& G = plan[plan.size() - 1 - j];
+        for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
+    }
+}
+
+// Keras Adam over the n parameters from P on their stored gradients times the device scalar `scale_dev`
+Launch adam_apply_launch(sacx_handle* h, const std::string& name, float* P, int64_t n, int group, const float* scale_dev,
+                         int t_adv) {
+    Launch U{};
+    U.kind = Launch::APPLY;
+    U.name = name;
+    AdamApplyArgs& a = U.ap;
+    a.P = P; a.n = n; a.p_stride = h->p_stride; a.group = group; a.t_off = 0;
+    a.grad_scale = 1.f; a.scale_dev = scale_dev;
+    a.ctl = h->ctl(); a.adam = adam_consts(h); a.t_adv = t_adv;
+    U.grid = (int)((n + 255) / 256);
+    U.bytes = 4.0 * n * 7;
+    return U;
 }
 
 // ---------------------------------------------------------------- shared plan builders
@@ -1369,13 +1390,77 @@ int add_gemm_split(sacx_handle* h, std::vector<Launch>& plan, const std::string&
 // these return.
 
 // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
-float* chain_buf(sacx_handle* h, const std::string& p, int i, int D) {
-    if (i == 0) return h->f(p + "1");
-    if (i == D - 1) return h->f(p + "2");
-    return h->f(p + "m" + std::to_string(i));
+std::string chain_name(const std::string& p, int i, int D) {
+    return p + (i == 0 ? "1" : i == D - 1 ? "2" : "m" + std::to_string(i));
 }
+float* chain_buf(sacx_handle* h, const std::string& p, int i, int D) { return h->f(chain_name(p, i, D)); }
 
 std::string layer_name(const std::string& net, int i) { return net + ".l" + std::to_string(i); }
+
+// One pass through one MLP on one slab of M rows.  Layer i of `net` is the segment <net>.l<i>, nd its widths and
+// activations.  Layer 0 reads K0 columns of X; hidden layer i writes H[i] and takes its delta in D[i] (empty: a
+// forward-only pass), both already at the slab's first row; the head (layer nd->D()) writes N columns of `out`
+// and takes its delta from `dout`.  What a caller's launch adds to a problem (loss epilogues, bscale, generated
+// operands, partials) it applies to what the three builders return.
+struct NetPass {
+    std::string net;
+    const NetDims* nd; int group;            // GRP_*: whose Adam constants the dW problems take
+    const float* X; int ldx, K0;
+    int M;
+    std::vector<float*> H, D;
+    int N; float* out; int ldo;              // the head: width, forward output and its row stride
+    const float* dout; int lddo;             //           its delta and that row stride
+};
+
+// layer i's input: X, or the hidden layer below
+struct NetIn { const float* p; int ld, K; };
+NetIn net_in(const NetPass& c, int i) {
+    if (i == 0) return {c.X, c.ldx, c.K0};
+    return {c.H[i - 1], c.nd->h[i - 1], c.nd->h[i - 1]};
+}
+
+// forward, layers 0 .. D (D: the head, no activation)
+GemmProb net_fwd_prob(sacx_handle* h, const NetPass& c, int i) {
+    const NetIn in = net_in(c, i);
+    if (i < c.nd->D()) return prob_fwd(in.p, in.ld, c.M, in.K, h->f(layer_name(c.net, i)), c.nd->h[i], c.H[i], c.nd->act[i]);
+    GemmProb p = prob_fwd(in.p, in.ld, c.M, in.K, h->f(layer_name(c.net, i)), c.N, c.out, ACT_NONE);
+    p.ldc = c.ldo;
+    return p;
+}
+
+// dX, layers D .. 1: the delta at layer i's output to layer i - 1's
+GemmProb net_dx_prob(sacx_handle* h, const NetPass& c, int i) {
+    const bool head = i == c.nd->D();
+    GemmProb p = prob_dx(head ? c.dout : c.D[i], c.M, head ? c.N : c.nd->h[i], h->f(layer_name(c.net, i)), c.nd->h[i - 1],
+                         c.H[i - 1], c.D[i - 1], c.nd->act[i - 1]);
+    if (head) p.lda = c.lddo;
+    return p;
+}
+
+// dW + Adam (+ Polyak into T), layers 0 .. D
+GemmProb net_dw_prob(sacx_handle* h, const NetPass& c, int i, float* T = nullptr) {
+    const bool head = i == c.nd->D();
+    const NetIn in = net_in(c, i);
+    GemmProb p = prob_dw(in.p, in.ld, in.K, c.M, head ? c.dout : c.D[i], head ? c.N : c.nd->h[i], h->f(layer_name(c.net, i)), T,
+                         c.group);
+    if (head) p.ldb = c.lddo;
+    return p;
+}
+
+// A pass of net `net` (widths h->nd[ndi]) over the chains Hn from row hrow0 and Dn from row drow0 (chain_buf;
+// Dn empty: forward only; a layer the layout holds no delta buffer for stays null).  The head is the caller's
+NetPass chain_pass(sacx_handle* h, const std::string& net, int ndi, int group, const float* X, int ldx, int K0, int M,
+                   const std::string& Hn, size_t hrow0, const std::string& Dn = "", size_t drow0 = 0) {
+    NetPass c{};
+    c.net = net; c.nd = &h->nd[ndi]; c.group = group; c.X = X; c.ldx = ldx; c.K0 = K0; c.M = M;
+    const int D = c.nd->D();
+    auto have = [&](int i) { return h->seg_index.count(chain_name(Dn, i, D)) != 0; };
+    for (int i = 0; i < D; ++i) {
+        c.H.push_back(chain_buf(h, Hn, i, D) + hrow0 * c.nd->h[i]);
+        if (!Dn.empty()) c.D.push_back(have(i) ? chain_buf(h, Dn, i, D) + drow0 * c.nd->h[i] : nullptr);
+    }
+    return c;
+}
 
 // --actor_layer_norm puts Dense -> LayerNorm -> tanh on layer 0 (nn_utils.py:110-119).  Forward: k_ln on
 // rows [r0, r1) of the pre-norm output Z, caching xhat / rstd for the rows below cache_rows
@@ -1418,6 +1503,7 @@ struct ActorPass {
     int M;                                  // rows
     int hrow0;                              // first row of the pass in H[i] (and in the layer-norm cache: xrow0)
     std::vector<float*> H, D;               // per hidden layer: output, delta
+    float* O = nullptr;                     // the output layer as a plain GEMM (the PPO step, a TRPO chunk), else null
     float *D3, *E;
     float *xhat, *rstd; int cache_rows;     // layer norm: the forward's cache
     float *gy, *gb;                         //             the backward's rows for the gamma / beta sums
@@ -1439,17 +1525,25 @@ ActorPass actor_pass_ws(sacx_handle* h, const float* X, int M, int hrow0, int ca
     return c;
 }
 
-// <name><i> for every hidden layer, k_ln (`ln_name`) behind layer 0's
+// the pass as a NetPass: the hidden rows from hrow0, the head on O / D3
+NetPass actor_net_pass(sacx_handle* h, const ActorPass& c) {
+    NetPass p{};
+    p.net = "actor"; p.nd = &h->nd[0]; p.group = GRP_PI; p.X = c.X; p.ldx = c.ldx; p.K0 = h->S; p.M = c.M;
+    for (int i = 0; i < p.nd->D(); ++i) p.H.push_back(c.H[i] + (size_t)c.hrow0 * p.nd->h[i]);
+    p.D = c.D;
+    p.N = p.ldo = p.lddo = h->Aout; p.out = c.O; p.dout = c.D3;
+    return p;
+}
+
+// <name><i> for every hidden layer, k_ln (`ln_name`) behind layer 0's (layer 0 without its activation then),
+// and for the output layer where the pass has an O
 void actor_fwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass& c, const std::string& name,
-                     const std::string& ln_name, bool record_probs) {
-    const NetDims& na = h->nd[0];
-    for (int i = 0; i < na.D(); ++i) {
-        const float* in = i == 0 ? c.X : c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1];
-        const int ldi = i == 0 ? c.ldx : na.h[i - 1], K = i == 0 ? h->S : na.h[i - 1];
-        add_gemm(h, plan, name + std::to_string(i),
-                 {prob_fwd(in, ldi, c.M, K, h->f(layer_name("actor", i)), na.h[i], c.H[i] + (size_t)c.hrow0 * na.h[i],
-                           (i == 0 && h->ln) ? ACT_NONE : na.act[i])},
-                 record_probs);
+                     const std::string& ln_name, GemmTiles tl = {}) {
+    const NetPass p = actor_net_pass(h, c);
+    for (int i = 0; i < p.nd->D() + (c.O ? 1 : 0); ++i) {
+        GemmProb q = net_fwd_prob(h, p, i);
+        if (i == 0 && h->ln) q.act = ACT_NONE;
+        add_gemm(h, plan, name + std::to_string(i), {q}, tl);
         if (i == 0 && h->ln)
             plan.push_back(ln_fwd_launch(h, ln_name, c.H[0], c.hrow0, c.hrow0 + c.M, c.xhat, c.rstd, c.cache_rows));
     }
@@ -1457,30 +1551,23 @@ void actor_fwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass&
 
 // actor.bwd<i> from layer `from` down to 1: the delta at layer i's output (D3 at the output layer) to
 // layer i - 1's, with tanh' at the norm's output under layer norm; then actor.ln.bwd
-void actor_bwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass& c, int from, bool record_probs) {
-    const NetDims& na = h->nd[0];
-    const int Da = na.D();
-    for (int i = from; i >= 1; --i)
-        add_gemm(h, plan, "actor.bwd" + std::to_string(i),
-                 {prob_dx(i == Da ? c.D3 : c.D[i], c.M, i == Da ? h->Aout : na.h[i], h->f(layer_name("actor", i)), na.h[i - 1],
-                          c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1], c.D[i - 1], (i == 1 && h->ln) ? ACT_TANH : na.act[i - 1])},
-                 record_probs);
+void actor_bwd_chain(sacx_handle* h, std::vector<Launch>& plan, const ActorPass& c, int from, GemmTiles tl = {}) {
+    const NetPass p = actor_net_pass(h, c);
+    for (int i = from; i >= 1; --i) {
+        GemmProb q = net_dx_prob(h, p, i);
+        if (i == 1 && h->ln) q.act = ACT_TANH;
+        add_gemm(h, plan, "actor.bwd" + std::to_string(i), {q}, tl);
+    }
     if (h->ln) plan.push_back(ln_bwd_launch(h, c.D[0], c.M, c.xhat, c.rstd, c.hrow0, c.gy, c.gb));
 }
 
 // the actor's dW problems in parameter order: layers 0 .. Da-1, the output layer, logstd unless
 // per_state_std, gamma and beta under layer norm
 std::vector<GemmProb> actor_dw_probs(sacx_handle* h, const ActorPass& c) {
-    const NetDims& na = h->nd[0];
-    const int Da = na.D(), H0 = h->H0, H1 = h->H1;
+    const NetPass np = actor_net_pass(h, c);
+    const int H0 = h->H0;
     std::vector<GemmProb> pw;
-    for (int i = 0; i < Da; ++i) {
-        const float* Xi = i == 0 ? c.X : c.H[i - 1] + (size_t)c.hrow0 * na.h[i - 1];
-        const int K = i == 0 ? h->S : na.h[i - 1];
-        pw.push_back(prob_dw(Xi, i == 0 ? c.ldx : K, K, c.M, c.D[i], na.h[i], h->f(layer_name("actor", i)), nullptr, GRP_PI));
-    }
-    pw.push_back(prob_dw(c.H[Da - 1] + (size_t)c.hrow0 * H1, H1, H1, c.M, c.D3, h->Aout, h->f(layer_name("actor", Da)), nullptr,
-                         GRP_PI));
+    for (int i = 0; i <= np.nd->D(); ++i) pw.push_back(net_dw_prob(h, np, i));
     if (!h->cfg.per_state_std && !h->softmax) {
         GemmProb p = prob_dw(c.E, 1, 0, c.M, c.E, h->A, h->f("actor.logstd"), nullptr, GRP_PI);
         p.ones_row = 0;   // single all-ones row: column sums of E
@@ -1531,16 +1618,19 @@ ExpertSplit expert_split(const sacx_handle* h) {
     return {nm, nm == 1 ? h->ne : h->ne / 2, h->ne / 2};
 }
 
-// model k's hidden layer i on its rows of Xm = [s_e | pi(s_e)]
-GemmProb model_fwd_prob(sacx_handle* h, const float* Xm, int k, int i) {
+// model k's pass on its rows of Xm = [s_e | pi(s_e)] (null: no layer 0) and of the ws.Hm / ws.Dm chain; the
+// delta at the head is its delta-s columns in ws.dout (the head's forward: model_head_probs)
+NetPass expert_pass(sacx_handle* h, const float* Xm, int k) {
     const ExpertSplit e = expert_split(h);
-    const NetDims& nmd = h->nd[2];
-    const int Dm = nmd.D(), ldQ = h->ldQ;
-    const float* in = i == 0 ? Xm + (size_t)k * e.half * ldQ : chain_buf(h, "ws.Hm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1];
-    return prob_fwd(in, i == 0 ? ldQ : nmd.h[i - 1], e.mrows, i == 0 ? h->S + h->A : nmd.h[i - 1],
-                    h->f(layer_name("m" + std::to_string(k), i)), nmd.h[i], chain_buf(h, "ws.Hm", i, Dm) + (size_t)k * e.half * nmd.h[i],
-                    nmd.act[i]);
+    const size_t r0 = (size_t)k * e.half;
+    NetPass c = chain_pass(h, "m" + std::to_string(k), 2, GRP_MODEL, Xm ? Xm + r0 * h->ldQ : nullptr, h->ldQ, h->S + h->A, e.mrows,
+                           "ws.Hm", r0, "ws.Dm", r0);
+    c.N = c.lddo = h->S; c.dout = h->f("ws.dout") + r0 * h->S;
+    return c;
 }
+
+// model k's hidden layer i
+GemmProb model_fwd_prob(sacx_handle* h, const float* Xm, int k, int i) { return net_fwd_prob(h, expert_pass(h, Xm, k), i); }
 
 // the models' head on the expert rows + the MSE against sp_e (SAC_expert.py:319-332, BC.py:340-352), `mse`
 // its epilogue's flags
@@ -1570,16 +1660,10 @@ std::vector<GemmProb> model_head_probs(sacx_handle* h, int mse, const float* se_
 // the models' dX problems at level i (Dm: from the head's delta-s columns) down to their layer-0 output,
 // the expert rows' action gradient
 std::vector<GemmProb> model_bwd_probs(sacx_handle* h, int i) {
-    const ExpertSplit e = expert_split(h);
-    const NetDims& nmd = h->nd[2];
-    const int Dm = nmd.D(), S = h->S;
+    const int Dm = h->nd[2].D();
     std::vector<GemmProb> pb;
-    for (int k = 0; k < e.nm; ++k) {
-        const float* D = i == Dm ? h->f("ws.dout") + (size_t)k * e.half * S
-                                 : chain_buf(h, "ws.Dm", i, Dm) + (size_t)k * e.half * nmd.h[i];
-        GemmProb p = prob_dx(D, e.mrows, i == Dm ? S : nmd.h[i], h->f(layer_name("m" + std::to_string(k), i)), nmd.h[i - 1],
-                             chain_buf(h, "ws.Hm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1],
-                             chain_buf(h, "ws.Dm", i - 1, Dm) + (size_t)k * e.half * nmd.h[i - 1], nmd.act[i - 1]);
+    for (int k = 0; k < expert_split(h).nm; ++k) {
+        GemmProb p = net_dx_prob(h, expert_pass(h, nullptr, k), i);
         if (i == Dm) p.ldb = h->Om;          // the head's delta-s columns: B[n][k] = W_ext[n][k], stride Om
         pb.push_back(p);
     }
@@ -1589,12 +1673,12 @@ std::vector<GemmProb> model_bwd_probs(sacx_handle* h, int i) {
 // The critics' problems by net and layer, as model_fwd_prob.  A chain (ws.Hq / ws.Dq: the target and critic
 // rows, ws.Hp / ws.Dp: the policy rows) holds one slab of B rows per net: t0 t1 q0 q1 in ws.Hq, q0 q1 in the
 // others.  Forward: `net`'s hidden layer i into slab `slab` of chain Hn, layer 0 reading X = [s | a]
+NetPass critic_pass(sacx_handle* h, const std::string& net, const float* X, const std::string& Hn, int hslab,
+                    const std::string& Dn = "", int dslab = 0) {
+    return chain_pass(h, net, 1, GRP_Q, X, h->ldQ, h->S + h->A, h->B, Hn, (size_t)hslab * h->B, Dn, (size_t)dslab * h->B);
+}
 GemmProb critic_fwd_prob(sacx_handle* h, const std::string& net, const float* X, const std::string& Hn, int slab, int i) {
-    const NetDims& nc = h->nd[1];
-    const int Dc = nc.D(), B = h->B;
-    const float* in = i == 0 ? X : chain_buf(h, Hn, i - 1, Dc) + (size_t)slab * B * nc.h[i - 1];
-    return prob_fwd(in, i == 0 ? h->ldQ : nc.h[i - 1], B, i == 0 ? h->S + h->A : nc.h[i - 1], h->f(layer_name(net, i)), nc.h[i],
-                    chain_buf(h, Hn, i, Dc) + (size_t)slab * B * nc.h[i], nc.act[i]);
+    return net_fwd_prob(h, critic_pass(h, net, X, Hn, slab), i);
 }
 
 // dX: the delta at `net`'s hidden layer i to layer i - 1, slab `dslab` of chain Dn, with act' at slab `hslab`
@@ -1602,24 +1686,18 @@ GemmProb critic_fwd_prob(sacx_handle* h, const std::string& net, const float* X,
 // delta from it on load (wgen, gen_act)
 GemmProb critic_dx_prob(sacx_handle* h, const std::string& net, const std::string& Hn, int hslab, const std::string& Dn,
                         int dslab, int i, bool gen = false) {
-    const NetDims& nc = h->nd[1];
-    const int Dc = nc.D(), B = h->B;
-    const float* D = gen ? chain_buf(h, Hn, i, Dc) + (size_t)hslab * B * nc.h[i] : chain_buf(h, Dn, i, Dc) + (size_t)dslab * B * nc.h[i];
-    return prob_dx(D, B, nc.h[i], h->f(layer_name(net, i)), nc.h[i - 1], chain_buf(h, Hn, i - 1, Dc) + (size_t)hslab * B * nc.h[i - 1],
-                   chain_buf(h, Dn, i - 1, Dc) + (size_t)dslab * B * nc.h[i - 1], nc.act[i - 1]);
+    const NetPass c = critic_pass(h, net, nullptr, Hn, hslab, Dn, dslab);
+    GemmProb p = net_dx_prob(h, c, i);
+    if (gen) p.A = c.H[i];
+    return p;
 }
 
 // dW + Keras Adam + Polyak into t<k> of q<k>'s layer i on the critic rows Xq (i = Dc: the output layer, from
 // the loss gradient ws.gq)
 GemmProb critic_dw_prob(sacx_handle* h, int k, const float* Xq, int i) {
-    const NetDims& nc = h->nd[1];
-    const int Dc = nc.D(), B = h->B;
-    const std::string n = "q" + std::to_string(k), t = "t" + std::to_string(k);
-    const float* X = i == 0 ? Xq : chain_buf(h, "ws.Hq", i - 1, Dc) + (size_t)(2 + k) * B * nc.h[i - 1];
-    const int K = i == 0 ? h->S + h->A : nc.h[i - 1];
-    if (i == Dc) return prob_dw(X, K, K, B, h->f("ws.gq") + (size_t)k * B, 1, h->f(layer_name(n, i)), h->f(layer_name(t, i)), GRP_Q);
-    return prob_dw(X, i == 0 ? h->ldQ : K, K, B, chain_buf(h, "ws.Dq", i, Dc) + (size_t)k * B * nc.h[i], nc.h[i],
-                   h->f(layer_name(n, i)), h->f(layer_name(t, i)), GRP_Q);
+    NetPass c = critic_pass(h, "q" + std::to_string(k), Xq, "ws.Hq", 2 + k, "ws.Dq", k);
+    c.N = c.lddo = 1; c.dout = h->f("ws.gq") + (size_t)k * h->B;
+    return net_dw_prob(h, c, i, h->f(layer_name("t" + std::to_string(k), i)));
 }
 
 // k_qhead's arguments on the last hidden rows H2, D2 the delta it writes there (nullable).  mode 0 (q.head):
@@ -1773,14 +1851,14 @@ Launch actor_head_bwd_launch(sacx_handle* h, int B, bool expert, const float* gp
 // gradients (part_action_grad: pi.q.bwd1's for the B policy rows, model.bwd1's for the expert rows), Da2
 // generated on load (an MFMA from Da3 and W3a) and stored by column tile 0.  Appends the launch and returns
 // it: the flops / bytes of the prologue are the caller's
-Launch& head_bwd_fold(sacx_handle* h, std::vector<Launch>& plan, int B, bool expert, bool record_probs) {
+Launch& head_bwd_fold(sacx_handle* h, std::vector<Launch>& plan, int B, bool expert) {
     const int ne = h->ne, rows = B + ne, H0 = h->H0, H1 = h->H1;
     GemmProb p = prob_dx(h->f("ws.Ha2") + (size_t)B * H1, rows, H1, h->f("actor.l1"), H0, h->f("ws.Ha1") + (size_t)B * H0,
                          h->f("ws.Da1"), h->ln ? ACT_TANH : h->aact[0]);
     p.wgen = h->f("actor.l2");               // W3a [(H1+1) x Aout]
     p.gen_act = h->aact[1];                  // act'(Ha2)
     p.hbw = 1;
-    add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p}, record_probs);
+    add_gemm(h, plan, "actor.head.bwd+actor.bwd1", {p});
     Launch& L = plan.back();
     set_rows(L, GR_HEAD_BWD);
     HeadBwdArgs& b = L.gemm.hbw;
@@ -1798,10 +1876,9 @@ Launch& head_bwd_fold(sacx_handle* h, std::vector<Launch>& plan, int B, bool exp
 // and the row kernels' arguments; what makes this the fused plan stays here: the head folded into q.fwd0,
 // the policy rows on critic.adam, model.head merged into pi.q.fwd*, the linearity fusion of the critic and
 // policy backward, fuse_fwd2 and xbf_wire.
-void build_plan(sacx_handle* h, int slot, bool record_probs) {
+void build_plan(sacx_handle* h, int slot) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
-    h->probs_cursor = 0;
     const int S = h->S, A = h->A, H1 = h->H1, B = h->B, Aout = h->Aout, Rb = h->Rb;
     const int Hm0 = h->Hm0, Hc0 = h->Hc0, Hc1 = h->Hc1;   // the critics' hidden sizes (--critic_layers; H0 / H1: the actor's)
     // expert rows of world model k: [k * half, (k + 1) * half) with 2 or more models (the expert term
@@ -1828,8 +1905,8 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
     // layer 0 per column tile measured slower once the alpha branch and the heads share
     // launches: 12.06k vs 12.33k updates/s)
     auto fwd_pair = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
-        add_gemm(h, plan, name + "0", p0, record_probs);
-        add_gemm(h, plan, name + "1", p1, record_probs);
+        add_gemm(h, plan, name + "0", p0);
+        add_gemm(h, plan, name + "1", p1);
     };
     // the same pair as ONE k_fwd2 launch where it qualifies (fuse_fwd2), else the two launches
     auto fwd_pair2 = [&](const std::string& name, const std::vector<GemmProb>& p0, const std::vector<GemmProb>& p1) {
@@ -1849,7 +1926,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
     // the actor's two layers on a pass's rows (--actor_layer_norm: k_ln behind layer 0), layer 1 with the
     // head partials, the pair as one k_fwd2 launch where it qualifies
     auto actor_fwd = [&](const ActorPass& c, const std::string& name, const std::string& ln_name) {
-        actor_fwd_chain(h, plan, c, name, ln_name, record_probs);
+        actor_fwd_chain(h, plan, c, name, ln_name);
         if (head_part) {
             head_part_dots(h, plan.back().gemm.probs[0], hpart(c.hrow0));
             set_rows(plan.back(), GR_HEAD_PART);
@@ -1912,7 +1989,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         }
         if (fuse_head) {
             p0[0].headp = p0[1].headp = 1;  // the target tiles' prologue
-            add_gemm(h, plan, "q.fwd0+actor.head", p0, record_probs);
+            add_gemm(h, plan, "q.fwd0+actor.head", p0);
             Launch& L = plan.back();
             set_rows(L, GR_ACTOR_HEAD);
             L.gemm.head = head_fused;
@@ -1924,7 +2001,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             L.frees_slot = true;
             // the models' layer 0 on Xm (written by the rows above)
             for (int k = 0; eo && k < nm; ++k) p1.push_back(model_fwd_prob(h, Xm, k, 0));
-            add_gemm(h, plan, "q.fwd1", p1, record_probs);
+            add_gemm(h, plan, "q.fwd1", p1);
             if (h->fwd2 && !eo) fuse_fwd2(h, plan, "q.fwd01+actor.head");
         } else {
             for (int k = 0; eo && k < nm; ++k) {
@@ -1946,7 +2023,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             p.gen_act = c1;                    // act'(Hq2); the epilogue takes act'(Hq1)
             pb.push_back(p);
         }
-        add_gemm(h, plan, "q.head+critic.bwd1", pb, record_probs);
+        add_gemm(h, plan, "q.head+critic.bwd1", pb);
         Launch& L = plan.back();
         set_rows(L, GR_QHEAD);
         L.gemm.row_blocks = (B + 3) / 4;
@@ -1961,7 +2038,8 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
                 if (i == 0) p.bscale = W("ws.gq") + (size_t)k * B;   // Dq1 = g (.) M1
                 pw.push_back(p);
             }
-        add_gemm(h, plan, "critic.adam", pw, record_probs, !fuse_head);
+        // (no k_dwl where rows ride along: the policy head rows)
+        add_gemm(h, plan, "critic.adam", pw, {-1, fuse_head ? 0 : -1});
         if (fuse_head) {                    // the policy rows of actor.head (read from pi.q.fwd0 on)
             Launch& L = plan.back();
             HeadArgs a = head_fused;
@@ -2001,8 +2079,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             Launch& F0 = plan[plan.size() - (fuse_head ? 1 : 2)];
             const std::vector<GemmProb> pm = model_head_probs(h, MSE_EXPERT, se_raw, spe_raw);
             std::vector<Launch> one;
-            add_gemm(h, one, "model.head", pm, false);
-            h->probs_cursor -= (int)pm.size();
+            add_gemm(h, one, "model.head", pm);
             if (!merge_gemm(F0.gemm, one[0].gemm)) { fprintf(stderr, "sacx: model.head merge\n"); abort(); }
             F0.name += "+model.head";
             F0.grid = F0.gemm.total_tiles;
@@ -2022,7 +2099,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             const std::vector<GemmProb> pd = model_bwd_probs(h, 2);
             pb.insert(pb.end(), pd.begin(), pd.end());
         }
-        add_gemm(h, plan, "pi.q.head+pi.q.bwd1", pb, record_probs);
+        add_gemm(h, plan, "pi.q.head+pi.q.bwd1", pb);
         {
             Launch& L = plan.back();
             set_rows(L, GR_PIQHEAD);
@@ -2038,7 +2115,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
             // partial action gradients of the expert rows instead of Dm1
             for (int k = 0; fold_hbw && k < nm; ++k)
                 part_action_grad(h, pd[k], W("m" + std::to_string(k) + ".l0"), Hm0, W("ws.mpart") + (size_t)k * half * A * tqm);
-            add_gemm(h, plan, "model.bwd1", pd, record_probs);
+            add_gemm(h, plan, "model.bwd1", pd);
             if (fold_hbw) set_rows(plan.back(), GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
         }
     }
@@ -2046,7 +2123,7 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
     {
         if (fold_hbw) {
             // actor.head.bwd as the tile prologue of actor.bwd1, from the partials of pi.q.bwd1 / model.bwd1
-            Launch& L = head_bwd_fold(h, plan, B, eo, record_probs);
+            Launch& L = head_bwd_fold(h, plan, B, eo);
             L.flops += 2.0 * B * 2 * Hc0 * A + 2.0 * Rb * H1 * Aout;
             L.bytes += 4.0 * (2.0 * B * tq * A + 2.0 * Rb * H1);
         } else {
@@ -2054,8 +2131,8 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
         }
         // (the folded head backward is layer 1's dX already: the norm's backward alone follows it)
         const ActorPass bw = actor_pass_ws(h, Xa + (size_t)B * ldS, Rb, B, h->Ra);
-        actor_bwd_chain(h, plan, bw, fold_hbw ? 0 : 1, record_probs);
-        add_gemm(h, plan, "actor.adam", actor_dw_probs(h, bw), record_probs);
+        actor_bwd_chain(h, plan, bw, fold_hbw ? 0 : 1);
+        add_gemm(h, plan, "actor.adam", actor_dw_probs(h, bw));
         if (h->dp_ranks > 0) dp_split_adam(h, plan, "actor.l0", "actor.logstd", "", GRP_PI);
     }
     // ---- alpha: updated actor on s, evaluate, Adam on alpha, statistics
@@ -2082,10 +2159,9 @@ void build_plan(sacx_handle* h, int slot, bool record_probs) {
 // loss-scaled one, the dW launches take unscaled rows.  merged_body folds the alpha branch exactly
 // as in the fused plan (alpha.fwd<i> into actor.fwd<i>, alpha.head into actor.head, alpha.final into
 // the first forward launch after it).
-void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
+void build_plan_generic(sacx_handle* h, int slot) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
-    h->probs_cursor = 0;
     const int B = h->B, Hc1 = h->Hc1;
     const int nm = expert_split(h).nm;      // the expert term's models
     const int ldS = h->ldS, Rb = h->Rb;
@@ -2101,7 +2177,7 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
 
     plan_inputs(h, plan, slot);
     // ---- actor forward on all Ra rows of Xa (the layer-norm cache holds them all)
-    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa, h->Ra, 0, h->Ra), "actor.fwd", "actor.ln", record_probs);
+    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa, h->Ra, 0, h->Ra), "actor.fwd", "actor.ln");
     // ---- actor head: evaluate(sp) -> target rows, evaluate(s) -> policy rows, sample(s_e) -> model rows
     plan.push_back(actor_head_launch(h, slot, nullptr));
     // ---- target / critic forward (t0, t1 on [sp | pi(sp)], q0, q1 on [s | a]; the world models' hidden
@@ -2112,10 +2188,10 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
             for (int k = 0; k < 4; ++k) ps.push_back(critic_fwd_prob(h, qn[k], k < 2 ? Xt : Xq, "ws.Hq", k, i));
         if (i < Dm)
             for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
-        add_gemm(h, plan, "q.fwd" + std::to_string(i), ps, record_probs);
+        add_gemm(h, plan, "q.fwd" + std::to_string(i), ps);
     }
     if (eo)     // the world models' head on the expert rows + the expert MSE (SAC_expert.py:319-332)
-        add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT, se_raw, spe_raw), record_probs);
+        add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT, se_raw, spe_raw));
     {   // ---- q.head: min target, TD target, critic losses and the delta at the critics' last hidden layer
         Launch L{};
         L.kind = Launch::QHEAD;
@@ -2130,20 +2206,20 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
         for (int k = 0; k < 2; ++k) pb.push_back(critic_dx_prob(h, qn[2 + k], "ws.Hq", 2 + k, "ws.Dq", k, i));
-        add_gemm(h, plan, "critic.bwd" + std::to_string(i), pb, record_probs);
+        add_gemm(h, plan, "critic.bwd" + std::to_string(i), pb);
     }
     {
         std::vector<GemmProb> pw;
         for (int k = 0; k < 2; ++k)
             for (int i = 0; i <= Dc; ++i) pw.push_back(critic_dw_prob(h, k, Xq, i));
-        const int n = add_gemm_split(h, plan, "critic.adam", pw, record_probs);
+        const int n = add_gemm_split(h, plan, "critic.adam", pw);
         if (h->dp_ranks > 0) dp_split_adam(h, plan, "q0.l0", L_("q1", Dc), "t0.l0", GRP_Q, n);
     }
     // ---- policy loss through the updated critics
     for (int i = 0; i < Dc; ++i) {
         std::vector<GemmProb> ps;
         for (int k = 0; k < 2; ++k) ps.push_back(critic_fwd_prob(h, qn[2 + k], Xp, "ws.Hp", k, i));
-        add_gemm(h, plan, "pi.q.fwd" + std::to_string(i), ps, record_probs);
+        add_gemm(h, plan, "pi.q.fwd" + std::to_string(i), ps);
     }
     {   // min, tie split, policy loss rows, the delta at the critics' last hidden layer (x d p / d Q_k)
         Launch L{};
@@ -2158,22 +2234,22 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
     for (int i = Dc - 1; i >= 1; --i) {
         std::vector<GemmProb> pb;
         for (int k = 0; k < 2; ++k) pb.push_back(critic_dx_prob(h, qn[2 + k], "ws.Hp", k, "ws.Dp", k, i));
-        add_gemm(h, plan, "pi.q.bwd" + std::to_string(i), pb, record_probs);
+        add_gemm(h, plan, "pi.q.bwd" + std::to_string(i), pb);
     }
     if (eo)     // the world models' backward to their layer-0 output (the expert rows' action gradient)
-        for (int i = Dm; i >= 1; --i) add_gemm(h, plan, "model.bwd" + std::to_string(i), model_bwd_probs(h, i), record_probs);
+        for (int i = Dm; i >= 1; --i) add_gemm(h, plan, "model.bwd" + std::to_string(i), model_bwd_probs(h, i));
     // ---- actor backward: action gradients -> tanh-Gaussian backward -> the delta at the last hidden
     // layer (k_actor_bwd, from the loss-scaled deltas: gpol = null), dX to layer 0, dW + Adam
     plan.push_back(actor_head_bwd_launch(h, B, eo, nullptr));
     {   // the policy and expert rows: rows [B, B + Rb) of Xa and of the hidden buffers, [0, Rb) of the deltas
         const ActorPass bw = actor_pass_ws(h, Xa + (size_t)B * ldS, Rb, B, h->Ra);
-        actor_bwd_chain(h, plan, bw, Da - 1, record_probs);
-        const int n = add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, bw), record_probs);
+        actor_bwd_chain(h, plan, bw, Da - 1);
+        const int n = add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, bw));
         if (h->dp_ranks > 0) dp_split_adam(h, plan, "actor.l0", "actor.logstd", "", GRP_PI, n);
     }
     // ---- alpha: the updated actor on s, evaluate, Adam on alpha, statistics
     const size_t alpha_first = plan.size();
-    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa + (size_t)B * ldS, B, Ra4, h->Ra), "alpha.fwd", "alpha.ln", record_probs);
+    actor_fwd_chain(h, plan, actor_pass_ws(h, Xa + (size_t)B * ldS, B, Ra4, h->Ra), "alpha.fwd", "alpha.ln");
     plan.push_back(alpha_head_launch(h, slot, nullptr));
     plan_alpha_final(h, plan, nm);
     for (size_t i = alpha_first; i < plan.size(); ++i) plan[i].alpha_branch = true;
@@ -2197,10 +2273,9 @@ void build_plan_generic(sacx_handle* h, int slot, bool record_probs) {
 //     sums; actor.adam then takes the advanced step, t_adv) -- 8 launches at the HalfCheetah shapes:
 //     actor.fwd01 actor.head model.fwd01 model.head model.bwd2+bc.final model.bwd1
 //     actor.head.bwd+actor.bwd1 actor.adam.
-void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
+void build_plan_bc(sacx_handle* h, int slot) {
     std::vector<Launch>& plan = h->plan[slot];
     plan.clear();
-    h->probs_cursor = 0;
     const int S = h->S, A = h->A, H1 = h->H1, ne = h->ne, Aout = h->Aout;
     const int Hm0 = h->Hm0;
     const ExpertSplit es = expert_split(h);
@@ -2217,7 +2292,7 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     // ---- actor forward on the expert rows: rows [0, ne) of every actor-side buffer
     const ActorPass ap = actor_pass_ws(h, Xa, ne, 0, ne);
     const bool head_part = fold && head_part_shape(h) && h->tile32_plan == 0;
-    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", record_probs);
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln");
     if (head_part) {                         // the head's Ha2 . W3 as per-column-tile partials of the last layer (GR_HEAD_PART)
         head_part_dots(h, plan.back().gemm.probs[0], W("ws.hpart"));   // (two layers: the norm's launch is behind layer 0's)
         set_rows(plan.back(), GR_HEAD_PART);
@@ -2233,13 +2308,13 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     for (int i = 0; i < Dm; ++i) {
         std::vector<GemmProb> ps;
         for (int k = 0; k < nm; ++k) ps.push_back(model_fwd_prob(h, Xm, k, i));
-        add_gemm(h, plan, "model.fwd" + std::to_string(i), ps, record_probs);
+        add_gemm(h, plan, "model.fwd" + std::to_string(i), ps);
     }
     // the pair as one k_fwd2 launch (GR_PREGATHERED: layer 0 up to 512 wide)
     if (fold && h->fwd2 && S + A <= 32) fuse_fwd2(h, plan, "model.fwd01", true);
     const int mtn = (S + 15) / 16;
     // ---- the models' head + the MSE (BC.py:340-352), weight 1
-    add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT | MSE_BC, se_raw, spe_raw), record_probs);
+    add_gemm(h, plan, "model.head", model_head_probs(h, MSE_EXPERT | MSE_BC, se_raw, spe_raw));
     FinalArgs fin{};
     fin.alpha = W("alpha"); fin.alpha_m = fin.alpha + h->p_stride; fin.alpha_v = fin.alpha + 2 * h->p_stride;
     fin.ctl = h->ctl();
@@ -2254,7 +2329,7 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
         std::vector<GemmProb> pb = model_bwd_probs(h, i);
         for (int k = 0; k < nm && i == 1 && fold_hbw; ++k)     // partial action gradients instead of Dm1
             part_action_grad(h, pb[k], W("m" + std::to_string(k) + ".l0"), Hm0, W("ws.mpart") + (size_t)k * es.half * A * tqm);
-        add_gemm(h, plan, "model.bwd" + std::to_string(i), pb, record_probs);
+        add_gemm(h, plan, "model.bwd" + std::to_string(i), pb);
         Launch& L = plan.back();
         if (i == 1 && fold_hbw) set_rows(L, GR_PIQHEAD);   // DX with the partial epilogue (no q-head rows)
         if (fold && i == Dm && L.gemm.rowk == GR_NONE) {   // + the finalisation: one more workgroup
@@ -2266,17 +2341,17 @@ void build_plan_bc(sacx_handle* h, int slot, bool record_probs) {
     }
     // ---- actor backward: tanh-Gaussian backward -> the delta at the last hidden layer, dX, dW + Adam
     if (fold_hbw) {                          // no policy rows (B = 0): the expert rows' partials alone
-        Launch& L = head_bwd_fold(h, plan, 0, true, record_probs);
+        Launch& L = head_bwd_fold(h, plan, 0, true);
         L.flops += 2.0 * ne * H1 * Aout;
         L.bytes += 4.0 * (ne * tqm * A + 2.0 * ne * H1);
     } else {
         plan.push_back(actor_head_bwd_launch(h, 0, true, nullptr));
     }
     // (the folded head backward is layer 1's dX already: the norm's backward alone follows it)
-    actor_bwd_chain(h, plan, ap, fold_hbw ? 0 : Da - 1, record_probs);
+    actor_bwd_chain(h, plan, ap, fold_hbw ? 0 : Da - 1);
     {
         const size_t first = plan.size();
-        add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, ap), record_probs);
+        add_gemm_split(h, plan, "actor.adam", actor_dw_probs(h, ap));
         for (size_t i = first; i < plan.size(); ++i) plan[i].gemm.t_adv = fin_folded ? 1 : 0;
     }
     if (!fin_folded) {
@@ -2306,8 +2381,7 @@ void build_model_plan(sacx_handle* h) {
     const int S = h->S, A = h->A, mb = h->mb, O = S + 1, ldQ = h->ldQ;
     const int nm = h->nm;
     const NetDims& nmd = h->nd[2];
-    const NetDims& nrd = h->nd[3];
-    const int Dm = nmd.D(), Dr = h->srn ? nrd.D() : 0;
+    const int Dm = nmd.D(), Dr = h->srn ? h->nd[3].D() : 0;
     const int Lf = std::max(Dm, Dr);          // forward levels 0 .. Lf (a net's head at its own depth)
     // GaussianModel / --separate_reward_nn fits exist only in the folded form (their loss epilogues)
     const bool fuse = h->mfuse != 0 || h->gm || h->srn;
@@ -2323,7 +2397,6 @@ void build_model_plan(sacx_handle* h) {
                        Dm == 2 && !h->wide && !h->cfg.gemm_bf16;
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
-    // hidden-layer buffer i of a chain of D layers: <p>1 (layer 0), <p>2 (the last), <p>m<i>
     float *Xf = W("ws.Xf"), *Tf = W("ws.Tf"), *Of = W("ws.Of");
     float *Df3 = W("ws.Df3");
     MGatherArgs mg{};
@@ -2370,99 +2443,58 @@ void build_model_plan(sacx_handle* h) {
     // (b[t]: the dX through layer D - t of each net of depth D > t), dW + Adam per net
     std::vector<std::vector<GemmProb>> f(Lf + 1), b(Lf);
     std::vector<GemmProb> w, wr;
+    // net `net` of model k on its mb rows: the chains Hn / Dn, the head's N columns into `out` (row stride ldo)
+    // and its delta in D3 (row stride ldd); its problems by level, its dW in layer order into `dw`
+    auto add_net = [&](const std::string& net, int ndi, int k, const std::string& Hn, const std::string& Dn, int N, float* out,
+                       int ldo, float* D3, int ldd, std::vector<GemmProb>& dw) {
+        const size_t r0 = (size_t)k * mb;
+        NetPass c = chain_pass(h, net, ndi, GRP_MODEL, Xin + r0 * ldQ, ldQ, S + A, mb, Hn, r0, Dn, r0);
+        c.N = N; c.out = out + r0 * ldo; c.ldo = ldo; c.dout = D3 + r0 * ldd; c.lddo = ldd;
+        const int D = c.nd->D();
+        for (int i = 0; i <= D; ++i) f[i].push_back(net_fwd_prob(h, c, i));
+        for (int i = D; i >= 1; --i) b[D - i].push_back(net_dx_prob(h, c, i));
+        for (int i = 0; i <= D; ++i) dw.push_back(net_dw_prob(h, c, i));
+    };
     for (int k = 0; k < nm; ++k) {
         const std::string n = "m" + std::to_string(k);
         const size_t r0 = (size_t)k * mb;
-        for (int i = 0; i <= Dm; ++i) {
-            const bool head = i == Dm;
-            const float* in = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
-            const int K = i == 0 ? S + A : nmd.h[i - 1];
-            if (!head) {
-                f[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, mb, K, W(L_(n, i)), nmd.h[i],
-                                        chain_buf(h, "ws.Hf", i, Dm) + r0 * nmd.h[i], nmd.act[i]));
-            } else {
-                f[i].push_back(prob_fwd(in, K, mb, K, W(L_(n, i)), Om, fuse ? Df3 + r0 * ldO : Of + r0 * O, ACT_NONE));
-                if (fuse) {   // MSEModel / GaussianModel.get_loss as the head's epilogue: C = d loss / d out, partials
-                    GemmProb& p = f[i].back();
-                    p.ldc = ldO;
-                    p.mse = MSE_FIT | (h->gm ? MSE_GAUSS : 0) | (h->lscale ? MSE_SCALE : 0) | (h->srn ? MSE_NOREW : 0);
-                    p.se_raw = Tin + r0 * O; p.ldp = O; p.part = W("ws.lf") + r0 * nt;
-                    p.grad_scale = 1.f / (float)mb; p.fcoef = h->cfg.reward_loss_coef;   // the reward column's
-                    if (h->gm) {
-                        p.spe_raw = W(n + ".logstd");
-                        p.ppart = W("ws.lgp") + (size_t)k * ntm * S;
-                    }
-                }
+        add_net(n, 2, k, "ws.Hf", "ws.Df", Om, fuse ? Df3 : Of, fuse ? ldO : O, Df3, ldO, w);
+        if (fuse) {   // MSEModel / GaussianModel.get_loss as the head's epilogue: C = d loss / d out, partials
+            GemmProb& p = f[Dm].back();
+            p.mse = MSE_FIT | (h->gm ? MSE_GAUSS : 0) | (h->lscale ? MSE_SCALE : 0) | (h->srn ? MSE_NOREW : 0);
+            p.se_raw = Tin + r0 * O; p.ldp = O; p.part = W("ws.lf") + r0 * nt;
+            p.grad_scale = 1.f / (float)mb; p.fcoef = h->cfg.reward_loss_coef;   // the reward column's
+            if (h->gm) {
+                p.spe_raw = W(n + ".logstd");
+                p.ppart = W("ws.lgp") + (size_t)k * ntm * S;
             }
         }
-        for (int i = Dm; i >= 1; --i) {
-            const bool head = i == Dm;
-            GemmProb p = prob_dx(head ? Df3 + r0 * ldO : chain_buf(h, "ws.Df", i, Dm) + r0 * nmd.h[i], mb, head ? Om : nmd.h[i],
-                                 W(L_(n, i)), nmd.h[i - 1], chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1],
-                                 chain_buf(h, "ws.Df", i - 1, Dm) + r0 * nmd.h[i - 1], nmd.act[i - 1]);
-            if (head) p.lda = ldO;
-            if (bfold && i == 1) {   // A = D2 generated from H2, D3 and W2 on load; column tile 0 stores it for model.adam
-                p.A = W("ws.Hf2") + r0 * nmd.h[1]; p.wgen = W(L_(n, 2)); p.gen_act = nmd.act[1];
-                p.gd = Df3 + r0 * ldO; p.gd_ld = ldO; p.g_o = O; p.gst = W("ws.Df2") + r0 * nmd.h[1]; p.gst_ld = nmd.h[1];
-            }
-            b[Lf - i - (Lf - Dm)].push_back(p);
-        }
-        for (int i = 0; i <= Dm; ++i) {
-            const bool head = i == Dm;
-            const float* X = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hf", i - 1, Dm) + r0 * nmd.h[i - 1];
-            const int K = i == 0 ? S + A : nmd.h[i - 1];
-            w.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Df3 + r0 * ldO : chain_buf(h, "ws.Df", i, Dm) + r0 * nmd.h[i],
-                                head ? Om : nmd.h[i], W(L_(n, i)), nullptr, GRP_MODEL));
-            if (head) w.back().ldb = ldO;
+        if (bfold) {   // layer 1's dX: A = D2 generated from H2, D3 and W2 on load; column tile 0 stores it for model.adam
+            GemmProb& p = b[Dm - 1].back();
+            p.A = W("ws.Hf2") + r0 * nmd.h[1]; p.wgen = W(L_(n, 2)); p.gen_act = nmd.act[1];
+            p.gd = Df3 + r0 * ldO; p.gd_ld = ldO; p.g_o = O; p.gst = W("ws.Df2") + r0 * nmd.h[1]; p.gst_ld = nmd.h[1];
         }
     }
-    if (h->srn) {
-        // --separate_reward_nn (base_world_model.py:32-37, :72-74): the reward nets ride in the same
-        // launches -- their hidden layers beside the model nets', the 1-wide head with the MSE loss
-        // epilogue on the targets' reward column, their dX and (own launch) dW + Adam
-        float* Dr3 = W("ws.Drf3");
-        for (int k = 0; k < nm; ++k) {
-            const std::string n = "r" + std::to_string(k);
-            const size_t r0 = (size_t)k * mb;
-            for (int i = 0; i <= Dr; ++i) {
-                const float* in = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
-                const int K = i == 0 ? S + A : nrd.h[i - 1];
-                if (i < Dr) {
-                    f[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, mb, K, W(L_(n, i)), nrd.h[i],
-                                            chain_buf(h, "ws.Hrf", i, Dr) + r0 * nrd.h[i], nrd.act[i]));
-                } else {
-                    f[i].push_back(prob_fwd(in, K, mb, K, W(L_(n, i)), 1, Dr3 + r0 * 4, ACT_NONE));
-                    GemmProb& p = f[i].back();
-                    p.ldc = 4;
-                    p.mse = MSE_FIT;                                // N = 1: column 0 is the reward column
-                    p.se_raw = Tin + r0 * O + S; p.ldp = O; p.part = W("ws.lf") + (size_t)nm * mb * nt + r0;
-                    p.grad_scale = 1.f / (float)mb; p.fcoef = h->cfg.reward_loss_coef;
-                }
-            }
-            for (int i = Dr; i >= 1; --i) {
-                const bool head = i == Dr;
-                GemmProb p = prob_dx(head ? Dr3 + r0 * 4 : chain_buf(h, "ws.Drf", i, Dr) + r0 * nrd.h[i], mb, head ? 1 : nrd.h[i],
-                                     W(L_(n, i)), nrd.h[i - 1], chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1],
-                                     chain_buf(h, "ws.Drf", i - 1, Dr) + r0 * nrd.h[i - 1], nrd.act[i - 1]);
-                if (head) p.lda = 4;
-                b[Dr - i].push_back(p);
-            }
-            for (int i = 0; i <= Dr; ++i) {
-                const bool head = i == Dr;
-                const float* X = i == 0 ? Xin + r0 * ldQ : chain_buf(h, "ws.Hrf", i - 1, Dr) + r0 * nrd.h[i - 1];
-                const int K = i == 0 ? S + A : nrd.h[i - 1];
-                wr.push_back(prob_dw(X, i == 0 ? ldQ : K, K, mb, head ? Dr3 + r0 * 4 : chain_buf(h, "ws.Drf", i, Dr) + r0 * nrd.h[i],
-                                     head ? 1 : nrd.h[i], W(L_(n, i)), nullptr, GRP_MODEL));
-                if (head) wr.back().ldb = 4;
-            }
-        }
+    // --separate_reward_nn (base_world_model.py:32-37, :72-74): the reward nets ride in the same
+    // launches -- their hidden layers beside the model nets', the 1-wide head with the MSE loss
+    // epilogue on the targets' reward column, their dX and (own launch) dW + Adam
+    for (int k = 0; h->srn && k < nm; ++k) {
+        const size_t r0 = (size_t)k * mb;
+        add_net("r" + std::to_string(k), 3, k, "ws.Hrf", "ws.Drf", 1, W("ws.Drf3"), 4, W("ws.Drf3"), 4, wr);
+        GemmProb& p = f[Dr].back();
+        p.mse = MSE_FIT;                                // N = 1: column 0 is the reward column
+        p.se_raw = Tin + r0 * O + S; p.ldp = O; p.part = W("ws.lf") + (size_t)nm * mb * nt + r0;
+        p.grad_scale = 1.f / (float)mb; p.fcoef = h->cfg.reward_loss_coef;
     }
     // the fit's own tile shapes (SACX_MTILE): its 2 x 200 rows want 16x16 forward / dX tiles
     // (832 workgroups at 512 wide, against 224 as 32x32) whatever the update's batch made
     // h->tile32; the dW + Adam launch takes 32x32 tiles when its 16x16 ones exceed one round of
     // residency (HC 2,372 -> 610 tiles), the rule of add_gemm at tile32 = 2.  2: the handle's.
-    const int tile32_h = h->tile32;
-    if (h->mtile != 2) h->tile32 = 0;
+    // Under mtile 1 a launch takes 32x32 tiles (tile32 = 2) where mt32 names it: bit 2 the hidden forward
+    // levels (not inside the k_fwd2 pair), bit 8 the last level's heads + loss epilogue (MSE heads only),
+    // bit 4 the heads' dX (+ k_mfinal's workgroup), bit 1 the other dX levels; dW + Adam always
+    const GemmTiles fit16{h->mtile == 2 ? h->tile32 : 0, h->dwl}, fit32{2, h->dwl};
+    auto tiles_if = [&](bool t32) { return h->mtile == 1 && t32 ? fit32 : fit16; };
     auto has_head = [](const std::vector<GemmProb>& ps) {
         for (const auto& p : ps)
             if (p.mse) return true;
@@ -2471,32 +2503,26 @@ void build_model_plan(sacx_handle* h) {
     int n_fwd0 = 1;                                  // launches of level 0
     for (int i = 0; i <= Lf; ++i) {
         const std::string name = "model.fwd" + std::to_string(i);
-        const int t32_fit = h->tile32;
         if (i == 0) {
             // the gather folded into layer 0's operand loads: one launch (gfold needs !srn, so f[0] holds
             // nm <= SACX_MAX_MODELS problems); otherwise, with the reward nets' layer 0 beside the models',
             // up to 2 nm problems, GEMM_MAXP to a launch as at every other level
             if (gfold) {
-                add_gemm(h, plan, name, f[0], false);
+                add_gemm(h, plan, name, f[0], fit16);
                 Launch& F = plan.back();
                 set_rows(F, GR_GATHER);         // (16x16 tiles: a row is a whole record)
                 F.gemm.mg = mg;
                 F.name = "model.gather+fwd0";
                 F.bytes += 4.0 * nm * mb * (2.0 * S + A + 1 + O);
             } else {
-                n_fwd0 = add_gemm_split(h, plan, name, f[0], false);
+                n_fwd0 = add_gemm_split(h, plan, name, f[0], fit16);
             }
             continue;
         }
-        if (!has_head(f[i])) {
-            // hidden levels on 32x32 tiles (mt32 bit 2) when not inside the k_fwd2 pair
-            if (h->mtile == 1 && (h->mt32 & 2) && !(i == 1 && (gfold || pre) && h->mfwd2 && S + A <= 32)) h->tile32 = 2;
-        } else if (i == Lf && h->mtile == 1 && (h->mt32 & 8) && !h->gm && !h->srn) {
-            h->tile32 = 2;     // the heads (+ the MSE loss epilogue) on 32x32 tiles (mt32 bit 8; MSE heads only)
-        }
+        const bool in_pair = i == 1 && (gfold || pre) && h->mfwd2 && S + A <= 32;
+        const bool t32 = !has_head(f[i]) ? (h->mt32 & 2) && !in_pair : i == Lf && (h->mt32 & 8) && !h->gm && !h->srn;
         const size_t first = plan.size();
-        const int n_lv = add_gemm_split(h, plan, name, f[i], false);
-        h->tile32 = t32_fit;
+        const int n_lv = add_gemm_split(h, plan, name, f[i], tiles_if(t32));
         // fuse_fwd2 pairs the plan's last two launches: layer 0 and layer 1, each ONE launch (a split level
         // -- more than GEMM_MAXP nets, which is more than k_fwd2's 4 -- keeps its launches as they are)
         const bool pair01 = i == 1 && n_fwd0 == 1 && n_lv == 1;
@@ -2536,7 +2562,7 @@ void build_model_plan(sacx_handle* h) {
     for (int t = 0; t < Lf; ++t) {
         const std::string name = "model.bwd" + std::to_string(Lf - t);
         if (t == Lf - 1 && bfold) {      // model.bwd2 folded: model.bwd1 generates its A operand
-            add_gemm(h, plan, name, b[t], false);
+            add_gemm(h, plan, name, b[t], fit16);
             Launch& B1 = plan.back();
             B1.name = "model.bwd2+bwd1+final";
             set_rows(B1, GR_GEN_BWD2);      // (16x16 tiles)
@@ -2546,11 +2572,8 @@ void build_model_plan(sacx_handle* h) {
             continue;
         }
         if (t == 0 && bfold) continue;   // (in the launch above)
-        const int t32_fit = h->tile32;   // the heads' dX (+ k_mfinal's workgroup): mt32 bit 4; the others bit 1
-        if (h->mtile == 1 && (h->mt32 & (t == 0 ? 4 : 1))) h->tile32 = 2;
         const size_t first = plan.size();
-        add_gemm_split(h, plan, name, b[t], false);
-        h->tile32 = t32_fit;
+        add_gemm_split(h, plan, name, b[t], tiles_if((h->mt32 & (t == 0 ? 4 : 1)) != 0));
         if (t == 0 && fuse) {
             Launch& B2 = plan[first];
             B2.name += "+final";
@@ -2558,15 +2581,13 @@ void build_model_plan(sacx_handle* h) {
             B2.gemm.mfin = mf;
         }
     }
-    if (h->mtile == 1) h->tile32 = 2;
-    int n_adam = add_gemm_split(h, plan, "model.adam", w, false);
+    int n_adam = add_gemm_split(h, plan, "model.adam", w, tiles_if(true));
     for (int j = 0; j < n_adam; ++j) plan[plan.size() - 1 - j].gemm.t_adv = fuse ? 1 : 0;
     if (!wr.empty()) {
-        const int nr = add_gemm_split(h, plan, "reward.adam", wr, false);
+        const int nr = add_gemm_split(h, plan, "reward.adam", wr, tiles_if(true));
         for (int j = 0; j < nr; ++j) plan[plan.size() - 1 - j].gemm.t_adv = 1;
         n_adam += nr;
     }
-    h->tile32 = tile32_h;
     for (Launch& L : plan)           // GaussianModel fits: the head epilogue has the 16x16 form only
         if (L.kind == Launch::GEMM && L.gemm.t32)
             for (int i = 0; i < L.gemm.nprob; ++i)
@@ -2578,13 +2599,12 @@ void build_model_plan(sacx_handle* h) {
         // --model_max_grad_norm (mbrl_onpolicy_alg.py:315-317): the dW launches store the
         // gradients (+3 p_stride; GaussianModel's logstd gradient from mfit_final); their global
         // norm gives one scale; Adam applies g * scale over the models' whole contiguous range
+        store_grads(plan, n_adam);
         for (int a = 0; a < n_adam; ++a) {
             Launch& G = plan[plan.size() - 1 - a];
-            for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
             const size_t at = G.name.find(".adam");
             G.name = G.name.substr(0, at) + ".grad" + G.name.substr(at + 5);
         }
-        const AdamConsts gadam = adam_consts(h);
         std::string last = L_("m" + std::to_string(nm - 1), Dm);
         if (h->gm) last = "m" + std::to_string(nm - 1) + ".logstd";
         if (h->srn) last = L_("r" + std::to_string(nm - 1), Dr);
@@ -2601,16 +2621,7 @@ void build_model_plan(sacx_handle* h) {
         N.grid = GNORM_PARTS;
         N.bytes = 4.0 * n;
         plan.push_back(N);
-        Launch U{};
-        U.kind = Launch::APPLY;
-        U.name = "model.adam";
-        AdamApplyArgs& a = U.ap;
-        a.P = P; a.n = n; a.p_stride = h->p_stride; a.group = GRP_MODEL; a.t_off = 0;
-        a.grad_scale = 1.f; a.scale_dev = N.gn.scale_out;
-        a.ctl = h->ctl(); a.adam = gadam; a.t_adv = fuse ? 1 : 0;
-        U.grid = (int)((n + 255) / 256);
-        U.bytes = 4.0 * n * 7;
-        plan.push_back(U);
+        plan.push_back(adam_apply_launch(h, "model.adam", P, n, GRP_MODEL, N.gn.scale_out, fuse ? 1 : 0));
     }
     if (!fuse) {
         Launch L{};
@@ -3675,7 +3686,6 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     h->arena = h->arena0 = static_cast<char*>(arena);
     h->sel = 0;
     h->stream = static_cast<hipStream_t>(stream);
-    h->probs.clear();
     {   // ws.ones: the B-row scale of unscaled dW problems
         const SegInfo& so = h->seg("ws.ones");
         std::vector<float> ones((size_t)(so.rows * so.cols), 1.0f);
@@ -3762,9 +3772,9 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
     // size by build_ppo_plan, and cfg.batch only bounds them)
     for (int sl = 0; sl < h->nslot && !h->ppo; ++sl) {
         h->abf_written.clear();
-        if (h->bc) build_plan_bc(h, sl, sl == 0);
-        else if (h->deep) build_plan_generic(h, sl, sl == 0);
-        else build_plan(h, sl, sl == 0);
+        if (h->bc) build_plan_bc(h, sl);
+        else if (h->deep) build_plan_generic(h, sl);
+        else build_plan(h, sl);
     }
     h->abf_written.clear();
     h->wbf_attach = false;
@@ -3779,21 +3789,16 @@ int sacx_bind(sacx_handle* h, void* arena, uint64_t bytes, void* stream) {
         }
     for (int sl = 1; sl < h->nslot; ++sl) {
         if (h->plan[0].size() != h->plan[sl].size()) return fail(h, "internal: slot plans differ");
-        for (size_t i = 0; i < h->plan[0].size(); ++i)
-            if (h->plan[0][i].kind == Launch::GEMM &&
-                (h->plan[0][i].gemm_first != h->plan[sl][i].gemm_first ||
-                 h->plan[0][i].gemm_first + h->plan[0][i].gemm.nprob > (int)h->probs.size()))
-                return fail(h, "internal: GEMM problem table mismatch");
+        for (size_t i = 0; i < h->plan[0].size(); ++i) {
+            const Launch &a = h->plan[0][i], &b = h->plan[sl][i];
+            if (a.kind != b.kind || a.name != b.name || a.grid != b.grid) return fail(h, "internal: slot plans differ at " + a.name);
+        }
     }
     h->mplans.assign(h->seeds, {});
     h->mpres.assign(h->seeds, Launch{});
     h->mgraphs.assign(h->seeds, {});
     h->mfit_hosts.assign(h->seeds, 0);
-    {
-        const int cur = h->probs_cursor;
-        build_model_plan(h);                  // seed 0's; the others' on their first model_fit
-        h->probs_cursor = cur;
-    }
+    build_model_plan(h);                      // seed 0's; the others' on their first model_fit
     HIPCHK(h, hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     HIPCHK(h, hipStreamCreateWithFlags(&h->rng_stream, hipStreamNonBlocking));
     HIPCHK(h, hipEventCreateWithFlags(&h->act_ev, hipEventDisableTiming));
@@ -4451,9 +4456,7 @@ int sacx_model_fit(sacx_handle* h, const int32_t* idx, int64_t n_steps, int32_t 
     if (!idx) return fail(h, "null index array");
     const int k = h->sel;                 // packed seeds: the selected seed's models and ring
     if (h->mplans[k].empty()) {
-        const int cur = h->probs_cursor;
         build_model_plan(h);
-        h->probs_cursor = cur;
     }
     const std::vector<Launch>& mplan = h->mplans[k];
     const int R2 = h->nm * h->mb;
@@ -4641,35 +4644,54 @@ int sacx_profile(sacx_handle* h, int64_t n_steps, double* ms_per_launch, int32_t
     return 0;
 }
 
-// The hidden layers of net `net` (nd: its widths / activations) on m rows of X (row stride ldX, K0
-// inputs), alternating between H1b and H2b (layer 0 -> H1b, layer 1 -> H2b, ...); returns the
-// buffer holding the last hidden layer.  The actor's --actor_layer_norm puts Dense -> LayerNorm ->
-// tanh on layer 0 (nn_utils.py:110-119).  Eager launches on st (or captured by the caller).
-static float* net_hidden(sacx_handle* h, const std::string& net, const NetDims& nd, const float* X, int ldX, int K0,
-                         int m, float* H1b, float* H2b, hipStream_t st, bool ln = false) {
-    const float* in = X;
-    int ld = ldX, K = K0;
-    float* out = H1b;
-    for (int i = 0; i < nd.D(); ++i) {
-        out = (i & 1) ? H2b : H1b;
-        std::vector<Launch> pl;
-        add_gemm(h, pl, net + ".fwd", {prob_fwd(in, ld, m, K, h->f(net + ".l" + std::to_string(i)), nd.h[i], out,
-                                                (i == 0 && ln) ? ACT_NONE : nd.act[i])}, false);
-        h->probs_cursor -= 1;      // host table bookkeeping of add_gemm (these launches are not in a plan)
-        launch_gemm(pl[0].gemm, st);
+// One GEMM launch outside any plan, enqueued at once on st (or captured by the caller)
+static void gemm_now(sacx_handle* h, const std::string& name, const std::vector<GemmProb>& ps, hipStream_t st) {
+    std::vector<Launch> pl;
+    for (int n = add_gemm_split(h, pl, name, ps), j = 0; j < n; ++j) launch_gemm(pl[j].gemm, st);
+}
+
+// The eager passes: net `net` (widths h->nd[ndi]) on m rows of X (row stride ldX, K0 inputs), its hidden
+// layers alternating between H1b and H2b (layer 0 -> H1b, layer 1 -> H2b, ...), the head's N columns into out
+static NetPass eager_pass(sacx_handle* h, const std::string& net, int ndi, const float* X, int ldX, int K0, int m, float* H1b,
+                          float* H2b, int N = 0, float* out = nullptr) {
+    NetPass c{};
+    c.net = net; c.nd = &h->nd[ndi]; c.X = X; c.ldx = ldX; c.K0 = K0; c.M = m;
+    for (int i = 0; i < c.nd->D(); ++i) c.H.push_back((i & 1) ? H2b : H1b);
+    c.N = c.ldo = N; c.out = out;
+    return c;
+}
+
+// The pass's hidden layers; returns the buffer holding the last.  The actor's --actor_layer_norm puts
+// Dense -> LayerNorm -> tanh on layer 0 (nn_utils.py:110-119).
+static float* net_hidden(sacx_handle* h, const NetPass& c, hipStream_t st, bool ln = false) {
+    for (int i = 0; i < c.nd->D(); ++i) {
+        GemmProb p = net_fwd_prob(h, c, i);
+        if (i == 0 && ln) p.act = ACT_NONE;
+        gemm_now(h, c.net + ".fwd", {p}, st);
         if (i == 0 && ln) {
             LNArgs a{};
-            a.mode = 0; a.H = nd.h[0]; a.Z = out; a.nrange = 1; a.r[1] = m; a.gamma = h->f("actor.ln");
+            a.mode = 0; a.H = c.nd->h[0]; a.Z = c.H[0]; a.nrange = 1; a.r[1] = c.M; a.gamma = h->f("actor.ln");
             launch_ln(a, st);
         }
-        in = out;
-        ld = K = nd.h[i];
     }
-    return out;
+    return c.H.back();
+}
+// the head (with the pass's `out`)
+static void net_head(sacx_handle* h, const NetPass& c, hipStream_t st) {
+    gemm_now(h, c.net + ".out", {net_fwd_prob(h, c, c.nd->D())}, st);
 }
 
 static float* actor_hidden(sacx_handle* h, const float* X, int ldX, int m, float* H1b, float* H2b, hipStream_t st) {
-    return net_hidden(h, "actor", h->nd[0], X, ldX, h->S, m, H1b, H2b, st, h->ln);
+    return net_hidden(h, eager_pass(h, "actor", 0, X, ldX, h->S, m, H1b, H2b), st, h->ln);
+}
+
+// n normals of np.random.normal from the global stream into out
+static void noise_draw(sacx_handle* h, int64_t n, float* out, hipStream_t st) {
+    RngArgs r{};
+    r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
+    r.n_int = 0; r.n_norm = (int32_t)n; r.out_idx = nullptr; r.out_norm = out;
+    r.slot = -1; r.reset_seq = 0; r.nupd = 1;
+    launch_rng(r, st);
 }
 
 static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t deterministic, float* act_out,
@@ -4689,13 +4711,7 @@ static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t determ
     if (act_rows_ok(h, n)) {
         // the env loop's few rows: the noise draw, then one workgroup per row (k_act_rows)
         float* noise = deterministic ? nullptr : W("act.noise");
-        if (!deterministic) {          // u = np.random.normal(size=(n, A)) from the global stream
-            RngArgs r{};
-            r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
-            r.n_int = 0; r.n_norm = (int32_t)n * A; r.out_idx = nullptr; r.out_norm = noise;
-            r.slot = -1; r.reset_seq = 0; r.nupd = 1;
-            launch_rng(r, h->stream);
-        }
+        if (!deterministic) noise_draw(h, n * A, noise, h->stream);   // u = np.random.normal(size=(n, A))
         ActRowArgs a = act_rows_args(h, obs, noise, act_out);
         a.done = done;
         launch_act_rows(a, (int)n, h->stream);
@@ -4705,13 +4721,7 @@ static int actor_act(sacx_handle* h, const float* obs, int64_t n, int32_t determ
     for (int64_t done = 0; done < n; done += ACT_CAP) {
         const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
         float* noise = deterministic ? nullptr : W("act.noise");
-        if (!deterministic) {          // u = np.random.normal(size=(m, A)) from the global stream
-            RngArgs r{};
-            r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
-            r.n_int = 0; r.n_norm = m * A; r.out_idx = nullptr; r.out_norm = noise;
-            r.slot = -1; r.reset_seq = 0; r.nupd = 1;
-            launch_rng(r, h->stream);
-        }
+        if (!deterministic) noise_draw(h, (int64_t)m * A, noise, h->stream);   // u = np.random.normal(size=(m, A))
         launch_obs_norm(obs + done * S, m, S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), ldS, h->stream);
         HeadArgs a = head_args(h, actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream), nullptr, false);
         a.nseg = 1;
@@ -4753,11 +4763,7 @@ int sacx_actor_evaluate(sacx_handle* h, const float* s, int64_t n, float* pi_out
     auto W = [&](const std::string& nm) { return h->f(nm); };
     for (int64_t done = 0; done < n; done += ACT_CAP) {
         const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
-        RngArgs r{};                   // u = np.random.normal(size=np.shape(a_mean)) (:351)
-        r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
-        r.n_int = 0; r.n_norm = m * A; r.out_idx = nullptr; r.out_norm = W("act.noise");
-        r.slot = -1; r.reset_seq = 0; r.nupd = 1;
-        launch_rng(r, h->stream);
+        noise_draw(h, (int64_t)m * A, W("act.noise"), h->stream);   // u = np.random.normal(size=np.shape(a_mean)) (:351)
         launch_obs_norm(s + done * S, m, S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), ldS, h->stream);
         HeadArgs a = head_args(h, actor_hidden(h, W("act.X"), ldS, m, W("act.H1"), W("act.H2"), h->stream), nullptr, false);
         a.nseg = 1;
@@ -4777,21 +4783,17 @@ int sacx_critic_forward(sacx_handle* h, int32_t net, const float* s, const float
     if (settle(h)) return -1;
     if (net < 0 || net > 3) return fail(h, "net must be 0..3 (q0, q1, t0, t1)");
     if (n < 0 || (n > 0 && (!s || !a || !out))) return fail(h, "bad arguments");
-    const int S = h->S, A = h->A, H1 = h->Hc1, ldQ = h->ldQ;   // the critics' sizes
+    const int S = h->S, A = h->A, ldQ = h->ldQ;
     auto W = [&](const std::string& nm) { return h->f(nm); };
     static const char* names[4] = {"q0", "q1", "t0", "t1"};
-    const std::string nm = names[net];
     for (int64_t done = 0; done < n; done += ACT_CAP) {
         const int m = (int)std::min<int64_t>(ACT_CAP, n - done);
         NetIOArgs g = netio_base(h);
         g.mode = 0; g.n = m; g.ldX = ldQ; g.s = s + done * S; g.a = a + done * A; g.X = W("act.Xq");
         launch_net_io(g, h->stream);
-        float* Hl = net_hidden(h, nm, h->nd[1], W("act.Xq"), ldQ, S + A, m, W("act.H1"), W("act.H2"), h->stream);
-        std::vector<Launch> pl;
-        add_gemm(h, pl, "critic.head", {prob_fwd(Hl, H1, m, H1, W(nm + ".l" + std::to_string(h->nd[1].D())), 1, W("act.Q"),
-                                                 ACT_NONE)}, false);
-        launch_gemm(pl[0].gemm, h->stream);
-        h->probs_cursor -= 1;
+        const NetPass c = eager_pass(h, names[net], 1, W("act.Xq"), ldQ, S + A, m, W("act.H1"), W("act.H2"), 1, W("act.Q"));
+        net_hidden(h, c, h->stream);
+        net_head(h, c, h->stream);
         g.mode = 1; g.O = W("act.Q"); g.ldO = 1; g.value = value ? 1 : 0; g.out0 = out + done;
         launch_net_io(g, h->stream);
     }
@@ -4805,55 +4807,28 @@ int sacx_critic_forward(sacx_handle* h, int32_t net, const float* s, const float
 // start at row k * rstride of M1 / M2 / O / R1 / R2 (nk models on the same inputs: the diagnostics)
 static void model_gemms(sacx_handle* h, const std::vector<int>& models, int m, int64_t rstride, hipStream_t st,
                         const char* tag) {
-    const int S = h->S, A = h->A, ldQ = h->ldQ, O = S + 1;
+    const int S = h->S, O = S + 1;
     auto W = [&](const std::string& nm) { return h->f(nm); };
-    const NetDims& nmd = h->nd[2];
-    const NetDims& nrd = h->nd[3];
-    const int Dm = nmd.D(), Dr = h->srn ? nrd.D() : 0, Lf = std::max(Dm, Dr);
+    const int Dm = h->nd[2].D(), Dr = h->srn ? h->nd[3].D() : 0, Lf = std::max(Dm, Dr);
     // the hidden layers alternate between the two buffers of each net (layer 0 -> M1 / R1, layer 1 ->
     // M2 / R2, ...): their row stride is the layer's width, so model i's rows start at i * rstride * width
-    auto hb = [&](const char* b1, const char* b2, int i, int w, size_t mi) {
-        return W((i & 1) ? b2 : b1) + mi * rstride * w;
+    auto pass = [&](const std::string& net, int ndi, const char* b1, const char* b2, size_t mi, int N, float* out) {
+        NetPass c = eager_pass(h, net, ndi, W("roll.Xm"), h->ldQ, S + h->A, m, W(b1), W(b2), N, out);
+        for (int i = 0; i < c.nd->D(); ++i) c.H[i] += mi * rstride * c.nd->h[i];
+        c.ldo = O;
+        return c;
     };
     std::vector<std::vector<GemmProb>> lv(Lf + 1);
     for (size_t mi = 0; mi < models.size(); ++mi) {
-        const std::string mn = "m" + std::to_string(models[mi]);
         float* Oo = W("roll.O") + mi * rstride * O;
-        for (int i = 0; i <= Dm; ++i) {
-            const float* in = i == 0 ? W("roll.Xm") : hb("roll.M1", "roll.M2", i - 1, nmd.h[i - 1], mi);
-            const int K = i == 0 ? S + A : nmd.h[i - 1];
-            if (i < Dm) {
-                lv[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, m, K, W(mn + ".l" + std::to_string(i)), nmd.h[i],
-                                         hb("roll.M1", "roll.M2", i, nmd.h[i], mi), nmd.act[i]));
-            } else {
-                lv[i].push_back(prob_fwd(in, K, m, K, W(mn + ".l" + std::to_string(i)), h->Om, Oo, ACT_NONE));
-                lv[i].back().ldc = O;
-            }
-        }
+        const NetPass cm = pass("m" + std::to_string(models[mi]), 2, "roll.M1", "roll.M2", mi, h->Om, Oo);
+        for (int i = 0; i <= Dm; ++i) lv[i].push_back(net_fwd_prob(h, cm, i));
         if (h->srn) {     // the reward net into roll.O's reward column (base_world_model.py:72-74)
-            const std::string rn = "r" + std::to_string(models[mi]);
-            for (int i = 0; i <= Dr; ++i) {
-                const float* in = i == 0 ? W("roll.Xm") : hb("roll.R1", "roll.R2", i - 1, nrd.h[i - 1], mi);
-                const int K = i == 0 ? S + A : nrd.h[i - 1];
-                if (i < Dr) {
-                    lv[i].push_back(prob_fwd(in, i == 0 ? ldQ : K, m, K, W(rn + ".l" + std::to_string(i)), nrd.h[i],
-                                             hb("roll.R1", "roll.R2", i, nrd.h[i], mi), nrd.act[i]));
-                } else {
-                    lv[i].push_back(prob_fwd(in, K, m, K, W(rn + ".l" + std::to_string(i)), 1, Oo + S, ACT_NONE));
-                    lv[i].back().ldc = O;
-                }
-            }
+            const NetPass cr = pass("r" + std::to_string(models[mi]), 3, "roll.R1", "roll.R2", mi, 1, Oo + S);
+            for (int i = 0; i <= Dr; ++i) lv[i].push_back(net_fwd_prob(h, cr, i));
         }
     }
-    std::vector<Launch> pl;
-    const std::string t(tag);
-    int np = 0;
-    for (int i = 0; i <= Lf; ++i) {
-        add_gemm_split(h, pl, t + ".fwd" + std::to_string(i), lv[i], false);
-        np += (int)lv[i].size();
-    }
-    for (auto& L : pl) launch_gemm(L.gemm, st);
-    h->probs_cursor -= np;   // add_gemm's table (not a plan)
+    for (int i = 0; i <= Lf; ++i) gemm_now(h, std::string(tag) + ".fwd" + std::to_string(i), lv[i], st);
 }
 
 // the model net on rows [c0, c0 + m) of (s, a): roll.Xm -> roll.M1 -> roll.M2 -> roll.O
@@ -4867,12 +4842,7 @@ static void model_net_chunk(sacx_handle* h, int32_t model, const float* s, const
 // GaussianModel noise (continuous_models.py:40, :61): np.random.normal(size=(m, S)) from the device
 // stream into roll.mnoise (+ offset rows)
 static void model_noise_draw(sacx_handle* h, int64_t rows, int64_t row0, hipStream_t st) {
-    RngArgs r{};
-    r.st = h->ptr<RngState>("rng"); r.ctl = h->ctl();
-    r.n_int = 0; r.n_norm = (int32_t)(rows * h->S); r.out_idx = nullptr;
-    r.out_norm = h->f("roll.mnoise") + row0 * h->S;
-    r.slot = -1; r.reset_seq = 0; r.nupd = 1;
-    launch_rng(r, st);
+    noise_draw(h, rows * h->S, h->f("roll.mnoise") + row0 * h->S, st);
 }
 
 int sacx_model_sample(sacx_handle* h, int32_t model, const float* s, const float* a, int64_t n,
@@ -5325,14 +5295,14 @@ int sacx_time_graph(sacx_handle* h, int64_t n_replays, const char* skip_kernel, 
 //   actor.adam     Keras Adam over the actor's parameter range at the device-read rate
 static std::vector<Launch> make_ppo_plan(sacx_handle* h, int mb) {
     std::vector<Launch> plan;
-    const int cur = h->probs_cursor;
-    const int S = h->S, A = h->A, H1 = h->H1, Aout = h->Aout, ldS = h->ldS;
+    const int S = h->S, A = h->A, Aout = h->Aout, ldS = h->ldS;
     const int Da = h->nd[0].D();
     auto W = [&](const std::string& n) { return h->f(n); };
     PpoCtl* pctl = h->ptr<PpoCtl>("ppo.ctl");
     PpoPar* par = h->ptr<PpoPar>("ppo.par");
     float *X = W("ppo.X"), *O = W("ppo.O"), *acc = W("ppo.acc");
-    const ActorPass ap = actor_pass_ws(h, X, mb, 0, mb);     // the minibatch: rows [0, mb) of the update's workspace
+    ActorPass ap = actor_pass_ws(h, X, mb, 0, mb);           // the minibatch: rows [0, mb) of the update's workspace
+    ap.O = O;
     {
         Launch L{};
         L.kind = Launch::PPOGATHER;
@@ -5348,9 +5318,7 @@ static std::vector<Launch> make_ppo_plan(sacx_handle* h, int mb) {
         L.bytes = 4.0 * mb * (S + ldS + 2.0 * A + 4);
         plan.push_back(L);
     }
-    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", false);
-    add_gemm(h, plan, "actor.fwd" + std::to_string(Da),
-             {prob_fwd(ap.H[Da - 1], H1, mb, H1, W(actor_head_name(h)), Aout, O, ACT_NONE)}, false);
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln");
     {
         Launch L{};
         L.kind = Launch::PPOHEAD;
@@ -5365,14 +5333,8 @@ static std::vector<Launch> make_ppo_plan(sacx_handle* h, int mb) {
         L.bytes = 4.0 * mb * (2.0 * Aout + 2.0 * A + 4);
         plan.push_back(L);
     }
-    actor_bwd_chain(h, plan, ap, Da, false);
-    {
-        const int n_dw = add_gemm_split(h, plan, "actor.grad", actor_dw_probs(h, ap), false);
-        for (int j = 0; j < n_dw; ++j) {       // store the gradients (+3 p_stride): the clip comes first
-            Launch& G = plan[plan.size() - 1 - j];
-            for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
-        }
-    }
+    actor_bwd_chain(h, plan, ap, Da);
+    store_grads(plan, add_gemm_split(h, plan, "actor.grad", actor_dw_probs(h, ap)));      // the clip comes first
     const ParamRange ar = actor_range(h);
     float* P = ar.P;
     const int64_t n = ar.n;
@@ -5398,19 +5360,10 @@ static std::vector<Launch> make_ppo_plan(sacx_handle* h, int mb) {
         plan.push_back(L);
     }
     {
-        Launch U{};
-        U.kind = Launch::APPLY;
-        U.name = "actor.adam";
-        AdamApplyArgs& a = U.ap;
-        a.P = P; a.n = n; a.p_stride = h->p_stride; a.group = GRP_PI; a.t_off = 0;
-        a.grad_scale = 1.f; a.scale_dev = acc + PPO_ACC_SCALE;
-        a.ctl = h->ctl(); a.adam = adam_consts(h); a.t_adv = 1;       // ppo.final advanced t_pi
-        a.lr_dev = &par->actor_lr; a.t_dev = &pctl->t_pi;
-        U.grid = (int)((n + 255) / 256);
-        U.bytes = 4.0 * n * 7;
+        Launch U = adam_apply_launch(h, "actor.adam", P, n, GRP_PI, acc + PPO_ACC_SCALE, 1);   // ppo.final advanced t_pi
+        U.ap.lr_dev = &par->actor_lr; U.ap.t_dev = &pctl->t_pi;
         plan.push_back(U);
     }
-    h->probs_cursor = cur;
     return plan;
 }
 static const std::vector<Launch>& build_ppo_plan(sacx_handle* h, int mb) {
@@ -5449,11 +5402,9 @@ static int ppo_check(sacx_handle* h) {
 static PpoDist ppo_forward(sacx_handle* h, const float* s, int m) {
     auto W = [&](const std::string& nm) { return h->f(nm); };
     launch_obs_norm(s, m, h->S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), h->ldS, h->stream);
-    const float* Hl = actor_hidden(h, W("act.X"), h->ldS, m, W("act.H1"), W("act.H2"), h->stream);
-    std::vector<Launch> pl;
-    add_gemm(h, pl, "actor.out", {prob_fwd(Hl, h->H1, m, h->H1, W(actor_head_name(h)), h->Aout, W("ppo.O"), ACT_NONE)}, false);
-    h->probs_cursor -= 1;
-    launch_gemm(pl[0].gemm, h->stream);
+    const NetPass c = eager_pass(h, "actor", 0, W("act.X"), h->ldS, h->S, m, W("act.H1"), W("act.H2"), h->Aout, W("ppo.O"));
+    net_hidden(h, c, h->stream, h->ln);
+    net_head(h, c, h->stream);
     return ppo_dist(h, W("ppo.O"));
 }
 
@@ -5775,18 +5726,26 @@ static int vc_check_critic(sacx_handle* h, int32_t critic) {
 //   v.adam       one Keras Adam over the critics' parameter range at the device-read rate
 static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
     std::vector<Launch> plan;
-    const int cur = h->probs_cursor;
     const int S = h->S, ldS = h->ldS, nc = h->vc;
     const NetDims& nd = h->nd[1];
     const int D = nd.D();
     auto W = [&](const std::string& n) { return h->f(n); };
-    auto L_ = [](int k, int i) { return "v" + std::to_string(k) + ".l" + std::to_string(i); };
-    auto Hb = [&](int i, int k) { return W("vc.H" + std::to_string(i)) + (size_t)k * mb * nd.h[i]; };
-    auto Db = [&](int i, int k) { return W("vc.D" + std::to_string(i)) + (size_t)k * mb * nd.h[i]; };
     VcCtl* ctl = h->ptr<VcCtl>("vc.ctl");
     VcPar* par = h->ptr<VcPar>("vc.par");
     float *X = W("vc.X"), *O = W("vc.O"), *G = W("vc.G"), *T = W("vc.T"), *sq = W("vc.sq");
     const int rows = nc * mb;
+    std::vector<NetPass> cs;                // critic k: slab k (mb rows) of vc.X, vc.H<i> / vc.D<i>, vc.O and vc.G
+    for (int k = 0; k < nc; ++k) {
+        NetPass c{};
+        c.net = "v" + std::to_string(k); c.nd = &nd; c.group = GRP_Q;
+        c.X = X + (size_t)k * mb * ldS; c.ldx = ldS; c.K0 = S; c.M = mb;
+        for (int i = 0; i < D; ++i) {
+            c.H.push_back(W("vc.H" + std::to_string(i)) + (size_t)k * mb * nd.h[i]);
+            c.D.push_back(W("vc.D" + std::to_string(i)) + (size_t)k * mb * nd.h[i]);
+        }
+        c.N = c.ldo = c.lddo = 1; c.out = O + (size_t)k * mb; c.dout = G + (size_t)k * mb;
+        cs.push_back(c);
+    }
     {
         Launch L{};
         L.kind = Launch::VCGATHER;
@@ -5802,13 +5761,8 @@ static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
     }
     for (int i = 0; i <= D; ++i) {
         std::vector<GemmProb> ps;
-        for (int k = 0; k < nc; ++k) {
-            const float* in = i == 0 ? X + (size_t)k * mb * ldS : Hb(i - 1, k);
-            const int ldi = i == 0 ? ldS : nd.h[i - 1], K = i == 0 ? S : nd.h[i - 1];
-            ps.push_back(i < D ? prob_fwd(in, ldi, mb, K, W(L_(k, i)), nd.h[i], Hb(i, k), nd.act[i])
-                               : prob_fwd(in, ldi, mb, K, W(L_(k, i)), 1, O + (size_t)k * mb, ACT_NONE));
-        }
-        add_gemm(h, plan, "v.fwd" + std::to_string(i), ps, false);
+        for (const NetPass& c : cs) ps.push_back(net_fwd_prob(h, c, i));
+        add_gemm(h, plan, "v.fwd" + std::to_string(i), ps);
     }
     {
         Launch L{};
@@ -5823,26 +5777,16 @@ static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
     }
     for (int i = D; i >= 1; --i) {
         std::vector<GemmProb> ps;
-        for (int k = 0; k < nc; ++k)
-            ps.push_back(prob_dx(i == D ? G + (size_t)k * mb : Db(i, k), mb, i == D ? 1 : nd.h[i], W(L_(k, i)), nd.h[i - 1],
-                                 Hb(i - 1, k), Db(i - 1, k), nd.act[i - 1]));
-        add_gemm(h, plan, "v.bwd" + std::to_string(i), ps, false);
+        for (const NetPass& c : cs) ps.push_back(net_dx_prob(h, c, i));
+        add_gemm(h, plan, "v.bwd" + std::to_string(i), ps);
     }
     {
         std::vector<GemmProb> pw;
-        for (int k = 0; k < nc; ++k)
-            for (int i = 0; i <= D; ++i) {
-                const float* Xi = i == 0 ? X + (size_t)k * mb * ldS : Hb(i - 1, k);
-                const int K = i == 0 ? S : nd.h[i - 1];
-                pw.push_back(prob_dw(Xi, i == 0 ? ldS : K, K, mb, i == D ? G + (size_t)k * mb : Db(i, k), i == D ? 1 : nd.h[i],
-                                     W(L_(k, i)), nullptr, GRP_Q));
-            }
-        const int n_dw = add_gemm_split(h, plan, "v.grad", pw, false);
-        for (int j = 0; j < n_dw; ++j) {       // the gradients go to +3 vc_pstride of the critics' own range
-            Launch& Gl = plan[plan.size() - 1 - j];
-            for (int i = 0; i < Gl.gemm.nprob; ++i) Gl.gemm.probs[i].epi = EPI_STORE;
-            Gl.gemm.p_stride = h->vc_pstride;
-        }
+        for (const NetPass& c : cs)
+            for (int i = 0; i <= D; ++i) pw.push_back(net_dw_prob(h, c, i));
+        const int n_dw = add_gemm_split(h, plan, "v.grad", pw);
+        store_grads(plan, n_dw);               // the gradients go to +3 vc_pstride of the critics' own range
+        for (int j = 0; j < n_dw; ++j) plan[plan.size() - 1 - j].gemm.p_stride = h->vc_pstride;
     }
     {
         Launch L{};
@@ -5859,7 +5803,7 @@ static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
         U.kind = Launch::VCADAM;
         U.name = "v.adam";
         VcAdamArgs& a = U.va;
-        const SegInfo& sl = h->seg(L_(nc - 1, D));
+        const SegInfo& sl = h->seg(layer_name(cs.back().net, D));
         a.P = W("v0.l0");
         a.n = (int64_t)((sl.off + (uint64_t)(sl.rows * sl.cols) * 4 - h->off_of("v0.l0")) / 4);
         a.p_stride = h->vc_pstride; a.lr_dev = &par->critic_lr; a.t_dev = &ctl->t; a.t_adv = 1;   // vc.final advanced t
@@ -5867,7 +5811,6 @@ static std::vector<Launch> make_vc_plan(sacx_handle* h, int mb) {
         U.bytes = 4.0 * a.n * 7;
         plan.push_back(U);
     }
-    h->probs_cursor = cur;
     return plan;
 }
 static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
@@ -5879,15 +5822,10 @@ static const std::vector<Launch>& build_vc_plan(sacx_handle* h, int mb) {
 // critic `critic` on m <= ACT_CAP caller rows s: normalise, hidden layers, the output layer -> act.Q [m]
 static void vc_forward(sacx_handle* h, int critic, const float* s, int m) {
     auto W = [&](const std::string& nm) { return h->f(nm); };
-    const NetDims& nd = h->nd[1];
-    const std::string net = "v" + std::to_string(critic);
     launch_obs_norm(s, m, h->S, W("norm.s_mean"), W("norm.s_den"), W("act.X"), h->ldS, h->stream);
-    const float* Hl = net_hidden(h, net, nd, W("act.X"), h->ldS, h->S, m, W("act.H1"), W("act.H2"), h->stream);
-    std::vector<Launch> pl;
-    add_gemm(h, pl, "v.out", {prob_fwd(Hl, nd.h.back(), m, nd.h.back(), W(net + ".l" + std::to_string(nd.D())), 1, W("act.Q"),
-                                       ACT_NONE)}, false);
-    h->probs_cursor -= 1;
-    launch_gemm(pl[0].gemm, h->stream);
+    const NetPass c = eager_pass(h, "v" + std::to_string(critic), 1, W("act.X"), h->ldS, h->S, m, W("act.H1"), W("act.H2"), 1, W("act.Q"));
+    net_hidden(h, c, h->stream);
+    net_head(h, c, h->stream);
 }
 
 // the whole-table passes: n rows of s through critic `critic` in chunks of ACT_CAP, k_vc_rows on each
@@ -6233,7 +6171,7 @@ static int trpo_check(sacx_handle* h) {
 //   -> trpo.head -> actor.bwd<i> (+ actor.ln.bwd) -> actor.grad -> trpo.acc
 static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode, int64_t row0, int m, int64_t stride,
                             const float* dir, float* out, bool first, bool last) {
-    const int S = h->S, A = h->A, H1 = h->H1, Aout = h->Aout, ldS = h->ldS, C = h->trpo_chunk;
+    const int S = h->S, A = h->A, Aout = h->Aout, ldS = h->ldS, C = h->trpo_chunk;
     const NetDims& na = h->nd[0];
     const int Da = na.D();
     auto W = [&](const std::string& n) { return h->f(n); };
@@ -6241,14 +6179,12 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
     auto Tb = [&](int i) { return W("trpo.T" + std::to_string(i)); };
     float* P0 = W("actor.l0");
     auto dir_of = [&](const std::string& seg) { return dir + (W(seg) - P0); };     // the direction's words of a segment
-    const int t32 = h->tile32, dwl = h->dwl;
-    h->tile32 = 0; h->dwl = 0;              // 16 x 16 tiles, k_gemm: the tiles the PPO step's tests pin
-    const int cur = h->probs_cursor;
+    const GemmTiles tl{0, 0};               // 16 x 16 tiles, k_gemm: the tiles the PPO step's tests pin
     float *X = W("trpo.X"), *O = W("trpo.O");
     float *G0 = W("trpo.G"), *G1 = W("trpo.G") + (size_t)C * h->seg("trpo.G").cols;
     TrpoPar* par = h->ptr<TrpoPar>("trpo.par");
     ActorPass ap{};                         // the chunk's rows: rows [0, m) of the trpo.* buffers
-    ap.X = X; ap.ldx = ldS; ap.M = m; ap.cache_rows = m;
+    ap.X = X; ap.ldx = ldS; ap.M = m; ap.cache_rows = m; ap.O = O;
     for (int i = 0; i < Da; ++i) {
         ap.H.push_back(W("trpo.H" + std::to_string(i)));
         ap.D.push_back(W("trpo.D" + std::to_string(i)));
@@ -6269,9 +6205,7 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         L.bytes = 4.0 * m * (S + ldS);
         plan.push_back(L);
     }
-    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", false);
-    add_gemm(h, plan, "actor.fwd" + std::to_string(Da), {prob_fwd(Hb(Da - 1), H1, m, H1, W(L_("actor", Da)), Aout, O, ACT_NONE)},
-             false);
+    actor_fwd_chain(h, plan, ap, "actor.fwd", "actor.ln", tl);
     if (mode == 1) {
         // the tangent forward: per layer h_in . V + v_b and t_in . W as the two problems of one launch
         // (V_ext = the direction's words of the layer, so its bias row is v_b; the second problem's bias
@@ -6287,7 +6221,7 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
                 p.bias = W("trpo.zero");
                 ps.push_back(p);
             }
-            add_gemm(h, plan, "actor.tan" + std::to_string(i), ps, false);
+            add_gemm(h, plan, "actor.tan" + std::to_string(i), ps, tl);
             if (i == Da) break;
             Launch L{};
             L.kind = Launch::TRTAN;
@@ -6323,14 +6257,10 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         plan.push_back(L);
     }
     if (mode != 2) {
-        actor_bwd_chain(h, plan, ap, Da, false);
+        actor_bwd_chain(h, plan, ap, Da, tl);
         std::vector<GemmProb> pw = actor_dw_probs(h, ap);
         for (GemmProb& p : pw) p.bscale = W("trpo.ones");       // the chunk's row scale
-        const int n_dw = add_gemm_split(h, plan, "actor.grad", pw, false);
-        for (int j = 0; j < n_dw; ++j) {       // stored at +3 p_stride, as the PPO step's
-            Launch& G = plan[plan.size() - 1 - j];
-            for (int i = 0; i < G.gemm.nprob; ++i) G.gemm.probs[i].epi = EPI_STORE;
-        }
+        store_grads(plan, add_gemm_split(h, plan, "actor.grad", pw, tl));   // stored at +3 p_stride, as the PPO step's
         Launch L{};
         L.kind = Launch::TRACC;
         L.name = "trpo.acc";
@@ -6341,8 +6271,6 @@ static void trpo_chunk_plan(sacx_handle* h, std::vector<Launch>& plan, int mode,
         L.bytes = 4.0 * h->trpo_nv * 3;
         plan.push_back(L);
     }
-    h->probs_cursor = cur;
-    h->tile32 = t32; h->dwl = dwl;
 }
 
 // a whole-table pass: every chunk's launches in chunk order

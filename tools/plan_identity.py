@@ -9,6 +9,11 @@ learner with a fixed NumPy stream state and pushed permutations, and prints one 
   case <name> plan=<sha256 of the plan_info listing: name, kernel, grid, block, flops, bytes>:<launches>
        arena=<sha256 of the whole arena after the steps> out=<sha256 of the returned values>
 
+The cases (CASES) by family: fused.* / generic.* / bc.* the SAC-family update plans; act.*, evaluate, rollout.*,
+expert_diag* and critic_forward, srn.* the inference paths (srn.*: on a handle with reward nets); dp.* the
+data-parallel split; fit.* the world-model fit (plan = model_plan_info); ppo.*, vc.*, trpo.* the on-policy plans of a
+trainable GaussianActor / SoftMaxActor handle (plan = ppo_plan_info / vcritic_plan_info / trpo_plan_info).
+
   SACX_LIBPATH=tools/libvar/libsacx_parent.so python tools/plan_identity.py run > parent.txt
   python tools/plan_identity.py run > new.txt
   python tools/plan_identity.py compare parent.txt new.txt       # EQUAL / DIFF per case; exit 1 on a DIFF
@@ -31,6 +36,8 @@ for p in ("sac-expert_amd", "oracle", "tests"):
 OFF = {"SACX_HEAD_PART": "0", "SACX_FOLD_HBW": "0"}
 EO = dict(use_expert=True, ne=12, model_hidden=(128, 96))      # Hm0 % 64 == 0: the hbw fold takes the expert rows too
 PACK = {"SACX_T32": "2"}          # what the packed test sets where the handle's own choice depends on the device
+GAUSS = dict(gaussian_model=True, scale_model_loss=True)
+SRN = dict(separate_reward_nn=True, reward_hidden=(64, 48), reward_act="elu")
 CASES = {
     # ---- the fused plan, plain SAC: B = 64, hidden (64, 64) -- head fold, head partials and hbw fold on
     "fused.base": dict(kind="sac"),
@@ -84,6 +91,42 @@ CASES = {
     # ---- the data-parallel split (dp_split_adam): two in-process ranks on one device
     "dp.fused": dict(kind="dp"),
     "dp.generic": dict(kind="dp", kw=dict(hidden=(96, 64, 80))),
+    # ---- the world-model fit (build_model_plan): 2 eager steps, then 3 graph-replayed ones, 40 rows per model;
+    #      plan = model_plan_info
+    "fit.mse.nm2": dict(kind="fit"),
+    "fit.gauss": dict(kind="fit", kw=dict(wm=GAUSS)),
+    "fit.srn.nm2": dict(kind="fit", kw=dict(wm=SRN)),
+    "fit.srn.nm5": dict(kind="fit", kw=dict(wm=SRN, num_models=5)),                       # 10 problems: the split levels
+    "fit.srn.m3r1": dict(kind="fit", kw=dict(model_hidden=(64, 48, 64), wm=dict(SRN, reward_hidden=(64,)))),   # Lf != Dr
+    "fit.srn.m1r3": dict(kind="fit", kw=dict(model_hidden=(64,), wm=dict(SRN, reward_hidden=(64, 48, 64)))),   # Lf != Dm
+    "fit.clip.mse": dict(kind="fit", kw=dict(model_max_grad_norm=0.05)),
+    "fit.clip.gauss": dict(kind="fit", kw=dict(model_max_grad_norm=0.05, wm=GAUSS)),
+    "fit.nopre": dict(kind="fit", env={"SACX_MPRE": "0"}),                                # the gather folded: model.gather+fwd01
+    "fit.nofuse": dict(kind="fit", env={"SACX_MFUSE": "0"}),
+    "fit.mtile0": dict(kind="fit", env={"SACX_MTILE": "0"}),
+    "fit.mtile2": dict(kind="fit", env={"SACX_MTILE": "2"}),
+    "fit.mt32all": dict(kind="fit", env={"SACX_MT32": "15"}),
+    "fit.seeds2": dict(kind="fit", kw=dict(seeds=2)),
+    # ---- the on-policy plans on a trainable GaussianActor handle (S = 17, A = 6, 64 x 64, tanh): 2 eager steps
+    #      of 33 rows, then 3 graph-replayed ones; neglogp and dist on 40 rows
+    "ppo.plain": dict(kind="ppo"),
+    "ppo.ln": dict(kind="ppo", cfg=dict(layer_norm=True)),
+    "ppo.pss": dict(kind="ppo", cfg=dict(per_state_std=True)),
+    "ppo.softmax": dict(kind="ppo", softmax=True),
+    "ppo.learners2": dict(kind="ppo", learners=2),
+    "vc.nc1": dict(kind="vc", nc=1),
+    "vc.nc2": dict(kind="vc", nc=2),
+    "vc.nc1.h3": dict(kind="vc", nc=1, hidden=(64, 48, 64)),
+    # TRPO on a table of one chunk + 5 rows (`first` / `last` of a chunk differ): gradient, one Fisher product, a step
+    "trpo.plain": dict(kind="trpo"),
+    "trpo.ln": dict(kind="trpo", cfg=dict(layer_norm=True)),
+    "trpo.softmax": dict(kind="trpo", softmax=True),
+    # ---- the eager net passes: sacx_critic_forward, model_gemms with reward nets / with 3 models
+    "critic_forward": dict(kind="critic"),
+    "srn.model_forward": dict(kind="model_forward", kw=dict(wm=SRN)),
+    "srn.rollout.h3.n8": dict(kind="rollout", kw=dict(wm=SRN)),
+    "srn.expert_diag": dict(kind="diag", kw=dict(wm=SRN)),
+    "expert_diag.nm3": dict(kind="diag", kw=dict(num_models=3)),
 }
 
 
@@ -107,7 +150,7 @@ def child(name):
     kind = c["kind"]
     kw = dict(B=64, hidden=(64, 64), act="relu", seed=3, normalizers="random", N=2000, done_p=0.02)
     kw.update(c.get("kw", {}))
-    outs = []
+    outs, plan = [], None
     if kind == "sac":
         n0, n1 = 3, 20
         eng, ocfg, st, buf, nrm, expert = make_pair(**kw)
@@ -149,6 +192,25 @@ def child(name):
             e.sync()
             outs.append(e.stats(23))
         eng = engs[0]
+    elif kind == "fit":
+        nm, mb, K = int(kw.get("num_models", 2)), 40, int(kw.get("seeds", 1))
+        kw = dict(dict(use_expert=True, ne=12, model_hidden=(64, 64), model_batch=mb), **kw)
+        eng, ocfg, st, buf, nrm, expert = make_pair(**kw)
+        idx = np.random.RandomState(13).randint(kw["N"], size=(K, 5, nm, mb))
+        for k in range(K):
+            eng.select_seed(k)
+            if k > 0:
+                _, stk, bufk, nrmk, exk = make_learner(**dict({a: v for a, v in kw.items() if a not in ("seeds", "model_batch",
+                                                       "model_max_grad_norm")}, seed=kw["seed"] + 7 * k))
+                load_learner(eng, stk, bufk, nrmk, exk, 0.1)
+            eng.model_fit(idx[k, :2], eager=True)
+            eng.model_fit(idx[k, 2:])
+            eng.sync()
+            outs.append(eng.model_stats(5))
+        plan = eng.model_plan_info()
+        engs = [eng]
+    elif kind in ("ppo", "vc", "trpo"):
+        plan, engs = onpolicy(c, outs)
     else:
         from sac_eo.engine import Engine, EngineConfig
         import sac_oracle as O
@@ -171,6 +233,14 @@ def child(name):
             outs.append(eng.act(obs, deterministic=c["det"]).cpu().numpy())
         elif kind == "evaluate":
             outs += [t.cpu().numpy() for t in eng.evaluate((r.normal(size=(40, S)) * 2).astype(np.float32))]
+        elif kind == "critic":
+            obs, act = (r.normal(size=(40, S)) * 2).astype(np.float32), r.uniform(-1, 1, (40, A)).astype(np.float32)
+            for i, net in enumerate(("q0", "q1", "t0", "t1")):
+                outs.append(eng.critic_forward(net, obs, act, value=bool(i & 1)).cpu().numpy())
+        elif kind == "model_forward":
+            obs, act = (r.normal(size=(40, S)) * 2).astype(np.float32), r.uniform(-1, 1, (40, A)).astype(np.float32)
+            for k in range(2):
+                outs += [t.cpu().numpy() for t in eng.model_forward(k, obs, act, 0.05, 0.3)]
         elif kind == "rollout":
             outs += [t.cpu().numpy() for t in eng.rollout(1, (r.normal(size=(8, S)) * 1.5).astype(np.float32), 3, False)]
         else:
@@ -184,9 +254,98 @@ def child(name):
         outs.append(eng.rng_get_state()[1])
         engs = [eng]
     arena = sha(*[e.arena_all.cpu().numpy() for e in engs])
-    print(f"case {name} plan={plan_sha(eng.plan_info())} arena={arena} out={sha(*outs)}", flush=True)
+    print(f"case {name} plan={plan_sha(plan if plan is not None else engs[0].plan_info())} arena={arena} out={sha(*outs)}", flush=True)
     for e in engs:
         e.close()
+
+
+def onpolicy(c, outs):
+    """The PPO step, the VCritic step and the TRPO update of a trainable GaussianActor / SoftMaxActor handle: fills
+    `outs`, returns (the family's plan_info listing, [engine])."""
+    import numpy as np
+    import ppo_ref as R
+    import sac_oracle as O
+    import vcritic_ref as V
+    from helpers import nontrivial_normalizers
+    from sac_eo.engine import Engine, EngineConfig
+    kind, S, A, mb = c["kind"], 17, 6, 33
+    soft, K, nc = bool(c.get("softmax")), int(c.get("learners", 0)), int(c.get("nc", 0))
+    chid = tuple(c.get("hidden", (64, 64)))
+    n = 50                                               # table rows (TRPO: set below, from the engine's chunk)
+    cfg = O.Config(S=S, A=A, hidden=(64, 64), actor_acts=("tanh", "tanh"), **c.get("cfg", {}))
+    eng = Engine(EngineConfig(s_dim=S, a_dim=A, hidden=(64, 64), activation="tanh", critic_hidden=chid, batch=mb,
+                              buffer_capacity=8208 if kind == "trpo" else n, per_state_std=cfg.per_state_std, actor_layer_norm=cfg.layer_norm,
+                              actor_gaussian="train", graph_steps=1, vcritics=nc, softmax=soft, learners=K, trpo=kind == "trpo"))
+    if kind == "trpo":                                    # one chunk of a whole-table pass and 5 rows: two chunks,
+        n = int(eng.segments["trpo.X"]["rows"]) + 5       # whose `first` / `last` differ (over the capacity: an error)
+    rows = []
+    for k in range(max(K, 1)):                            # each learner's own state, table and indices
+        if K:
+            eng.select_seed(k)
+        rng = np.random.RandomState(100 + 7 * k)
+        st = R.init_state(cfg, seed=20 + k, logstd=0.2 * rng.normal(size=A) - 0.3, gain=0.5, dt=np.float32)
+        nrm = nontrivial_normalizers(rng, S, A)
+        s = (rng.normal(size=(n, S)) * rng.uniform(0.3, 2.0, S)).astype(np.float32)
+        a = rng.randint(0, A, n).astype(np.float32) if soft else rng.normal(size=(n, A)).astype(np.float32)
+        adv = (rng.normal(size=n) * 1.5 + 0.4).astype(np.float32)
+        rtg = (rng.normal(size=n) * 4 + 1).astype(np.float32)
+        eng.set_normalizers(nrm.s_mean, nrm.s_den, nrm.a_mean, nrm.a_den, ret_den=2.7)
+        for i, w in enumerate(V.init_state(S, chid, max(nc, 1), seed=40 + k, dt=np.float32).critics[:nc]):
+            eng.set_net(f"v{i}", w)
+
+        def give(move):                                   # the policy, `move` updates after the rollout
+            mv = np.random.RandomState(300 + k)
+            eng.set_net("actor", [w + (move * mv.normal(size=w.shape)).astype(np.float32) for w in st.actor])
+            if not soft:
+                eng.set_logstd(st.logstd)
+        give(0.0)
+        if kind == "ppo":
+            eng.ppo_begin(s, a, adv)
+            give(0.05)
+        elif kind == "vc":
+            for i in range(nc):
+                eng.vcritic_begin(i, s[: n - 2 * i], rtg[: n - 2 * i])
+        rows.append((s, a, rtg))
+    if kind != "trpo":                                    # 5 steps' table rows per learner
+        idx = np.stack([[np.random.RandomState(500 + 10 * k + j).permutation(n - 2 * max(nc - 1, 0))[:mb] for j in range(5)]
+                        for k in range(max(K, 1))]).astype(np.int32)
+    if kind == "ppo":
+        par = dict(eps_ppo=0.2, actor_lr=3e-4, max_grad_norm=0.5)
+        for sl, eager in ((slice(0, 2), True), (slice(2, 5), False)):
+            if K:
+                eng.ppo_steps_packed(idx[:, sl], eager=eager, **par)
+            else:
+                eng.ppo_steps(idx[0, sl], eager=eager, **par)
+        eng.sync()
+        for k in range(max(K, 1)):
+            if K:
+                eng.select_seed(k)
+            end = eng.ppo_end(0.2)
+            outs += [eng.ppo_stats(5), np.array([float(end[q]) for q in sorted(end)]),
+                     eng.neglogp(rows[k][0][:40], rows[k][1][:40]).cpu().numpy()]
+            outs += [t.cpu().numpy() for t in eng.dist(rows[k][0][:40]) if t is not None]
+        plan = eng.ppo_plan_info(mb)
+    elif kind == "vc":
+        for sl, eager in ((slice(0, 2), True), (slice(2, 5), False)):
+            eng.vcritic_steps(idx[0, sl], critic_lr=1e-3, eager=eager)
+        eng.sync()
+        end = eng.vcritic_end()
+        outs += [eng.vcritic_stats(5), np.array(end["critic_loss"] + [end["n_steps"]], np.float64)]
+        for i in range(nc):
+            outs += [eng.vcritic_value(i, rows[0][0][:40]).cpu().numpy(),
+                     eng.vcritic_loss(i, rows[0][0][:40], rows[0][2][:40]).cpu().numpy()]
+        plan = eng.vcritic_plan_info(mb)
+    else:
+        par = dict(delta=0.01, cg_it=5, trust_sub=1, trust_damp=0.5, kl_maxfactor=1.5)
+        s, a, _ = rows[0]
+        eng.trpo_begin(s, a, adv, **par)
+        g = eng.trpo_grad(flat=True)
+        f = eng.trpo_fvp(g, flat=True)
+        step = eng.trpo_step(**par)
+        outs += [g.cpu().numpy(), f.cpu().numpy(), np.array([float(step[q]) for q in sorted(step)])] + eng.get_net("actor")
+        plan = eng.trpo_plan_info(n)
+    eng.sync()
+    return plan, [eng]
 
 
 def run(names, timeout):
