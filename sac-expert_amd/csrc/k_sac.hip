@@ -1826,7 +1826,9 @@ __device__ __forceinline__ void gemm_core(const KHdr kh, const GemmArgs& ga) {
                         v = v + 0.f;
                         a[u][q] = v * dact_f(a[u][q], g.gen_act);
                     }
-                    if (store && it + u < it1)
+                    // the last slab of a row that is no multiple of 16 wide: the pieces past the row stay unwritten
+                    // (host: gst_ld = K, a multiple of 4, so a piece lies wholly inside the row or wholly past it)
+                    if (store && it + u < it1 && k0 < g.gst_ld)
                         *reinterpret_cast<float4*>(&g.gst[(size_t)m * g.gst_ld + k0]) = float4{a[u][0], a[u][1], a[u][2], a[u][3]};
                 }
                 if constexpr (BF) {

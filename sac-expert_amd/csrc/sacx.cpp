@@ -2392,9 +2392,13 @@ void build_model_plan(sacx_handle* h) {
     // model.bwd2 generated on model.bwd1's operand loads (GR_GEN_BWD2) for narrow heads (S + 1 <= 32).
     // fp32 only: the generation is an fp32 MFMA, while model.bwd2 as a launch of its own is a bf16 GEMM
     // under config C5 -- the fold would leave the head's dX operands unrounded in this one variant
-    // (every GEMM operand is rounded, whichever launch carries the GEMM)
+    // (every GEMM operand is rounded, whichever launch carries the GEMM).
+    // Layer 1 a whole number of float4s wide: column tile 0 stores the generated D2 in 16-B pieces at row
+    // stride Hm1, every lane of a 16-column slab one piece.  The kernel leaves out the pieces that begin past
+    // the row (a last slab of Hm1 % 16 columns); a piece straddling the row's end -- Hm1 % 4 != 0 -- it cannot
+    // split, and it would land on the next row's first columns (the last row's on the buffer behind ws.Df2)
     const bool bfold = fuse && h->mfuse >= 3 && O <= 32 && h->mtile != 2 && h->unaligned_b && !h->gm && !h->srn &&
-                       Dm == 2 && !h->wide && !h->cfg.gemm_bf16;
+                       Dm == 2 && !h->wide && !h->cfg.gemm_bf16 && nmd.h[1] % 4 == 0;
     auto W = [&](const std::string& n) { return h->f(n); };
     auto L_ = [](const std::string& net, int i) { return net + ".l" + std::to_string(i); };
     float *Xf = W("ws.Xf"), *Tf = W("ws.Tf"), *Of = W("ws.Of");

@@ -46,6 +46,8 @@ CASES = {
     "pss_ln": dict(S=17, A=6, B=64, hidden=(64, 48), act="relu", seed=23, N=600, per_state_std=True, layer_norm=True),
     "generic": dict(S=17, A=6, B=64, hidden=(520, 64), act="relu", seed=31, N=600),
     "wide_k0": dict(S=376, A=17, B=64, hidden=(64, 64), act="relu", seed=42, N=300),
+    # widths off the 4-grid: element-wise operand loads, a half-filled last bf16 pair (tests/test_gpu_ragged.py)
+    "off4_bf16": dict(S=17, A=6, B=37, hidden=(63, 65), act="elu", seed=9, N=600),
 }
 UNIT_DELTAS = {"generic": False}           # every other case takes the fused plan
 DONE_P = 0.05

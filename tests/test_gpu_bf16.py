@@ -81,8 +81,9 @@ def test_bf16_update_odd(gpu_available, monkeypatch):
 
 
 def test_bf16_update_narrow(gpu_available, monkeypatch):
-    """S=17, A=6, B=37, hidden (100, 60), elu: widths that are no multiple of 4, so the operands load
-    scalar by scalar, and H1 % 16 != 0, so the head keeps its own launch (actor.head, actor.head.bwd).
+    """S=17, A=6, B=37, hidden (100, 60), elu: widths that are multiples of 4 but not of 16 (ragged k slabs;
+    off the 4-grid, where the operands load scalar by scalar, is tests/test_gpu_ragged.py's off4_bf16), and
+    H1 % 16 != 0, so the head keeps its own launch (actor.head, actor.head.bwd).
     Slabs: forward 2 (K = 17, 23: even, ragged) / 7 (K = 100: odd, ragged); dX 4 (K = 60: even,
     ragged); dW 3 (37 rows)."""
     _one_update("narrow", monkeypatch, expect=("actor.head", "actor.head.bwd", "actor.bwd1", "critic.adam"),

@@ -81,8 +81,7 @@ def _pair(monkeypatch, case, B=64, seed=0, **over):
 
 
 @pytest.mark.parametrize("case", list(CASES))
-def test_one_update_any_depth(gpu_available, monkeypatch, case):
-    B = 64
+def test_one_update_any_depth(gpu_available, monkeypatch, case, B=64):
     eng, ocfg, st, buf, nrm, expert = _pair(monkeypatch, case, B=B, seed=3)
     eo = expert is not None
     nm = eng.cfg.num_models
@@ -98,6 +97,7 @@ def test_one_update_any_depth(gpu_available, monkeypatch, case):
     eng.step(1, eager=True)
     eng.sync()
     row = eng.stats(1)[0]
+    print(f"update {case} B={B}: launches " + " ".join(p["name"] for p in eng.plan_info()))
     print(f"update {case}: loss errors " + " ".join(f"{abs(row[i] - ref[k]) / abs(ref[k]):.2e}" for i, k in enumerate(
         ("q1_loss", "q2_loss", "p_loss", "alpha_loss"))) + (f" mse {abs(row[5] - ref['mse_loss']) / abs(ref['mse_loss']):.2e}"
                                                            if eo else "") + " (bar 2e-5)")

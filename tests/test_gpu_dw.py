@@ -16,16 +16,20 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("B", [128, 1024])
 @pytest.mark.parametrize("bf16", [False, True])
 @pytest.mark.parametrize("use_expert", [False, True])
-def test_dw_tilings_bit_identical(monkeypatch, variant, B, bf16, use_expert):
+def test_dw_tilings_bit_identical(monkeypatch, variant, B, bf16, use_expert, hidden=(256, 256), critic_hidden=None):
+    """hidden / critic_hidden: the widths of another caller (tests/test_gpu_ragged.py: rows that are no whole
+    number of 16-B pieces, k_dwl's dword staging)."""
     from sac_eo.engine import Engine, EngineConfig
     n, N, eps = 11, 5000, 0.1
     monkeypatch.setenv("SACX_FUSE_HEAD", "0")       # critic.adam without rows riding along (k_dwl takes it)
-    _, st, buf, nrm, ex = make_learner(act="relu", B=B, N=N, seed=3, use_expert=use_expert, epsilon=eps)
+    _, st, buf, nrm, ex = make_learner(hidden=hidden, act="relu", B=B, N=N, seed=3, use_expert=use_expert, epsilon=eps,
+                                       wm=dict(critic_hidden=critic_hidden) if critic_hidden else None)
 
     def run(env):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        e = Engine(EngineConfig(s_dim=17, a_dim=6, activation="relu", batch=B, buffer_capacity=N,
+        e = Engine(EngineConfig(s_dim=17, a_dim=6, hidden=hidden, critic_hidden=critic_hidden, activation="relu", batch=B,
+                                buffer_capacity=N,
                                 use_expert=use_expert, expert_capacity=20, expert_batch=20, graph_steps=8,
                                 epsilon=eps, gemm_bf16=bf16))
         for k in env:

@@ -211,8 +211,9 @@ def test_one_update_wide_hidden(gpu_available):
 
 
 def test_one_update_narrow_hidden(gpu_available):
-    """Hidden 100 / 60 (not multiples of 16 or 4): scalar operand loads and the separate
-    actor.head launch (the fold needs H1 % 16 == 0)."""
+    """Hidden 100 / 60 (multiples of 4, not of 16 / 64): ragged last tiles and k slabs and the separate
+    actor.head launch (the fold needs H1 % 16 == 0).  Every row is still a whole number of float4s, so the
+    operands load by 16-B pieces; widths off the 4-grid (scalar operand loads) are tests/test_gpu_ragged.py's."""
     _one_step_compare("elu", hidden=(100, 60), seed=9)
 
 
@@ -344,7 +345,7 @@ def test_fused_forward_pair_bit_identical(gpu_available, monkeypatch, act, B, ea
 
 
 @pytest.mark.parametrize("S,A,B,clip", [(17, 6, 256, 0.0), (376, 17, 1024, 0.0), (17, 6, 64, 5.0)])
-def test_model_fit_folds_bit_identical(gpu_available, monkeypatch, S, A, B, clip):
+def test_model_fit_folds_bit_identical(gpu_available, monkeypatch, S, A, B, clip, model_hidden=(512, 512)):
     """The folded world-model fit chain (the loss and its gradient in model.fwd2's epilogue,
     k_mfinal as an extra workgroup of model.bwd2: SACX_MFUSE=1; the rows gathered on model.fwd0's
     operand loads: 2; model.bwd2 generated on model.bwd1's operand loads for heads of <= 32
@@ -368,9 +369,13 @@ def test_model_fit_folds_bit_identical(gpu_available, monkeypatch, S, A, B, clip
         monkeypatch.setenv("SACX_MT32", mt32)
         monkeypatch.setenv("SACX_MPRE", pre)
         eng, ocfg, st, buf, nrm, _ = make_pair(S=S, A=A, B=B, act="tanh", N=3000, seed=33, use_expert=True,
-                                               normalizers="random", model_max_grad_norm=clip)
+                                               normalizers="random", model_max_grad_norm=clip, model_hidden=model_hidden)
         names = [L["name"] for L in eng.model_plan_info()]
-        pair = f2 == "1" and S + A <= 32 and (fuse != "1" if pre == "0" else tile != "2")
+        print(f"fit folds {model_hidden} MFUSE={fuse} MTILE={tile} MFWD2={f2} MT32={mt32} MPRE={pre}: " + " ".join(names))
+        # (k_fwd2: layer 0 in 64-column groups up to 512, layer 1 in whole 16-column tiles; another width keeps
+        # the two launches)
+        pair = f2 == "1" and S + A <= 32 and (fuse != "1" if pre == "0" else tile != "2") and \
+            model_hidden[0] % 64 == 0 and model_hidden[0] <= 512 and model_hidden[1] % 16 == 0
         assert (("model.gather+fwd01" if pre == "0" else "model.fwd01") in names) == pair, names
         mb = eng.cfg.model_batch
         idx = np.random.RandomState(4).randint(buf["r"].shape[0], size=(steps, 2, mb))
@@ -418,11 +423,11 @@ def test_actor_act_matches_oracle(gpu_available, deterministic, per_state_std, n
 @pytest.mark.parametrize("S,A,act,per_state_std,n", [(376, 17, "tanh", False, 3), (376, 17, "relu", True, 1),
                                                       (17, 6, "elu", True, 16), (17, 6, "relu", False, 1),
                                                       (17, 6, "tanh", True, 1)])
-def test_actor_act_rows_shapes(gpu_available, S, A, act, per_state_std, n):
+def test_actor_act_rows_shapes(gpu_available, S, A, act, per_state_std, n, hidden=(256, 256)):
     """k_act_rows on both of its paths (the prefetching one, S <= 128 and H <= 256; the generic
     one, Humanoid S = 376), stochastic, vs the oracle; the device stream advances as NumPy's;
     repeats from the same stream state give the same action."""
-    eng, ocfg, st, buf, nrm, _ = make_pair(S=S, A=A, act=act, B=64, N=500, seed=43, normalizers="random",
+    eng, ocfg, st, buf, nrm, _ = make_pair(S=S, A=A, hidden=hidden, act=act, B=64, N=500, seed=43, normalizers="random",
                                            per_state_std=per_state_std)
     obs = np.random.RandomState(5).normal(size=(n, S)) * 2.0
     eng.rng_set_state(np.random.RandomState(19).get_state())

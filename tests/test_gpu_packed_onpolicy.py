@@ -31,18 +31,18 @@ PPO_LR = (1e-4, 3e-4, 2e-4)          # each learner's own rate (adaptlr makes th
 VC_LR = (1e-3, 5e-4, 2e-3)
 
 
-def make_engine(learners=0, vcritics=0, **kw):
+def make_engine(learners=0, vcritics=0, hidden=HID, acts=None, **kw):
     from sac_eo.engine import Engine, EngineConfig
     A = 3 if kw.get("softmax") else 2
-    return Engine(EngineConfig(s_dim=S, a_dim=A, hidden=HID, activation="tanh", critic_hidden=HID, batch=BATCH,
-                               buffer_capacity=CAP, actor_gaussian="train", graph_steps=1, vcritics=vcritics,
+    return Engine(EngineConfig(s_dim=S, a_dim=A, hidden=hidden, activation="tanh", actor_activations=acts, critic_hidden=hidden,
+                               batch=BATCH, buffer_capacity=CAP, actor_gaussian="train", graph_steps=1, vcritics=vcritics,
                                learners=learners, **kw))
 
 
-def learner(k, n_steps, mb, nc=0, softmax=False, per_state_std=False, layer_norm=False):
+def learner(k, n_steps, mb, nc=0, softmax=False, per_state_std=False, layer_norm=False, hidden=HID, acts=ACTS):
     """Everything learner k brings, decided on the CPU from its own seed."""
     A = 3 if softmax else 2
-    cfg = O.Config(S=S, A=A, hidden=HID, actor_acts=ACTS, per_state_std=per_state_std, layer_norm=layer_norm)
+    cfg = O.Config(S=S, A=A, hidden=hidden, actor_acts=acts, per_state_std=per_state_std, layer_norm=layer_norm)
     rng = np.random.RandomState(100 + 7 * k)
     st0 = R.init_state(cfg, seed=20 + k, logstd=(0.2 * rng.normal(size=A) - 0.3), gain=0.5, dt=np.float32)
     st = st0.copy()                                       # the policy a few updates after the rollout: r leaves 1
@@ -55,7 +55,7 @@ def learner(k, n_steps, mb, nc=0, softmax=False, per_state_std=False, layer_norm
     adv = (rng.normal(size=n) * 1.5 + 0.4).astype(np.float32)
     nrm = nontrivial_normalizers(rng, S, A)
     nrm.ret_den = np.float32(2.7 + k)
-    crit = V.init_state(S, HID, max(nc, 1), seed=40 + k, dt=np.float32)
+    crit = V.init_state(S, hidden, max(nc, 1), seed=40 + k, dt=np.float32)
     vn = [n - 2 * c for c in range(nc)]                   # the critics' tables differ in length too
     vs = [(rng.normal(size=(m, S)) * 1.3).astype(np.float32) for m in vn]
     vrtg = [(rng.normal(size=m) * 4 + 1).astype(np.float32) for m in vn]
@@ -117,25 +117,29 @@ PPO_CASES = {
     "ent_reg": (dict(), 9, 11, dict(max_grad_norm=None, ent_reg=True, alpha_lr=0.02, ent_targ=4.0)),
     "grad_clip": (dict(), 5, 11, dict(max_grad_norm=0.05)),
     "ring_wrap": (dict(), 5, 1100, dict(max_grad_norm=0.5)),
+    # two learners off the 4-grid: every row stride odd, the learners' blocks apart by the arena's own stride
+    "odd": (dict(hidden=(23, 41), acts=("tanh", "elu"), K=2), 5, 11, dict(max_grad_norm=None)),
 }
 
 
 def _eng_flags(flags):
     f = dict(flags)
+    f.pop("K", None)                                       # (the case's learner count: K unless it says so)
     if f.pop("layer_norm", False):
         f["actor_layer_norm"] = True
     return f
 
 
 def _run_packed_ppo(Ls, flags, par, eager=False):
-    pk = make_engine(learners=K, **_eng_flags(flags))
-    assert pk.seeds == K and pk.arena_all.numel() == K * pk.seed_stride
-    for k in reversed(range(K)):                           # (any order: each call addresses the selected learner)
+    nk = len(Ls)
+    pk = make_engine(learners=nk, **_eng_flags(flags))
+    assert pk.seeds == nk and pk.arena_all.numel() == nk * pk.seed_stride
+    for k in reversed(range(nk)):                          # (any order: each call addresses the selected learner)
         pk.select_seed(k)
         ppo_prepare(pk, Ls[k])
-    pk.ppo_steps_packed(np.stack([L["idx"] for L in Ls]), actor_lr=PPO_LR, eps_ppo=0.2, eager=eager, **par)
+    pk.ppo_steps_packed(np.stack([L["idx"] for L in Ls]), actor_lr=PPO_LR[:nk], eps_ppo=0.2, eager=eager, **par)
     ends = []
-    for k in range(K):
+    for k in range(nk):
         pk.select_seed(k)
         ends.append(pk.ppo_end(0.2))
     return pk, ends
@@ -144,9 +148,10 @@ def _run_packed_ppo(Ls, flags, par, eager=False):
 @pytest.mark.parametrize("case", list(PPO_CASES))
 def test_packed_ppo_steps_equal_the_one_learner_steps(gpu_available, case):
     flags, mb, n_steps, par = PPO_CASES[case]
-    Ls = [learner(k, n_steps, mb, **flags) for k in range(K)]
+    nk = flags.get("K", K)
+    Ls = [learner(k, n_steps, mb, **{a: b for a, b in flags.items() if a != "K"}) for k in range(nk)]
     pk, ends = _run_packed_ppo(Ls, flags, par)
-    for k in range(K):
+    for k in range(nk):
         one = make_engine(**_eng_flags(flags))
         ppo_prepare(one, Ls[k])
         one.ppo_steps(Ls[k]["idx"], actor_lr=PPO_LR[k], eps_ppo=0.2, **par)

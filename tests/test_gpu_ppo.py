@@ -31,6 +31,8 @@ SHAPES = {
     "layer_norm": dict(S=7, A=3, hidden=(64, 48), acts=("tanh", "relu"), layer_norm=True),
     "three": dict(S=7, A=3, hidden=(32, 48, 40), acts=("relu", "tanh", "elu")),
     "wide1": dict(S=7, A=3, hidden=(520,), acts=("tanh",)),
+    # widths off the 4-grid: every activation / delta row and W_ext row at an odd stride
+    "odd": dict(S=7, A=3, hidden=(23, 41), acts=("tanh", "elu")),
 }
 
 
@@ -105,7 +107,7 @@ def moved(st, cfg, seed, scale, floor_dim=False):
 
 # ---------------------------------------------------------------------------------------------- rows
 ROWS = [("pendulum", 1), ("pendulum", 17), ("pendulum", 300), ("halfcheetah", 313), ("pss17", 33), ("layer_norm", 33),
-        ("three", 33), ("wide1", 33)]
+        ("three", 33), ("wide1", 33), ("odd", 33)]
 
 
 @pytest.mark.parametrize("shape,n", ROWS)
@@ -148,6 +150,7 @@ STEP_CASES = {
     "wide_33": dict(shape="wide1", mb=33, n=50, par=dict(max_grad_norm=0.2), move=0.03, seed=7),
     "ent_reg": dict(shape="halfcheetah", mb=33, n=64, par=dict(max_grad_norm=0.5, ent_reg=True, alpha_lr=0.02,
                                                                  ent_targ=12.0), move=0.018, seed=22, steps=3),
+    "odd_17": dict(shape="odd", mb=17, n=40, par=dict(max_grad_norm=None), move=0.04, seed=11),
 }
 
 

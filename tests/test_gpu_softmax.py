@@ -33,6 +33,7 @@ NETS = {
     "ln": dict(hidden=(64, 48), acts=("tanh", "relu"), layer_norm=True),
     "three": dict(hidden=(32, 48, 40), acts=("relu", "tanh", "elu")),
     "wide1": dict(hidden=(520,), acts=("tanh",)),
+    "odd": dict(hidden=(23, 41), acts=("tanh", "elu")),      # widths off the 4-grid
 }
 
 
@@ -97,7 +98,8 @@ def bar_err(got, want):
 
 # ---------------------------------------------------------------------------------------------- rows
 ROWS = [("h64", (3, 17)[(i + j) % 2], A, n, None) for i, n in enumerate((1, 5, 313)) for j, A in enumerate((1, 2, 3, 17, 32))]
-ROWS += [("ln", 7, 3, 33, None), ("three", 7, 3, 33, None), ("wide1", 7, 3, 33, None), ("h64", 17, 17, 33, 80.0)]
+ROWS += [("ln", 7, 3, 33, None), ("three", 7, 3, 33, None), ("wide1", 7, 3, 33, None), ("h64", 17, 17, 33, 80.0),
+         ("odd", 7, 3, 33, None)]
 
 
 @pytest.mark.parametrize("net,S,A,n,span", ROWS)
@@ -149,6 +151,7 @@ STEP_CASES = {
     "a3_33_plain": dict(S=3, A=3, mb=33, n=50, par=dict(max_grad_norm=None, adv_center=False, adv_scale=False), move=0.1, seed=1),
     "ent_reg": dict(S=17, A=3, mb=33, n=64, par=dict(max_grad_norm=0.5, ent_reg=True, alpha_lr=0.02, ent_targ=2.0), move=0.1,
                     seed=1, steps=3),
+    "odd_17": dict(S=17, A=3, mb=17, n=40, net="odd", par=dict(max_grad_norm=None), move=0.2, seed=1),
 }
 _STEP_CACHE = {}
 
@@ -159,7 +162,7 @@ def step_case(name):
     if name in _STEP_CACHE:
         return _STEP_CACHE[name]
     c = STEP_CASES[name]
-    cfg, st0, nrm = make_state("h64", c["S"], c["A"], c["seed"])
+    cfg, st0, nrm = make_state(c.get("net", "h64"), c["S"], c["A"], c["seed"])
     s, a, adv = rollout(cfg, st0, nrm, c["n"], c["seed"])
     st = moved(st0, c["seed"], c["move"])
     rng = np.random.RandomState(c["seed"] + 31)
@@ -198,7 +201,7 @@ def test_one_minibatch_step(gpu_available, case):
     import torch
     k = step_case(case)
     c, cfg, par = k["c"], k["cfg"], k["par"]
-    eng = make_engine("h64", c["S"], c["A"], batch=c["mb"], capacity=c["n"])
+    eng = make_engine(c.get("net", "h64"), c["S"], c["A"], batch=c["mb"], capacity=c["n"])
     load(eng, k["st0"], k["nrm"])
     eng.set_logstd(np.full((1, c["A"]), 0.25, np.float32))      # no trainable here: it must come back as it is
     eng.v["grad"].fill_(3.0)                        # a reused arena: ppo_begin clears the gradient words it reads
@@ -355,13 +358,14 @@ NETS[THID] = dict(hidden=(24, 40), acts=("tanh", "tanh"))
 CHUNK = 4096
 
 
-@pytest.mark.parametrize("n", [33, CHUNK + 1])
-def test_trpo_gradient_and_fisher_product(gpu_available, n):
+@pytest.mark.parametrize("n,net,sub", [pytest.param(33, THID, 1, id="33"), pytest.param(CHUNK + 1, THID, 1, id=str(CHUNK + 1)),
+                                       pytest.param(100, "odd", 3, id="odd-100-3")])
+def test_trpo_gradient_and_fisher_product(gpu_available, n, net, sub):
     import torch
-    cfg, st, nrm = make_state(THID, TS, TA, seed=2)
+    cfg, st, nrm = make_state(net, TS, TA, seed=2)
     s, a, adv = rollout(cfg, st, nrm, n, seed=4)
-    kw = dict(trust_sub=1, trust_damp=0.05, ent_targ=0.5)
-    eng = make_engine(THID, TS, TA, batch=16, capacity=n, trpo=True)
+    kw = dict(trust_sub=sub, trust_damp=0.05, ent_targ=0.5)
+    eng = make_engine(net, TS, TA, batch=16, capacity=n, trpo=True)
     load(eng, st, nrm)
     eng.v["ppo.alpha"][0, 0] = 0.3                       # the entropy term takes part
     st.alpha = np.array(np.float64(np.float32(0.3)))
@@ -374,7 +378,7 @@ def test_trpo_gradient_and_fisher_product(gpu_available, n):
     rng = np.random.RandomState(7)
     x = [rng.normal(size=w.shape).astype(np.float32) for w in st.actor]
     got_f = eng.trpo_fvp(x)
-    want_f = SM.fvp(st, cfg, nrm, s, [np.asarray(v, np.float64) for v in x], kw["trust_damp"])
+    want_f = SM.fvp(st, cfg, nrm, s[::sub], [np.asarray(v, np.float64) for v in x], kw["trust_damp"])
     assert len(got_g) == len(got_f) == len(neg_pg) == 6
     errs = []
     for i, (g, f, ng, wf) in enumerate(zip(got_g, got_f, neg_pg, want_f)):
@@ -385,8 +389,8 @@ def test_trpo_gradient_and_fisher_product(gpu_available, n):
         errs.append((eg, ef))
     xf = eng.trpo_pack(x)
     f0, f1 = eng.trpo_fvp(xf), eng.trpo_fvp(xf, eager=True)
-    plan = eng.trpo_plan_info(n)
-    chunks = (n + CHUNK - 1) // CHUNK
+    plan = eng.trpo_plan_info((n + sub - 1) // sub)
+    chunks = ((n + sub - 1) // sub + CHUNK - 1) // CHUNK
     assert max(e[0] for e in errs) < 2e-4 and max(e[1] for e in errs) < 2e-4, errs
     assert torch.equal(f0, f1)
     assert [p["name"] for p in plan].count("trpo.acc") == chunks

@@ -38,6 +38,9 @@ SHAPES = {
     "three": dict(A=2, hidden=(24, 40, 20), acts=("relu", "tanh", "elu")),
     "ln": dict(A=2, hidden=(24, 40), acts=("tanh", "relu"), layer_norm=True),
     "pss": dict(A=2, hidden=(24, 40), acts=("tanh", "elu"), per_state_std=True, std_mult=0.8),
+    # widths off the 4-grid; the flat range is 1,282 floats, so the vectors' last float4 is half padding
+    # (tests/test_trpo_config.py holds that on the CPU)
+    "odd": dict(A=2, hidden=(23, 41), acts=("tanh", "elu")),
 }
 S = 3
 
@@ -89,7 +92,8 @@ def par_of(kw):
 
 
 # ------------------------------------------------------------------------------------- gradient, Fisher product
-GF = [("a1", 1, 1), ("a1", CHUNK + 1, 1), ("a2_floor", 100, 3), ("three", 100, 3), ("ln", CHUNK + 1, 3), ("pss", 100, 3)]
+GF = [("a1", 1, 1), ("a1", CHUNK + 1, 1), ("a2_floor", 100, 3), ("three", 100, 3), ("ln", CHUNK + 1, 3), ("pss", 100, 3),
+      ("odd", 100, 3)]
 
 
 @pytest.mark.parametrize("shape,n,sub", GF)

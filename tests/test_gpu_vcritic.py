@@ -29,6 +29,7 @@ SHAPES = {
     "two": dict(hidden=(64, 64), acts=("tanh", "tanh")),
     "three": dict(hidden=(32, 48, 40), acts=("relu", "tanh", "elu")),
     "wide1": dict(hidden=(520,), acts=("tanh",)),
+    "odd": dict(hidden=(23, 41), acts=("tanh", "elu")),      # widths off the 4-grid
 }
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gae_ref.npz")
 
@@ -235,6 +236,7 @@ STEP_CASES = {
     "two_8_17": dict(S=3, shape="two", nc=8, mb=17, n=[17, 20, 18, 25, 19, 17, 30, 21]),   # 24: three
     "three_3_17": dict(S=17, shape="three", nc=3, mb=17, n=[40, 64, 33]),
     "wide_2_16": dict(S=7, shape="wide1", nc=2, mb=16, n=[16, 30]),
+    "odd_2_17": dict(S=17, shape="odd", nc=2, mb=17, n=[40, 33]),
 }
 
 

@@ -232,12 +232,12 @@ def test_bc_trajectory_wide(gpu_available, monkeypatch):
     eng.close()
 
 
-def test_packed_seeds_wide(gpu_available):
+def test_packed_seeds_wide(gpu_available, hidden=(64, 1024)):
     """seeds = 2, hidden (64, 1024): each seed's 10-update statistics, parameters, second moments and
-    RNG key bit-identical to the same learner run alone (test_packed_seeds_equal_single's comparison)."""
+    RNG key bit-identical to the same learner run alone (test_packed_seeds_equal_single's comparison).
+    hidden: another caller's widths (tests/test_gpu_ragged.py)."""
     from sac_eo.engine import Engine, EngineConfig
     n, B, N, K = 10, 64, 2000, 2
-    hidden = (64, 1024)
     learners = [make_learner(hidden=hidden, act="tanh", B=B, N=N, seed=40 + 7 * k) for k in range(K)]
 
     def cfg(seeds):

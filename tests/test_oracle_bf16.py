@@ -20,6 +20,7 @@ leaving out flip_cap elements, none of which lay beyond a bar):
   pss_ln    2.7e-07   2.7e-07  8.3e-08    5.0e-08   1.0
   generic   3.4e-07   2.3e-07  3.6e-04    2.0e-08   7.1  (grad.q0.0)
   wide_k0   2.3e-07   2.6e-07  2.0e-05    5.0e-08   1.0
+  off4_bf16 2.8e-07   2.6e-07  1.9e-05    5.3e-08   1.0  (hidden (63, 65): tests/test_gpu_ragged.py)
   hc, Q1 / Q2 over 30 updates: 3.8e-05 (bar 1.5e-04)
   world-model fit: first-step gradients 1.9e-04 (3.9, grad.m0.2), three losses 6.5e-07; object calls on
   64 rows <= 3e-07 (nothing left out); one rollout step <= 1.1e-07 (no element beyond a bar)

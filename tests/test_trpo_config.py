@@ -57,6 +57,19 @@ def test_without_the_init_call_the_layout_is_the_parents():
     lib.sacx_destroy(h)
 
 
+def test_the_odd_shapes_flat_range_is_no_whole_number_of_float4s():
+    """tests/test_gpu_trpo.py's "odd" shape (S = 3, A = 2, hidden (23, 41)): the flat range actor.l0 ..
+    actor.logstd is 1,282 floats, so trpo.vec's rows are padded (k_trpo_cg / k_trpo_acc walk them by float4)."""
+    lib, h, rc, msg = _create(_cfg(s_dim=3, a_dim=2, hidden=(23, 41), actor_activations=("tanh", "elu"), batch=16,
+                                   buffer_capacity=100).to_c())
+    assert rc == 0, msg
+    assert lib.sacx_trpo_init(h) == 0, lib.sacx_last_error(h)
+    segs = _layout(lib, h)
+    nv = (segs["actor.logstd"][0] + 4 * segs["actor.logstd"][2] - segs["actor.l0"][0]) // 4
+    assert nv % 4 != 0 and segs["trpo.vec"][2] == nv + 4 - nv % 4, (nv, segs["trpo.vec"])
+    lib.sacx_destroy(h)
+
+
 @pytest.mark.parametrize("order", ["trpo_first", "vcritic_first"])
 def test_with_vcritics_in_either_order_every_earlier_segment_keeps_its_offset(order):
     lib, h0, rc, msg = _create(_cfg().to_c())
