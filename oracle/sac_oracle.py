@@ -714,7 +714,10 @@ def sac_update(st: SACState, cfg: Config, nrm: Normalizers, batch, noise_t, nois
     grads_a = actor_backward(actor_all, X, Hs, dout_a, cfg)
     if keep is not None:
         keep.update(actor_h_p=hs_p, mu_p=mu_p, ls_p=ls_p, a_p=a_p, nlp_p=nlp_p, q1p=q1p, q2p=q2p,
-                    dxa=dxa, dmu=DMU, dl=DL, actor_grads=grads_a, g_logstd=g_logstd)
+                    dxa=dxa, dmu=DMU, dl=DL, actor_grads=grads_a, g_logstd=g_logstd,
+                    # the head caches (x, t, std, u, clip mask) of the policy rows and of each expert section:
+                    # arrays of their own, where ls_p is a view of st.logstd that Adam moves below
+                    head_p=cache_p, head_e=[c_[2] for c_ in caches] if expert is not None else [])
     stats["p_loss"] = float(p_loss)
     adam_step(st.actor + [st.logstd], hook("actor", grads_a + [g_logstd]), st.opt_actor, cfg.lr_pi, dt)
 

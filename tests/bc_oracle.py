@@ -27,7 +27,7 @@ def bc_sections(perm, num_models):
 def bc_update(st, cfg, nrm, halves, mnrm=None, keep=None):
     """One ``BC._update_actor`` in place on ``st``.  ``halves``: [(s_e, sp_e, noise)] of the one or two
     sections (model k takes halves[k]); ``mnrm``: the world models' normaliser (None: ``nrm``).
-    Returns {"mse_loss"}; ``keep`` receives actor_grads / g_logstd."""
+    Returns {"mse_loss"}; ``keep`` receives actor_grads / g_logstd / heads (the sections' head caches)."""
     dt = st.alpha.dtype.type
     F = lambda x: O._F(dt, x)
     nrm = nrm.cast(dt)
@@ -72,7 +72,7 @@ def bc_update(st, cfg, nrm, halves, mnrm=None, keep=None):
         dout_a, g_logstd = DMU, DL.sum(axis=0, keepdims=True)
     grads = O.actor_backward(st.actor, X, Hs, dout_a, cfg)
     if keep is not None:
-        keep.update(actor_grads=grads, g_logstd=g_logstd)
+        keep.update(actor_grads=grads, g_logstd=g_logstd, heads=[c[2] for c in caches])
     O.adam_step(st.actor + [st.logstd], grads + [g_logstd], st.opt_actor, cfg.lr_pi, dt)
     return {"mse_loss": float(mse)}
 

@@ -18,6 +18,8 @@ import os
 import numpy as np
 import pytest
 
+import edge_cases as EC
+import helpers
 import sac_oracle as O
 import test_gpu_loop as L
 from bc_oracle import BCLoopOracle, bc_sections, bc_update
@@ -25,6 +27,7 @@ from helpers import B1, make_pair, nontrivial_normalizers, relerr
 from test_gpu_depth import _adam_grads, _same_stream
 
 pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
 
 CASES = {
     # halves of 6: a partial 16-row tile
@@ -47,6 +50,9 @@ CASES = {
     # the folded plan with every fold (k_fwd2 pairs, folded head backward, folded finalisation)
     "hc": dict(hidden=(256, 256), model_hidden=(512, 512), ne=20, B=256),
     "hc_generic": dict(hidden=(256, 256), model_hidden=(512, 512), ne=20, B=256, generic=True),
+    # the log-std variable below, at, inside and above its clip bounds [-5, 2] (tests/edge_cases.py): the
+    # mask of the sample rows, with no entropy term beside it
+    "lsvar": dict(hidden=(64, 64), model_hidden=(96, 96), ne=12, edge="lsvar"),
 }
 
 
@@ -55,6 +61,9 @@ def _pair(monkeypatch, case, seed=0, **over):
     kw.update(over)
     generic = kw.pop("generic", False)
     mnorm = kw.pop("mnorm", False)
+    edge = kw.pop("edge", None)
+    if edge:                               # make_pair resolves make_learner through its module
+        monkeypatch.setattr(helpers, "make_learner", EC.mutating(helpers.make_learner, EC.split(edge)[0]))
     kw.setdefault("act", "relu")
     kw.setdefault("B", 64)
     if generic:
@@ -118,6 +127,11 @@ def test_bc_one_update(gpu_available, monkeypatch, case):
     ctl0 = eng.ctl()
     alpha0 = eng.alpha()
     keep = {}
+    ls0 = st.logstd.copy()
+    edge = "edge" in CASES[case]
+    if edge:                               # the update must write its rows of the mask: none of them holds 7
+        eng.v["ws.c_mask"].fill_(7.0)
+        torch.cuda.synchronize()           # the fill runs on torch's stream, the update on the engine's
     ref = bc_update(st, ocfg, nrm, halves, mn, keep=keep)
     if ocfg.delta_clip_pred:               # the case's premise: some columns clipped, not all
         frac = _clip_fraction(st, ocfg, nrm, halves)
@@ -151,6 +165,23 @@ def test_bc_one_update(gpu_available, monkeypatch, case):
     for a_, b_ in zip(eng.get_net("actor"), st.actor):
         assert np.max(np.abs(a_ - b_)) < 1e-6
     assert np.max(np.abs(eng.v["actor.logstd"].cpu().numpy() - st.logstd)) < 1e-6
+    if edge:
+        # the sample rows' clip mask (the update's rows of ws.c_mask, wherever the plan keeps them) equal to the
+        # oracle's; the masked coordinates of the log-std variable: gradient exactly 0, not moved by Adam
+        mask = np.concatenate([h.mask for h in keep["heads"]], 0)
+        masked = EC.clip_mask(ls0[0]) == 0
+        assert (mask == 0).any() and (mask == 1).any() and masked.any() and not masked.all()
+        dev = eng.v["ws.c_mask"].cpu().numpy()
+        rows = np.where((dev != 7.0).any(axis=1))[0]
+        assert len(rows) == len(mask) and np.array_equal(rows, rows[0] + np.arange(len(mask))), rows
+        assert np.array_equal(dev[rows], mask), (dev[rows], mask)
+        gl = _moment(eng, "actor.logstd")[0]
+        assert np.all(gl[masked] == 0.0) and np.all(keep["g_logstd"][0][masked] == 0.0), gl
+        assert np.all(gl[~masked] != 0.0), gl
+        ls = eng.v["actor.logstd"].cpu().numpy().reshape(-1)
+        assert np.array_equal(ls[masked], ls0[0][masked].astype(np.float32)), (ls, ls0)
+        print(f"{case}: mask rows {rows[0]}..{rows[-1]}, zeros {int((mask == 0).sum())} of {mask.size}; g_logstd {gl} "
+              f"error {relerr(gl, keep['g_logstd'][0]):.2e} (held to 2e-4 by the comparison above)")
     # critics, targets, alpha, world models: weights and moments byte for byte
     for (name, x), (_, y) in zip(before, _others(eng)):
         assert np.array_equal(x, y), name
